@@ -2,7 +2,7 @@
 """
 bench.py -- headline benchmark of the self-play rollout path on MI355X (contract: see the task statement).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Metric (BASELINE.json): MCTS nodes/sec (+ self-play plies / games per hour) at 800 simulations per move
@@ -55,8 +55,8 @@ NETS = {"4x64": (3, 1, 64), "10x128": (8, 2, 128), "20x256": (15, 5, 256)}
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (plies of every game; default 20, --fast: 1)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 3, --fast: 0)")
     ap.add_argument("--games", type=int, default=None, help="concurrent games per GPU (default 256; --fast: 32768)")
     ap.add_argument("--sims", type=int, default=None, help="simulations per move (default 800; --fast: 128)")
     ap.add_argument("--batch", type=int, default=96)
@@ -84,6 +84,8 @@ def parse():
                          "step kernel then finishes the value head too, bo_step_heads -- same bits, same speed: profiles/r05_device_turn_and_tiles.md section 6)")
     ap.add_argument("--exchange-every", type=int, default=16, help="N>1: plies per record-exchange period")
     ap.add_argument("--dump-games", default="", help="write the move lists of finished games to this JSON file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--wide-trees", type=int, default=0, help="0 = 262144 if >= 150 GB of HBM is free, else 131072")
     ap.add_argument("--wide-nodes", type=int, default=800)
     ap.add_argument("--fast", action="store_true", help="FAST search mode (virtual loss; not the reference's semantics; not the headline)")
@@ -112,8 +114,12 @@ def parse():
         args.cohorts = next((k for k in (4, 2) if args.games % k == 0 and args.games // k >= 64), 1)
     if args.cohorts < 1 or args.games % args.cohorts or (args.fast and args.cohorts > 1):
         ap.error("--cohorts must divide --games (and is 1 with --fast)")
-    if args.fast and args.steps == 20 and args.warmup == 3:
-        args.steps, args.warmup = 1, 0  # (a ply of 32768 games x 800 simulations is 26 M evaluations: ~12 s)
+    if args.steps is None:
+        args.steps = 1 if args.fast else 20  # (--fast: a ply of 32768 games x 800 simulations is 26 M evaluations: ~12 s)
+    if args.warmup is None:
+        args.warmup = 0 if args.fast else 3
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.fast and args.opening_steps == 20:
         args.opening_steps = 0          # (the opening-only extra would be twenty such plies)
     if args.long_run_steps is None:     # ~5.5 s of the default workload; off for other workloads, N > 1 and with measurement switches off
@@ -601,6 +607,7 @@ class Driver:
         self.batch, self.n_finished, self.plies_finished, self.lengths = [], 0, 0, []
         self.n_received = 0
         self.exchange_seconds = 0.0
+        self.finished_in_step = {}  # slot -> FinishedGame handed over during the current step (dump_outputs)
 
     def new_id(self):
         i = self.next_id
@@ -612,6 +619,7 @@ class Driver:
         self.n_finished += 1
         self.plies_finished += len(fin.moves)
         self.lengths.append(len(fin.moves))
+        self.finished_in_step[fin.slot] = fin
         if self.dump is not None:
             self.dump.append({"game_id": fin.game_id, "terminal": fin.terminal, "moves": [int(m) for m in fin.moves]})
 
@@ -621,6 +629,7 @@ class Driver:
 
     def step(self):
         self.extra_steps = 0  # (evaluate -> step iterations run by a measurement since the last ply)
+        self.finished_in_step = {}
         self.ro.play_ply(on_finished=self.on_finished, refill=self.refill, while_searching=self.hand_over)
 
     def hand_over(self):
@@ -649,6 +658,52 @@ class Driver:
             slots = list(range(started, G))
             ids = [self.new_id() for _ in slots]
             ro.start_games(slots, ids, ids)
+
+
+DUMP_MAX_ROWS = 2048  # pi rows written by dump_outputs: 2048 x 4672 float32 = 38 MB, the whole dump stays under 64 MB
+
+
+def dump_outputs(out_dir, ro, drv, rank=0):
+    """--dump-outputs: what the LAST timed step computed, as a caller of the path receives it -- the search's pi of every game
+    that searched in that step (a game that ended with that step's move included).  Rows are keyed by (game id, ply) and sorted, not
+    by slot: with cohorts, the slot a refilled game lands in follows the order in which the cohorts finish, while what a game
+    plays depends only on its id.  More than DUMP_MAX_ROWS searches (--fast): a fixed sample (RandomState(0)) of the sorted rows.
+
+      game_id.npy   float64 [N]        the game that searched
+      ply.npy       float64 [N]        moves the game had played before that search
+      pi.npy        float32 [N, 4672]  the search's pi (visit-count distribution over the actions), dense
+    Rank r > 0 of an N > 1 run writes <name>.rank<r>.npy."""
+    from betaone_amd import engine as E
+
+    rows = []
+    for k, p in enumerate(getattr(ro, "parts", [ro])):
+        last = p._hist.get(p._step - 1)  # (went[G], n[G], idx[G, K], val[G, K]) of the cohort's last ply
+        if last is None:
+            continue
+        went, n, idx, val = last
+        for g in np.nonzero(went)[0]:
+            gs = p.games[g]
+            if gs is not None and p._start_step[g] < p._step:  # the game that searched is still in its slot
+                gid, ply = gs.game_id, int(p._plies[g]) - 1
+            else:  # it ended with that move and was handed over (CohortRollout: the slot has been refilled since)
+                fin = drv.finished_in_step[k * p.G + int(g)]
+                gid, ply = fin.game_id, len(fin.moves) - 1
+            rows.append((int(gid), ply, idx[g, :n[g]], val[g, :n[g]]))
+    if not rows:
+        raise RuntimeError("--dump-outputs: no game searched in the last timed step")
+    rows.sort(key=lambda r: (r[0], r[1]))
+    pick = np.arange(len(rows))
+    if len(rows) > DUMP_MAX_ROWS:
+        pick = np.sort(np.random.RandomState(0).choice(len(rows), DUMP_MAX_ROWS, replace=False))
+    pi = np.zeros((len(pick), E.NUM_ACTIONS), dtype=np.float32)
+    for i, j in enumerate(pick):
+        pi[i, rows[j][2]] = rows[j][3]
+    arrays = {"game_id": np.array([rows[j][0] for j in pick], dtype=np.float64),
+              "ply": np.array([rows[j][1] for j in pick], dtype=np.float64),
+              "pi": pi}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
 
 
 def main():
@@ -753,6 +808,8 @@ def main():
             if t0 <= b_ <= step_end[min(1, len(step_end) - 1)]:
                 print(f"[ply trace] {(a_ - t0) * 1e6:8.0f} -> {(b_ - t0) * 1e6:8.0f} us  cohort {who}  {name}", file=sys.stderr, flush=True)
     gc.enable()
+    if args.dump_outputs:  # (before anything after the timed steps plays on: the state is the last timed step's)
+        dump_outputs(args.dump_outputs, ro, drv, rank)
     timed = None
     if timing_on:  # the tower launches of the timed region, timed by the kernel itself
         khz = C_INT32(0)
