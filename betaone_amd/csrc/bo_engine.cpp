@@ -24,6 +24,7 @@
 
 #include <math.h>
 #include <stdio.h>
+#include <string.h>
 #include <string>
 #include <vector>
 #include <algorithm>
@@ -1613,6 +1614,8 @@ struct bo_tower_s {
     float *params = nullptr;
     bo_tower_layer *layers = nullptr;
     int *overflow = nullptr;  // BO_TOWER_SPLIT_F16: an activation left the fp16 range
+    int64_t n_weights = 0, n_params = 0;
+    std::vector<bo_tower_layer_desc> host_layers;  // (bo_nn_tower_pair_check compares two towers' descriptors)
 };
 #else
 struct bo_tower_s { int unused; };
@@ -1679,6 +1682,8 @@ extern "C" int bo_nn_tower_create(const bo_tower_layer_desc *layers, int n_layer
     bo_tower_s *t = new bo_tower_s();
     t->channels = C; t->n_layers = n_layers; t->n_cu = prop.multiProcessorCount; t->device = device; t->algo = algo;
     if (head) { t->head_channels = head->channels; t->head_split = head->split; t->head_w_off = head->w_off; t->head_b_off = head->b_off; }
+    t->n_weights = n_weights; t->n_params = n_params;
+    t->host_layers.assign(layers, layers + n_layers);
     int rc = (int)hipMalloc((void **)&t->wts, (size_t)n_weights * 4);
     if (!rc) rc = (int)hipMalloc((void **)&t->params, (size_t)n_params * 4);
     if (!rc) rc = (int)hipMalloc((void **)&t->layers, (size_t)n_layers * sizeof(bo_tower_layer));
@@ -1770,11 +1775,11 @@ static int tower_forward_impl(bo_tower *t, const float *x_dev, float *y_dev, voi
         if (t->algo == BO_TOWER_SPLIT_F16_T16)  // the same products as 16x16x32 tiles (bo_tower_s16.h: the chip holds a higher clock under them)
             // (weight fragments 6 K-steps = 24 KiB per wave ahead; 12 ahead needs all 512 registers + 12 spilled and measured 185 us
             // against 179 for a lone 64-board launch: profiles/r05_device_turn_and_tiles.md)
-            hipLaunchKernelGGL((bo_k_tower_s16<6>), dim3(grid), dim3(256), 0, st, x_dev, w8, t->params, t->layers, t->n_layers, y_dev, batch, hs);
-        else if (t->channels == 256 && ar256 == 8) hipLaunchKernelGGL((bo_k_tower_s<256, 2, 1, 8>), dim3(grid), dim3(256), 0, st, x_dev, w8, t->params, t->layers, t->n_layers, y_dev, batch, hs);
-        else if (t->channels == 256) hipLaunchKernelGGL((bo_k_tower_s<256, 2, 1, 4>), dim3(grid), dim3(256), 0, st, x_dev, w8, t->params, t->layers, t->n_layers, y_dev, batch, hs);
+            hipLaunchKernelGGL((bo_k_tower_s16<6>), dim3(grid), dim3(256), 0, st, x_dev, w8, t->params, t->layers, t->n_layers, y_dev, batch, hs, bo_tower_pair{});
+        else if (t->channels == 256 && ar256 == 8) hipLaunchKernelGGL((bo_k_tower_s<256, 2, 1, 8>), dim3(grid), dim3(256), 0, st, x_dev, w8, t->params, t->layers, t->n_layers, y_dev, batch, hs, bo_tower_pair{});
+        else if (t->channels == 256) hipLaunchKernelGGL((bo_k_tower_s<256, 2, 1, 4>), dim3(grid), dim3(256), 0, st, x_dev, w8, t->params, t->layers, t->n_layers, y_dev, batch, hs, bo_tower_pair{});
         else  // (B operands read two K-steps ahead, weight fragments requested twelve ahead: profiles/r03_split_tower.md)
-            hipLaunchKernelGGL((bo_k_tower_s<128, 1, 2, 12>), dim3(grid), dim3(256), 0, st, x_dev, w8, t->params, t->layers, t->n_layers, y_dev, batch, hs);
+            hipLaunchKernelGGL((bo_k_tower_s<128, 1, 2, 12>), dim3(grid), dim3(256), 0, st, x_dev, w8, t->params, t->layers, t->n_layers, y_dev, batch, hs, bo_tower_pair{});
         RT((int)hipGetLastError());
         return BO_OK;
     }
@@ -1786,6 +1791,56 @@ static int tower_forward_impl(bo_tower *t, const float *x_dev, float *y_dev, voi
         hipLaunchKernelGGL((bo_k_tower<128>), dim3(grid), dim3(256), 0, st, x_dev, t->wts, t->params, t->layers, t->n_layers, y_dev, batch);
     else
         hipLaunchKernelGGL((bo_k_tower<64>), dim3(grid), dim3(128), 0, st, x_dev, t->wts, t->params, t->layers, t->n_layers, y_dev, batch);
+    RT((int)hipGetLastError());
+    return BO_OK;
+#endif
+}
+
+// ---- two nets in one launch of the split-precision tower (a match: row b evaluated by the net of its game's side to move) --------
+extern "C" int bo_nn_tower_pair_check(bo_tower *t0, bo_tower *t1) {
+#if defined(BO_WAVE_EMU)
+    (void)t0; (void)t1;
+    return fail(BO_E_CONFIG, "bo_nn_tower is a gfx950-only kernel");
+#else
+    if (!t0 || !t1) return fail(BO_E_ARG, "null tower");
+    if (t0->algo != t1->algo || (t0->algo != BO_TOWER_SPLIT_F16 && t0->algo != BO_TOWER_SPLIT_F16_T16))
+        return fail(BO_E_CONFIG, "bo_nn_tower_forward_pair: both towers must be BO_TOWER_SPLIT_F16 or both BO_TOWER_SPLIT_F16_T16");
+    if (t0->device != t1->device) return fail(BO_E_CONFIG, "bo_nn_tower_forward_pair: the two towers live on different devices");
+    if (t0->channels != t1->channels || t0->n_layers != t1->n_layers || t0->n_weights != t1->n_weights || t0->n_params != t1->n_params)
+        return fail(BO_E_CONFIG, "bo_nn_tower_forward_pair: the two towers differ in channels, layers or buffer sizes");
+    if (t0->head_channels != t1->head_channels || t0->head_split != t1->head_split || t0->head_w_off != t1->head_w_off || t0->head_b_off != t1->head_b_off)
+        return fail(BO_E_CONFIG, "bo_nn_tower_forward_pair: the two towers' head descriptors differ");
+    if (t0->head_channels == 0) return fail(BO_E_CONFIG, "bo_nn_tower_forward_pair: the towers need their fused head convolutions");
+    if (memcmp(t0->host_layers.data(), t1->host_layers.data(), t0->host_layers.size() * sizeof(bo_tower_layer_desc)) != 0)
+        return fail(BO_E_CONFIG, "bo_nn_tower_forward_pair: the two towers' layer descriptors differ");
+    return BO_OK;
+#endif
+}
+
+extern "C" int bo_nn_tower_forward_pair(bo_tower *t0, bo_tower *t1, const int32_t *sel_dev, const float *x_dev, void *head_a_dev,
+                                        void *head_b_dev, int batch, void *stream) {
+#if defined(BO_WAVE_EMU)
+    (void)t0; (void)t1; (void)sel_dev; (void)x_dev; (void)head_a_dev; (void)head_b_dev; (void)batch; (void)stream;
+    return fail(BO_E_CONFIG, "bo_nn_tower is a gfx950-only kernel");
+#else
+    if (int rc = bo_nn_tower_pair_check(t0, t1)) return rc;
+    if (!sel_dev || !x_dev || batch < 1) return fail(BO_E_ARG, "bad arguments");
+    if ((t0->head_split > 0 && !head_a_dev) || (t0->head_split < t0->head_channels && !head_b_dev)) return fail(BO_E_ARG, "head output buffers missing");
+    bo_tower_head_s hs;
+    hs.channels = t0->head_channels; hs.split = t0->head_split; hs.w_off8 = t0->head_w_off; hs.b_off = t0->head_b_off;
+    hs.out_a = (float *)head_a_dev; hs.out_b = (float *)head_b_dev; hs.overflow = t0->overflow;
+    bo_tower_pair pr;
+    pr.sel = sel_dev; pr.wts1 = reinterpret_cast<const bo_h8 *>(t1->wts); pr.params1 = t1->params; pr.overflow1 = t1->overflow;
+    const unsigned grid = (unsigned)(batch < t0->n_cu ? batch : t0->n_cu);
+    hipStream_t st = (hipStream_t)stream;
+    const bo_h8 *w8 = reinterpret_cast<const bo_h8 *>(t0->wts);
+    // the single-net launch's instances with PAIR = true (bo_nn_tower_forward: why these ring depths)
+    if (t0->algo == BO_TOWER_SPLIT_F16_T16)
+        hipLaunchKernelGGL((bo_k_tower_s16<6, true>), dim3(grid), dim3(256), 0, st, x_dev, w8, t0->params, t0->layers, t0->n_layers, nullptr, batch, hs, pr);
+    else if (t0->channels == 256)
+        hipLaunchKernelGGL((bo_k_tower_s<256, 2, 1, 4, true>), dim3(grid), dim3(256), 0, st, x_dev, w8, t0->params, t0->layers, t0->n_layers, nullptr, batch, hs, pr);
+    else
+        hipLaunchKernelGGL((bo_k_tower_s<128, 1, 2, 12, true>), dim3(grid), dim3(256), 0, st, x_dev, w8, t0->params, t0->layers, t0->n_layers, nullptr, batch, hs, pr);
     RT((int)hipGetLastError());
     return BO_OK;
 #endif
@@ -2059,9 +2114,93 @@ extern "C" int bo_nn_heads(const void *p_dev, const void *v_dev, const float *wp
     a.B = batch; a.softmax = flags & 1; a.pb = bo_heads_policy_boards(batch);
     const int otw = 4 / (a.pb >> 5);
     const unsigned tiles = (unsigned)(((batch + a.pb - 1) / a.pb) * ((BO_HEADS_NA / 32 + otw - 1) / otw) + ((batch + 63) / 64) * 4 * BO_HEADS_KS);
-    if (flags & 2) hipLaunchKernelGGL(bo_k_heads_tiles<true>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);   // fp16 head planes
-    else hipLaunchKernelGGL(bo_k_heads_tiles<false>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
+    if (flags & 2) hipLaunchKernelGGL(bo_k_heads_tiles<true>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a, bo_heads_pair{});   // fp16 head planes
+    else hipLaunchKernelGGL(bo_k_heads_tiles<false>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a, bo_heads_pair{});
     if (!(flags & 4)) hipLaunchKernelGGL(bo_k_heads_rows, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);  // (4: bo_step_heads is the rows' consumer)
+    RT((int)hipGetLastError());
+    return BO_OK;
+#endif
+}
+
+// the same with two nets' float32 head weights, row b on the net sel_dev[b] names (bo_heads.h: bo_heads_pair)
+extern "C" int bo_nn_heads_pair(const void *p_dev, const void *v_dev, const bo_head_weights *net0, const bo_head_weights *net1,
+                                const int32_t *sel_dev, float *policy_out_dev, float *value_out_dev, float *scratch_dev, int batch, int flags,
+                                void *stream) {
+#if defined(BO_WAVE_EMU)
+    (void)p_dev; (void)v_dev; (void)net0; (void)net1; (void)sel_dev; (void)policy_out_dev; (void)value_out_dev; (void)scratch_dev; (void)batch;
+    (void)flags; (void)stream;
+    return fail(BO_E_CONFIG, "bo_nn_heads_pair is a gfx950-only kernel");
+#else
+    if (!p_dev || !v_dev || !net0 || !net1 || !sel_dev || !policy_out_dev || !value_out_dev || !scratch_dev) return fail(BO_E_ARG, "null argument");
+    for (const bo_head_weights *w : {net0, net1})
+        if (!w->wp || !w->bp || !w->w1 || !w->b1 || !w->w2 || !w->b2) return fail(BO_E_ARG, "null head weight");
+    if (flags & ~3) return fail(BO_E_ARG, "bo_nn_heads_pair: flags 1 (softmax) and 2 (fp16 planes) only");
+    if (batch < 1 || batch > 65536) return fail(BO_E_ARG, "bo_nn_heads_pair: 1 <= batch <= 65536");
+    bo_heads_args a;
+    a.p = p_dev; a.v = v_dev; a.wp = net0->wp; a.bp = net0->bp; a.w1 = net0->w1; a.b1 = net0->b1; a.w2 = net0->w2; a.b2 = net0->b2;
+    a.policy_out = policy_out_dev; a.value_out = value_out_dev;
+    a.vpart = scratch_dev;
+    a.B = batch; a.softmax = flags & 1; a.pb = bo_heads_policy_boards(batch);
+    bo_heads_pair q;
+    q.sel = sel_dev; q.wp = net1->wp; q.bp = net1->bp; q.w1 = net1->w1; q.b1 = net1->b1; q.w2 = net1->w2; q.b2 = net1->b2;
+    const int otw = 4 / (a.pb >> 5);
+    const unsigned tiles = (unsigned)(((batch + a.pb - 1) / a.pb) * ((BO_HEADS_NA / 32 + otw - 1) / otw) + ((batch + 63) / 64) * 4 * BO_HEADS_KS);
+    if (flags & 2) hipLaunchKernelGGL((bo_k_heads_tiles<true, true>), dim3(tiles), dim3(256), 0, (hipStream_t)stream, a, q);
+    else hipLaunchKernelGGL((bo_k_heads_tiles<false, true>), dim3(tiles), dim3(256), 0, (hipStream_t)stream, a, q);
+    hipLaunchKernelGGL(bo_k_heads_rows_pair, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a, q);
+    RT((int)hipGetLastError());
+    return BO_OK;
+#endif
+}
+
+#if !defined(BO_WAVE_EMU)
+// out[b] = sel[b] ? (logits1, value1)[b] : (logits0, value0)[b]; one workgroup per row
+__global__ void __launch_bounds__(256)
+bo_k_merge_rows(const int32_t *__restrict__ sel, const float *__restrict__ l0, const float *__restrict__ v0, const float *__restrict__ l1,
+                const float *__restrict__ v1, float *__restrict__ lo, float *__restrict__ vo, int width) {
+    const int b = (int)blockIdx.x;
+    const bool one = __builtin_amdgcn_readfirstlane(sel[b]) != 0;
+    const float *src = (one ? l1 : l0) + (size_t)b * width;
+    float *dst = lo + (size_t)b * width;
+    for (int i = threadIdx.x; i < width; i += blockDim.x) dst[i] = src[i];
+    if (threadIdx.x == 0) vo[b] = (one ? v1 : v0)[b];
+}
+
+// sel[g] = net_of_white[g] ^ (the root of slot g has black to move); slots past the root stack's capacity keep net_of_white
+__global__ void bo_k_match_select(Eng e, const int32_t *__restrict__ net_of_white, int32_t *__restrict__ sel) {
+    const int g = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (g >= e.c.G) return;
+    const int ply = e.ply[g];
+    const bool black = ply >= 0 && ply < e.c.PLY_CAP && !(e.gpos[(size_t)g * e.c.PLY_CAP + ply].flags & F_TURN);
+    sel[g] = (net_of_white[g] != 0) ^ (black ? 1 : 0);
+}
+#endif
+
+extern "C" int bo_nn_merge_rows(const int32_t *sel_dev, const float *logits0_dev, const float *value0_dev, const float *logits1_dev,
+                                const float *value1_dev, float *logits_out_dev, float *value_out_dev, int batch, int width, void *stream) {
+#if defined(BO_WAVE_EMU)
+    (void)sel_dev; (void)logits0_dev; (void)value0_dev; (void)logits1_dev; (void)value1_dev; (void)logits_out_dev; (void)value_out_dev;
+    (void)batch; (void)width; (void)stream;
+    return fail(BO_E_CONFIG, "bo_nn_merge_rows is a gfx950-only kernel");
+#else
+    if (!sel_dev || !logits0_dev || !value0_dev || !logits1_dev || !value1_dev || !logits_out_dev || !value_out_dev) return fail(BO_E_ARG, "null argument");
+    if (batch < 1 || batch > (1 << 22) || width < 1 || width > (1 << 16)) return fail(BO_E_ARG, "bo_nn_merge_rows: 1 <= batch <= 2^22, 1 <= width <= 65536");
+    hipLaunchKernelGGL(bo_k_merge_rows, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, sel_dev, logits0_dev, value0_dev, logits1_dev,
+                       value1_dev, logits_out_dev, value_out_dev, width);
+    RT((int)hipGetLastError());
+    return BO_OK;
+#endif
+}
+
+extern "C" int bo_match_select(bo_engine *e, const int32_t *net_of_white_dev, int32_t *sel_dev, void *stream) {
+#if defined(BO_WAVE_EMU)
+    (void)e; (void)net_of_white_dev; (void)sel_dev; (void)stream;
+    return fail(BO_E_CONFIG, "bo_match_select is a gfx950-only kernel");
+#else
+    if (!e || !net_of_white_dev || !sel_dev) return fail(BO_E_ARG, "null argument");
+    if (e->fast) return fail(BO_E_CONFIG, "bo_match_select: reference-semantics engines only (fast mode has L rows per game)");
+    const int G = e->d.c.G;
+    hipLaunchKernelGGL(bo_k_match_select, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->d, net_of_white_dev, sel_dev);
     RT((int)hipGetLastError());
     return BO_OK;
 #endif

@@ -45,6 +45,15 @@ struct bo_heads_args {
 };
 static inline int bo_heads_policy_boards(int batch) { return batch > 64 ? 128 : batch > 32 ? 64 : 32; }
 
+// The two-net launches (bo_nn_heads_pair): row b is computed with bo_heads_args' weights when sel[b] == 0, with these when sel[b] != 0.
+// A tile whose rows all use one net runs once with that net; a MIXED tile runs once per net present and stores only that net's rows (a
+// row's dot products are the same instructions in the same order either way: bit-identical to the single-net launch).  A single-net
+// launch passes an empty one (PAIR = false: never read).
+struct bo_heads_pair {
+    const int32_t *sel = nullptr;                                   // [B]
+    const float *wp = nullptr, *bp = nullptr, *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;  // the second net's
+};
+
 // four consecutive activations as float32 from a float32 or float16 array (element index e, a multiple of 4)
 template <bool HALF>
 __device__ __forceinline__ bo_f32x4 bo_heads_load4(const void *base, size_t e) {
@@ -57,9 +66,9 @@ __device__ __forceinline__ bo_f32x4 bo_heads_load4(const void *base, size_t e) {
     }
 }
 
-template <bool HALF>
+template <bool HALF, bool PAIR = false>
 __global__ void __launch_bounds__(256)
-bo_k_heads_tiles(bo_heads_args a) {
+bo_k_heads_tiles(bo_heads_args a, bo_heads_pair pr) {
     __shared__ __attribute__((aligned(16))) float tileA[64 * BO_HEADS_PITCH], tileW[64 * BO_HEADS_PITCH];  // value tiles [64][128 + 4]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), kq = lane >> 4, i = lane & 15;
     // A policy workgroup's four waves cover `pb` boards x (128 / pb) output tiles of 32: pb = 128 (one output tile, the boards of four
@@ -71,46 +80,59 @@ bo_k_heads_tiles(bo_heads_args a) {
         // ---- logits tile: boards pb*rb + 32*(wave % nbw) + [0,32) (N), outputs 32*(otw*ct + wave / nbw) + [0,32) (M) ----
         const int rb = wg / NPT, ct = wg - rb * NPT, r0 = pb * rb + 32 * (wave % nbw), c0 = 32 * (otw * ct + wave / nbw);
         if (c0 >= BO_HEADS_NA) return;  // (146 output tiles do not divide by four)
-        const bo_f32x4 *w4 = reinterpret_cast<const bo_f32x4 *>(a.wp);
-        constexpr int PG = BO_HEADS_KP / 16;
-        bo_f32x4 fp[PG][2], fw[PG][2];
-#pragma unroll
-        for (int t = 0; t < PG; t++) {
-            const int kk = 16 * t + 4 * kq;
-#pragma unroll
-            for (int c = 0; c < 2; c++) fw[t][c] = w4[((size_t)(c0 + 16 * c + i) * BO_HEADS_KP + kk) >> 2];
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++) {
-                const int row = r0 + 16 * rt + i;
-                fp[t][rt] = row < B ? bo_heads_load4<HALF>(a.p, (size_t)row * BO_HEADS_KP + kk) : bo_f32x4{0, 0, 0, 0};
-            }
+        // PAIR: one pass per net among this wave's 32 boards; a wave with both stores only the pass's net's rows (only_net >= 0)
+        bool has[2] = {true, false};
+        if constexpr (PAIR) {
+            const bool in = lane < 32 && r0 + lane < B;
+            const int s1 = in ? (pr.sel[r0 + lane] != 0) : 0;
+            has[0] = __ballot(in && !s1) != 0ull;
+            has[1] = __ballot(in && s1) != 0ull;
         }
-        bo_f32x4 bias[2];
+        for (int pass = 0; pass < (PAIR ? 2 : 1); pass++) {
+            if (PAIR && !has[pass]) continue;
+            const float *wp = PAIR && pass ? pr.wp : a.wp, *bp = PAIR && pass ? pr.bp : a.bp;
+            const int only_net = PAIR && has[0] && has[1] ? pass : -1;
+            const bo_f32x4 *w4 = reinterpret_cast<const bo_f32x4 *>(wp);
+            constexpr int PG = BO_HEADS_KP / 16;
+            bo_f32x4 fp[PG][2], fw[PG][2];
 #pragma unroll
-        for (int c = 0; c < 2; c++) bias[c] = *reinterpret_cast<const bo_f32x4 *>(a.bp + c0 + 16 * c + 4 * kq);
-        __builtin_amdgcn_sched_barrier(0);
-        bo_f32x4 acc[2][2];
+            for (int t = 0; t < PG; t++) {
+                const int kk = 16 * t + 4 * kq;
 #pragma unroll
-        for (int c = 0; c < 2; c++)
+                for (int c = 0; c < 2; c++) fw[t][c] = w4[((size_t)(c0 + 16 * c + i) * BO_HEADS_KP + kk) >> 2];
 #pragma unroll
-            for (int rt = 0; rt < 2; rt++) acc[c][rt] = bo_f32x4{0, 0, 0, 0};
+                for (int rt = 0; rt < 2; rt++) {
+                    const int row = r0 + 16 * rt + i;
+                    fp[t][rt] = row < B ? bo_heads_load4<HALF>(a.p, (size_t)row * BO_HEADS_KP + kk) : bo_f32x4{0, 0, 0, 0};
+                }
+            }
+            bo_f32x4 bias[2];
 #pragma unroll
-        for (int t = 0; t < PG; t++)
+            for (int c = 0; c < 2; c++) bias[c] = *reinterpret_cast<const bo_f32x4 *>(bp + c0 + 16 * c + 4 * kq);
+            __builtin_amdgcn_sched_barrier(0);
+            bo_f32x4 acc[2][2];
 #pragma unroll
-            for (int e = 0; e < 4; e++)
+            for (int c = 0; c < 2; c++)
 #pragma unroll
-                for (int c = 0; c < 2; c++)
+                for (int rt = 0; rt < 2; rt++) acc[c][rt] = bo_f32x4{0, 0, 0, 0};
 #pragma unroll
-                    for (int rt = 0; rt < 2; rt++) acc[c][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(fw[t][c][e], fp[t][rt][e], acc[c][rt], 0, 0, 0);
+            for (int t = 0; t < PG; t++)
 #pragma unroll
-        for (int c = 0; c < 2; c++) {
-            const int col = c0 + 16 * c + 4 * kq;  // this lane: outputs col .. col+3 of board r0 + 16*rt + i
+                for (int e = 0; e < 4; e++)
 #pragma unroll
-            for (int rt = 0; rt < 2; rt++) {
-                const int row = r0 + 16 * rt + i;
-                if (row < B)
-                    *reinterpret_cast<bo_f32x4 *>(a.policy_out + (size_t)row * BO_HEADS_NA + col) =
-                        bo_f32x4{acc[c][rt][0] + bias[c][0], acc[c][rt][1] + bias[c][1], acc[c][rt][2] + bias[c][2], acc[c][rt][3] + bias[c][3]};
+                    for (int c = 0; c < 2; c++)
+#pragma unroll
+                        for (int rt = 0; rt < 2; rt++) acc[c][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(fw[t][c][e], fp[t][rt][e], acc[c][rt], 0, 0, 0);
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                const int col = c0 + 16 * c + 4 * kq;  // this lane: outputs col .. col+3 of board r0 + 16*rt + i
+#pragma unroll
+                for (int rt = 0; rt < 2; rt++) {
+                    const int row = r0 + 16 * rt + i;
+                    if (row < B && (only_net < 0 || (pr.sel[row] != 0) == only_net))
+                        *reinterpret_cast<bo_f32x4 *>(a.policy_out + (size_t)row * BO_HEADS_NA + col) =
+                            bo_f32x4{acc[c][rt][0] + bias[c][0], acc[c][rt][1] + bias[c][1], acc[c][rt][2] + bias[c][2], acc[c][rt][3] + bias[c][3]};
+                }
             }
         }
     } else {
@@ -119,59 +141,78 @@ bo_k_heads_tiles(bo_heads_args a) {
         //      fragment-order fetch of rows 8 KB apart serialises on a few L2 channels), fragments come from LDS. ----
         const int vt = wg - n_policy, ks = vt & (BO_HEADS_KS - 1), ht = (vt >> 4) & 3, rbv = vt >> 6;
         const int r0 = 64 * rbv, h0 = 64 * ht, k0 = (BO_HEADS_KV / BO_HEADS_KS) * ks;
-        const bo_f32x4 *w4 = reinterpret_cast<const bo_f32x4 *>(a.w1);
-        bo_f32x4 ga[8], gw[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int idx = tid + 256 * q, row = idx >> 5, c4 = idx & 31;  // 32 lanes per 512-byte row segment
-            ga[q] = r0 + row < B ? bo_heads_load4<HALF>(a.v, ((size_t)(r0 + row)) * BO_HEADS_KV + k0 + 4 * c4) : bo_f32x4{0, 0, 0, 0};
-            gw[q] = w4[(((size_t)(h0 + row)) * BO_HEADS_KV + k0) / 4 + c4];
+        // PAIR: the same per net among the tile's 64 boards (every wave finds the same: the barriers stay uniform)
+        bool has[2] = {true, false};
+        if constexpr (PAIR) {
+            const bool in = r0 + lane < B;
+            const int s1 = in ? (pr.sel[r0 + lane] != 0) : 0;
+            has[0] = __ballot(in && !s1) != 0ull;
+            has[1] = __ballot(in && s1) != 0ull;
         }
+        for (int pass = 0; pass < (PAIR ? 2 : 1); pass++) {
+            if (PAIR && !has[pass]) continue;
+            if (PAIR && pass && has[0]) __syncthreads();  // (every wave is done with the first pass's LDS tiles before they are restaged)
+            const float *w1 = PAIR && pass ? pr.w1 : a.w1;
+            const int only_net = PAIR && has[0] && has[1] ? pass : -1;
+            const bo_f32x4 *w4 = reinterpret_cast<const bo_f32x4 *>(w1);
+            bo_f32x4 ga[8], gw[8];
 #pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int idx = tid + 256 * q, row = idx >> 5, c4 = idx & 31;
-            *reinterpret_cast<bo_f32x4 *>(&tileA[row * BO_HEADS_PITCH + 4 * c4]) = ga[q];
-            *reinterpret_cast<bo_f32x4 *>(&tileW[row * BO_HEADS_PITCH + 4 * c4]) = gw[q];
-        }
-        __syncthreads();
-        // wave: hidden units 32*(wave & 1) + [0,32) (M), boards 32*(wave >> 1) + [0,32) (N)
-        const int hb = 32 * (wave & 1), bb = 32 * (wave >> 1);
-        bo_f32x4 acc[2][2];
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++) acc[c][rt] = bo_f32x4{0, 0, 0, 0};
-#pragma unroll
-        for (int t = 0; t < BO_HEADS_KV / BO_HEADS_KS / 16; t++) {
-            bo_f32x4 fw[2], fv[2];
-#pragma unroll
-            for (int c = 0; c < 2; c++) fw[c] = *reinterpret_cast<const bo_f32x4 *>(&tileW[(hb + 16 * c + i) * BO_HEADS_PITCH + 16 * t + 4 * kq]);
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++) fv[rt] = *reinterpret_cast<const bo_f32x4 *>(&tileA[(bb + 16 * rt + i) * BO_HEADS_PITCH + 16 * t + 4 * kq]);
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-#pragma unroll
-                for (int c = 0; c < 2; c++)
-#pragma unroll
-                    for (int rt = 0; rt < 2; rt++) acc[c][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(fw[c][e], fv[rt][e], acc[c][rt], 0, 0, 0);
-        }
-        // partial sums [ks][board][256 hidden]: this lane holds hidden h0 + hb + 16c + 4kq + [0,4) of board r0 + bb + 16rt + i
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++) {
-                const int row = r0 + bb + 16 * rt + i;
-                if (row < B) *reinterpret_cast<bo_f32x4 *>(a.vpart + ((size_t)ks * B + row) * BO_HEADS_NH + h0 + hb + 16 * c + 4 * kq) = acc[c][rt];
+            for (int q = 0; q < 8; q++) {
+                const int idx = tid + 256 * q, row = idx >> 5, c4 = idx & 31;  // 32 lanes per 512-byte row segment
+                ga[q] = r0 + row < B ? bo_heads_load4<HALF>(a.v, ((size_t)(r0 + row)) * BO_HEADS_KV + k0 + 4 * c4) : bo_f32x4{0, 0, 0, 0};
+                gw[q] = w4[(((size_t)(h0 + row)) * BO_HEADS_KV + k0) / 4 + c4];
             }
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const int idx = tid + 256 * q, row = idx >> 5, c4 = idx & 31;
+                *reinterpret_cast<bo_f32x4 *>(&tileA[row * BO_HEADS_PITCH + 4 * c4]) = ga[q];
+                *reinterpret_cast<bo_f32x4 *>(&tileW[row * BO_HEADS_PITCH + 4 * c4]) = gw[q];
+            }
+            __syncthreads();
+            // wave: hidden units 32*(wave & 1) + [0,32) (M), boards 32*(wave >> 1) + [0,32) (N)
+            const int hb = 32 * (wave & 1), bb = 32 * (wave >> 1);
+            bo_f32x4 acc[2][2];
+#pragma unroll
+            for (int c = 0; c < 2; c++)
+#pragma unroll
+                for (int rt = 0; rt < 2; rt++) acc[c][rt] = bo_f32x4{0, 0, 0, 0};
+#pragma unroll
+            for (int t = 0; t < BO_HEADS_KV / BO_HEADS_KS / 16; t++) {
+                bo_f32x4 fw[2], fv[2];
+#pragma unroll
+                for (int c = 0; c < 2; c++) fw[c] = *reinterpret_cast<const bo_f32x4 *>(&tileW[(hb + 16 * c + i) * BO_HEADS_PITCH + 16 * t + 4 * kq]);
+#pragma unroll
+                for (int rt = 0; rt < 2; rt++) fv[rt] = *reinterpret_cast<const bo_f32x4 *>(&tileA[(bb + 16 * rt + i) * BO_HEADS_PITCH + 16 * t + 4 * kq]);
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+#pragma unroll
+                    for (int c = 0; c < 2; c++)
+#pragma unroll
+                        for (int rt = 0; rt < 2; rt++) acc[c][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(fw[c][e], fv[rt][e], acc[c][rt], 0, 0, 0);
+            }
+            // partial sums [ks][board][256 hidden]: this lane holds hidden h0 + hb + 16c + 4kq + [0,4) of board r0 + bb + 16rt + i
+#pragma unroll
+            for (int c = 0; c < 2; c++)
+#pragma unroll
+                for (int rt = 0; rt < 2; rt++) {
+                    const int row = r0 + bb + 16 * rt + i;
+                    if (row < B && (only_net < 0 || (pr.sel[row] != 0) == only_net))
+                        *reinterpret_cast<bo_f32x4 *>(a.vpart + ((size_t)ks * B + row) * BO_HEADS_NH + h0 + hb + 16 * c + 4 * kq) = acc[c][rt];
+                }
+        }
     }
 }
 
-// one board per workgroup (grid = B): the softmax of its logits row and its value
-extern "C" __global__ void __launch_bounds__(256)
-bo_k_heads_rows(bo_heads_args a) {
+// one board per workgroup (grid = B): the softmax of its logits row and its value (PAIR: value_fc1's bias and value_fc2 of the row's net)
+template <bool PAIR>
+__device__ __forceinline__ void bo_heads_rows_body(const bo_heads_args &a, const bo_heads_pair &q) {
     __shared__ float sred[8];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int B = a.B, row = (int)blockIdx.x;
+    const float *b1 = a.b1, *w2 = a.w2, *b2 = a.b2;
+    if constexpr (PAIR) {
+        if (__builtin_amdgcn_readfirstlane(q.sel[row]) != 0) { b1 = q.b1; w2 = q.w2; b2 = q.b2; }
+    }
     // value: the K chunks' partial sums in a fixed order, bias, ReLU, value_fc2, tanh (requested first: it overlaps the row)
     float part[BO_HEADS_KS];
 #pragma unroll
@@ -191,8 +232,8 @@ bo_k_heads_rows(bo_heads_args a) {
     float hsum = 0.0f;
 #pragma unroll
     for (int ks = 0; ks < BO_HEADS_KS; ks++) hsum += part[ks];
-    hsum += a.b1[tid];
-    hsum = (hsum > 0.0f ? hsum : 0.0f) * a.w2[tid];
+    hsum += b1[tid];
+    hsum = (hsum > 0.0f ? hsum : 0.0f) * w2[tid];
     if (a.softmax) {
 #pragma unroll
         for (int u = 0; u < IT; u++) mx = fmaxf(mx, fmaxf(fmaxf(x[u][0], x[u][1]), fmaxf(x[u][2], x[u][3])));
@@ -202,7 +243,7 @@ bo_k_heads_rows(bo_heads_args a) {
     if (lane == 0) { sred[wave] = mx; sred[4 + wave] = hsum; }
     __syncthreads();
     mx = fmaxf(fmaxf(sred[0], sred[1]), fmaxf(sred[2], sred[3]));
-    if (tid == 0) a.value_out[row] = tanhf(((sred[4] + sred[5]) + (sred[6] + sred[7])) + a.b2[0]);
+    if (tid == 0) a.value_out[row] = tanhf(((sred[4] + sred[5]) + (sred[6] + sred[7])) + b2[0]);
     if (a.softmax) {
         float sum = 0.0f;
 #pragma unroll
@@ -225,6 +266,12 @@ bo_k_heads_rows(bo_heads_args a) {
         }
     }
 }
+
+extern "C" __global__ void __launch_bounds__(256)
+bo_k_heads_rows(bo_heads_args a) { bo_heads_rows_body<false>(a, bo_heads_pair{}); }
+
+extern "C" __global__ void __launch_bounds__(256)
+bo_k_heads_rows_pair(bo_heads_args a, bo_heads_pair q) { bo_heads_rows_body<true>(a, q); }
 
 // ---- fp16 head planes, any number of rows (fast mode: 4 096 .. 131 072 rows per evaluation) -------------------------------------------
 // Behind the fp16 tower (bo_tower_h.h) the head planes are fp16 and so are the Linear weights the reference's autocast evaluation

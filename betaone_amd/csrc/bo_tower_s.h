@@ -37,6 +37,17 @@ struct bo_tower_head_s {
 };
 #define BO_TOWER_TIMING_CAP 4096
 
+// The two-net launch (bo_nn_tower_forward_pair: a match between two nets of the same shape): board b runs on the kernel's own weights /
+// params when sel[b] == 0 and on these when sel[b] != 0.  The layer table and every offset are the first net's (the pair was checked to
+// have identical descriptors), so only the two base addresses change per board.  A single-net launch passes an empty one (PAIR = false:
+// never read).
+struct bo_tower_pair {
+    const int32_t *sel = nullptr;     // [B]: which net board b runs on
+    const bo_h8 *wts1 = nullptr;      // the second net's weight fragments and params
+    const float *params1 = nullptr;
+    int *overflow1 = nullptr;         // its saturation word: a saturation is reported into both nets' words
+};
+
 // hi / lo halves of 4 float32 values (saturating: |v| beyond the fp16 range would turn into inf - inf)
 __device__ inline void bo_split4(const float (&v)[4], bo_h4 &hi, bo_h4 &lo) {
 #pragma unroll
@@ -60,10 +71,11 @@ __device__ inline void bo_split4_pos(const float (&v)[4], bo_h4 &hi, bo_h4 &lo, 
 
 // BD = how many K-steps ahead of its MFMAs a B operand is read from LDS (1: two register sets; 2, 3: four);
 // AR = weight-fragment sets = how many K-steps ahead a weight fragment is requested (4 or 8, or 12 with the loop unrolled 24-fold)
-template <int C, int MT, int BD = 1, int AR = 8>
+// PAIR: the two-net launch (bo_tower_pair); false compiles to the single-net kernel.
+template <int C, int MT, int BD = 1, int AR = 8, bool PAIR = false>
 __global__ void __launch_bounds__(256)
 bo_k_tower_s(const float *__restrict__ x, const bo_h8 *__restrict__ wts, const float *__restrict__ params,
-             const bo_tower_layer *__restrict__ layers, int n_layers, float *__restrict__ y, int B, bo_tower_head_s head) {
+             const bo_tower_layer *__restrict__ layers, int n_layers, float *__restrict__ y, int B, bo_tower_head_s head, bo_tower_pair pair) {
     constexpr int NW = 4, NT = 256, PH = C, CELLS = 100, IMGH = CELLS * PH, CIN0 = 120, HPW = 16 / NW;
     static_assert(C == 32 * MT * NW, "four waves of MT 32-channel tiles");
     __shared__ __attribute__((aligned(16))) _Float16 X[2 * IMGH];  // [hi | lo][cell][PH]
@@ -92,7 +104,10 @@ bo_k_tower_s(const float *__restrict__ x, const bo_h8 *__restrict__ wts, const f
     const int sw0 = bo_sw(cell0);  // (position n + 32 sits 4 rows further down: the same swizzle)
     // B operand address (in halves) of K-step j of a group of 8: tap cell offset `tc`, first channel group cg0 (a multiple of 8)
     auto b_base = [&](int tc, int cg0) { return (cell0 + tc) * PH + 16 * cg0 + (((kg ^ bo_sw(cell0 + tc)) & 15) << 3); };
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bo_h8 *>(wts), 0, 0x7fffffff, 0x00020000);
+    __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bo_h8 *>(wts), 0, 0x7fffffff, 0x00020000);
+    const bo_h8 *const wts0 = wts;
+    const float *const params0 = params;
+    int net = 0;  // PAIR: whose weights the ring holds
     const int wvoff = ((wave * MT * 2) * 64 + lane) * 16;
     auto load_a = [&](int j, int w_off8, int step) {
         typedef int bo_i32x4_t __attribute__((ext_vector_type(4)));
@@ -117,6 +132,17 @@ bo_k_tower_s(const float *__restrict__ x, const bo_h8 *__restrict__ wts, const f
 #pragma unroll
     for (int j = 0; j < AR; j++) load_a(j, layers[0].w_off4, j);
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
+        if constexpr (PAIR) {  // this board's net; the ring prefetched the previous board's net's first layer: reload it on a change
+            const int nb = __builtin_amdgcn_readfirstlane(pair.sel[b]) != 0;
+            if (nb != net) {
+                net = nb;
+                wts = nb ? pair.wts1 : wts0;
+                params = nb ? pair.params1 : params0;
+                wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bo_h8 *>(wts), 0, 0x7fffffff, 0x00020000);
+#pragma unroll
+                for (int j = 0; j < AR; j++) load_a(j, layers[0].w_off4, j);
+            }
+        }
         // ---- stage the 120 input planes (float32 NCHW) as fp16 pairs, channels-last; channels >= 120 stay zero ----
         __syncthreads();
         for (int i = tid; i < 128 * 16; i += NT) {
@@ -264,7 +290,10 @@ bo_k_tower_s(const float *__restrict__ x, const bo_h8 *__restrict__ wts, const f
                     }
                 // an activation beyond the fp16 range cannot be carried as a (hi, lo) pair: the tower's result is wrong from here on --
                 // say so (bo_nn_tower_status) instead of returning it silently; such a net needs the fp32-pipe tower
-                if (__ballot(sat) != 0ull && lane == 0 && head.overflow) atomicOr(head.overflow, 1);
+                if (__ballot(sat) != 0ull && lane == 0) {
+                    if (head.overflow) atomicOr(head.overflow, 1);
+                    if constexpr (PAIR) { if (pair.overflow1) atomicOr(pair.overflow1, 1); }
+                }
             };
             using std::integral_constant;
             if (L.last && y) {

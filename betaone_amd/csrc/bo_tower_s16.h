@@ -31,10 +31,11 @@ __device__ __host__ inline int bo_sw16(int cell) { return 2 * ((cell % 10) & 7);
 // offset (in halves) of 16-byte chunk `chunk` (0..15) of padded cell `cell` in a [cell][128] image
 __device__ inline int bo_sw16_addr(int cell, int chunk) { return cell * 128 + (((chunk ^ bo_sw16(cell)) & 15) << 3); }
 
-template <int AR = 6>
+// PAIR: the two-net launch (bo_tower_pair, bo_tower_s.h); false compiles to the single-net kernel.
+template <int AR = 6, bool PAIR = false>
 __global__ void __launch_bounds__(256)
 bo_k_tower_s16(const float *__restrict__ x, const bo_h8 *__restrict__ wts, const float *__restrict__ params,
-               const bo_tower_layer *__restrict__ layers, int n_layers, float *__restrict__ y, int B, bo_tower_head_s head) {
+               const bo_tower_layer *__restrict__ layers, int n_layers, float *__restrict__ y, int B, bo_tower_head_s head, bo_tower_pair pair) {
     constexpr int C = 128, NW = 4, NT = 256, PH = C, CELLS = 100, IMGH = CELLS * PH, CIN0 = 120, HPW = 16 / NW;
     constexpr int UNR = 12;  // K-steps per unrolled body: the three taps of one kernel row x four channel groups
     static_assert(UNR % AR == 0, "the weight ring is indexed statically");
@@ -62,7 +63,10 @@ bo_k_tower_s16(const float *__restrict__ x, const bo_h8 *__restrict__ wts, const
     int xk[3];
 #pragma unroll
     for (int d = 0; d < 3; d++) xk[d] = kb ^ (2 * (((n16 & 7) + 1 + d - 1) & 7));
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bo_h8 *>(wts), 0, 0x7fffffff, 0x00020000);
+    __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bo_h8 *>(wts), 0, 0x7fffffff, 0x00020000);
+    const bo_h8 *const wts0 = wts;
+    const float *const params0 = params;
+    int net = 0;  // PAIR: whose weights the ring holds
     const int wvoff = ((wave * 2 * 2) * 64 + lane) * 16;
     auto load_a = [&](int j, int w_off8, int step) {
         typedef int bo_i32x4_t __attribute__((ext_vector_type(4)));
@@ -88,6 +92,17 @@ bo_k_tower_s16(const float *__restrict__ x, const bo_h8 *__restrict__ wts, const
 #pragma unroll
     for (int j = 0; j < AR; j++) load_a(j, layers[0].w_off4, j);
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
+        if constexpr (PAIR) {  // this board's net; the ring prefetched the previous board's net's first layer: reload it on a change
+            const int nb = __builtin_amdgcn_readfirstlane(pair.sel[b]) != 0;
+            if (nb != net) {
+                net = nb;
+                wts = nb ? pair.wts1 : wts0;
+                params = nb ? pair.params1 : params0;
+                wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bo_h8 *>(wts), 0, 0x7fffffff, 0x00020000);
+#pragma unroll
+                for (int j = 0; j < AR; j++) load_a(j, layers[0].w_off4, j);
+            }
+        }
         // ---- stage the 120 input planes (float32 NCHW) as fp16 pairs, channels-last; channels >= 120 stay zero ----
         __syncthreads();
         for (int i = tid; i < 128 * 16; i += NT) {
@@ -219,7 +234,10 @@ bo_k_tower_s16(const float *__restrict__ x, const bo_h8 *__restrict__ wts, const
                             for (int r = 0; r < 4; r++) g2[r * 64] = o[r];
                         }
                     }
-                if (__ballot(sat) != 0ull && lane == 0 && head.overflow) atomicOr(head.overflow, 1);
+                if (__ballot(sat) != 0ull && lane == 0) {
+                    if (head.overflow) atomicOr(head.overflow, 1);
+                    if constexpr (PAIR) { if (pair.overflow1) atomicOr(pair.overflow1, 1); }
+                }
             };
             using std::integral_constant;
             if (L.last && y) {

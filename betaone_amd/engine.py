@@ -62,6 +62,10 @@ class BoNode(C.Structure):
                 ("q_value", C.c_float), ("prior", C.c_float), ("move", C.c_int32), ("terminal", C.c_int32)]
 
 
+class BoHeadWeights(C.Structure):  # bo_head_weights: device addresses of one net's head Linear weights (bo_nn_heads_pair)
+    _fields_ = [("wp", C.c_void_p), ("bp", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p)]
+
+
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
 _F64P = C.POINTER(C.c_double)
@@ -135,6 +139,12 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_stream_destroy": (C.c_int, [C.c_void_p]),
     "bo_nn_value_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "bo_nn_tower_destroy": (None, [C.c_void_p]),
+    "bo_nn_tower_pair_check": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bo_nn_tower_forward_pair": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p]),
+    "bo_nn_heads_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BoHeadWeights), C.POINTER(BoHeadWeights)] + [C.c_void_p] * 4
+                         + [C.c_int, C.c_int, C.c_void_p]),
+    "bo_nn_merge_rows": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p]),
+    "bo_match_select": (C.c_int, [C.c_void_p] * 4),
 }
 # include/betaone_lab.h: introspection for the parity tests and in-kernel timing for bench.py / scripts/ (same library, not the boundary)
 _LAB_SYMBOLS = {
@@ -341,6 +351,10 @@ class Engine:
         return nl, tm, ply
 
     # -- search ----------------------------------------------------------------------------------
+    def match_select(self, net_of_white_ptr: int, sel_ptr: int, stream: int = 0):
+        """sel[g] = net_of_white[g] ^ (slot g's root has black to move), on the device (bo_match_select)."""
+        self._check(self.lib.bo_match_select(self.h, net_of_white_ptr, sel_ptr, stream))
+
     def search_begin(self, go, noise: Optional[np.ndarray], nn_in_ptr: int, stream: int = 0):
         g = _i32(go)
         nz = None

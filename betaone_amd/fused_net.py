@@ -787,3 +787,123 @@ class FusedPolicyValueNet(nn.Module):
         v = h[:, self.n_policy_ch:].flatten(1)
         logits = self.policy_fc(p)
         return (torch.softmax(logits.float(), dim=1) if probs else logits), torch.tanh(self.value_fc2(F.relu(self.value_fc1(v))))
+
+
+class PairedNet(nn.Module):
+    """Two evaluate stages as one (head-to-head matches, betaone_amd/match.py): forward(x, sel) evaluates row b with net sel[b]
+    (int32 [B] on the device, 0 = the first net) and returns what that net alone returns for the row -- bit for bit.
+
+      route "pair:tower_split": both nets on the split-precision tower with the reference's head shapes and identical layer tables: ONE
+                 launch of the tower (bo_nn_tower_forward_pair: each workgroup streams the weights of its own board's net) and one
+                 two-net bo_nn_heads (bo_nn_heads_pair) instead of two launches of each (what a match ply costs against a
+                 self-play ply, and where the difference goes: profiles/match_two_net.md, scripts/match_cost.py);
+      route "pair:merge": every other pair (different shapes, the other hand-written routes, library nets, test stand-ins): BOTH nets run
+                 over the whole batch and the rows are merged (bo_nn_merge_rows) -- twice the evaluate stage's time.
+
+    model0 / model1: PolicyValueNets (an inference copy is made: nn_tune.pair_route decides), or evaluate stages already built (any
+    module with forward(x) -> (logits, value); FusedPolicyValueNet(conv='tower_split') pairs share the launch).  route='merge' forces
+    the merge path.  There is no forward_tail: Rollout keeps the stage's own rows kernel for a pair (the step tail stays single-net)."""
+
+    is_pair = True
+
+    def __init__(self, model0, model1, batch: int, device="cuda:0", route: str = None, f32_pipe=None):
+        super().__init__()
+        from . import nn_tune
+
+        self.lib = E.load_hip_library()
+        device = torch.device(device)
+
+        def stage(m):
+            if not hasattr(m, "for_inference"):
+                return m
+            r = nn_tune.pair_route(m.conv_input.out_channels, batch, torch.float32, f32_pipe)
+            if r == "tower_split" and route != "merge":
+                return FusedPolicyValueNet(m.to(device), conv="tower_split").to(device)
+            return nn_tune.best_inference_copy(m, batch, device, f32_pipe=f32_pipe)
+
+        self.nets = [stage(model0), stage(model1)]
+        for i, n in enumerate(self.nets):  # (registered for .to() / state; forward goes through self.nets)
+            if isinstance(n, nn.Module):
+                self.add_module(f"net{i}", n)
+        self.route = "pair:merge"
+        if route != "merge" and self._can_share_launch():
+            self.route = "pair:tower_split"
+            self._hw = [self._head_weights(n) for n in self.nets]
+
+    def _can_share_launch(self) -> bool:
+        a, b = self.nets
+        if not all(isinstance(n, FusedPolicyValueNet) and n.conv == "tower_split" and n.__dict__.get("_tower") for n in (a, b)):
+            return False
+        heads_ok = all(n.fused_heads and n.policy_fc.weight.shape == (4672, 128) and n.value_fc1.weight.shape == (256, 2048)
+                       and n._head_ch == 34 and n._head_split == 2 for n in (a, b))
+        if not heads_ok or a.split_tile != b.split_tile or a._tower_dev != b._tower_dev:
+            return False
+        return self.lib.bo_nn_tower_pair_check(a._tower, b._tower) == 0
+
+    @staticmethod
+    def _head_weights(n):
+        return E.BoHeadWeights(n.policy_fc.weight.data_ptr(), n.policy_fc.bias.data_ptr(), n.value_fc1.weight.data_ptr(),
+                               n.value_fc1.bias.data_ptr(), n.value_fc2.weight.data_ptr(), n.value_fc2.bias.data_ptr())
+
+    OVERFLOW_MESSAGE = FusedPolicyValueNet.OVERFLOW_MESSAGE
+
+    def overflow_words(self):
+        """The first net's fault words: on the shared launch a saturation is reported into both nets' words, so watching one is watching
+        both.  On the merge path the two nets' words are separate and the engine watches one consecutive run of words: only the first
+        net's is checked with every ply's result block; the second net's is checked by check_overflow, which the match driver calls
+        when the match ends (a saturating second net then fails the match at its end, not on the ply it happened)."""
+        words = getattr(self.nets[0], "overflow_words", None)
+        return words() if words is not None else (0, 1)
+
+    def check_overflow(self):
+        for n in self.nets:
+            chk = getattr(n, "check_overflow", None)
+            if chk is not None:
+                chk()
+
+    def forward_probs(self, x, sel):
+        return self.forward(x, sel, probs=True)
+
+    @torch.no_grad()
+    def forward(self, x, sel, probs: bool = False):
+        B = x.shape[0]
+        if sel.dtype != torch.int32 or sel.numel() < B or sel.device != x.device:
+            raise E.EngineError("PairedNet: sel must be an int32 tensor of >= batch entries on the input's device")
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        if self.route == "pair:tower_split":
+            a, b = self.nets
+            if x.device != a._tower_dev or x.dtype != torch.float32 or x.shape[1:] != (120, 8, 8):
+                raise E.EngineError("PairedNet: x must be float32 [B, 120, 8, 8] on the nets' device")
+            x = x.contiguous()
+            pa = torch.empty((B, 2 * 64), dtype=torch.float32, device=x.device)
+            pv = torch.empty((B, 32 * 64), dtype=torch.float32, device=x.device)
+            rc = self.lib.bo_nn_tower_forward_pair(a._tower, b._tower, sel.data_ptr(), x.data_ptr(), pa.data_ptr(), pv.data_ptr(), B, stream)
+            if rc:
+                raise E.EngineError(self.lib.bo_last_error().decode())
+            scr = torch.empty(4096 * B, dtype=torch.float32, device=x.device)  # (per call, as FusedPolicyValueNet._heads: graph-pool safe)
+            out = torch.empty((B, 4672), dtype=torch.float32, device=x.device)
+            value = torch.empty((B, 1), dtype=torch.float32, device=x.device)
+            rc = self.lib.bo_nn_heads_pair(pa.data_ptr(), pv.data_ptr(), C.byref(self._hw[0]), C.byref(self._hw[1]), sel.data_ptr(),
+                                           out.data_ptr(), value.data_ptr(), scr.data_ptr(), B, 1 if probs else 0, stream)
+            if rc:
+                raise E.EngineError(self.lib.bo_last_error().decode())
+            return out, value
+        # merge: both nets over the whole batch (twice the evaluate time), then each row from its own net
+        outs = []
+        for n in self.nets:
+            fp = getattr(n, "forward_probs", None) if probs else None
+            l, v = fp(x) if fp is not None else n(x)
+            l = l.float()
+            if probs and fp is None:
+                l = torch.softmax(l, dim=1)
+            outs.append((l.to(x.device).contiguous(), v.float().reshape(B, 1).to(x.device).contiguous()))
+        (l0, v0), (l1, v1) = outs
+        if l0.shape != l1.shape:
+            raise E.EngineError(f"PairedNet: the two nets' policy widths differ ({tuple(l0.shape)} vs {tuple(l1.shape)})")
+        out = torch.empty_like(l0)
+        value = torch.empty_like(v0)
+        rc = self.lib.bo_nn_merge_rows(sel.data_ptr(), l0.data_ptr(), v0.data_ptr(), l1.data_ptr(), v1.data_ptr(), out.data_ptr(),
+                                       value.data_ptr(), B, l0.shape[1], stream)
+        if rc:
+            raise E.EngineError(self.lib.bo_last_error().decode())
+        return out, value

@@ -51,6 +51,18 @@ def kernel_route(filters: int, batch: int, dtype: torch.dtype, f32_pipe: bool = 
     return None
 
 
+def pair_route(filters: int, batch: int, dtype: torch.dtype, f32_pipe: bool = None):
+    """kernel_route for one net of a two-net evaluate stage (fused_net.PairedNet): 'tower_split' wherever kernel_route gives it, and also
+    at the small batches where kernel_route takes a one-board route ('tower_b1', 'mfma_small') -- the split tower evaluates both nets'
+    rows in ONE launch, where those routes would need two.  Otherwise what kernel_route says (the pair then merges two forwards)."""
+    if f32_pipe is None:
+        f32_pipe = f32_pipe_default()
+    r = kernel_route(filters, batch, dtype, f32_pipe)
+    if r in ("tower_b1", "mfma_small") and dtype == torch.float32 and filters in (128, 256) and not f32_pipe:
+        return "tower_split"
+    return r
+
+
 def best_inference_copy(model, batch: int, device, dtype: torch.dtype = torch.float32, verbose: bool = False, f32_pipe=None):
     """BN-folded inference copy of a PolicyValueNet for `batch` rows: the hand-written kernels chosen by kernel_route(); where
     there are none (other filter counts, bfloat16) the PyTorch-ROCm copy in NCHW up to 512 rows and channels-last beyond, with

@@ -150,6 +150,11 @@ class Rollout:
         self.temperature = temperature
         self.model = model
         self.autocast = autocast
+        # a two-net evaluate stage (fused_net.PairedNet, betaone_amd/match.py): row g is evaluated by the net of the side to move at slot g's
+        # root -- sel[g] = net_of_white[g] ^ (black to move), set on the device (bo_match_select) right before every forward
+        self.pair = bool(getattr(model, "is_pair", False))
+        if self.pair and (fast or autocast):
+            raise ValueError("Rollout: a two-net (match) evaluate stage supports the reference search semantics only (fast=False, autocast=False)")
         dev_index = self.device.index if self.device.index is not None else 0
         self.eng = E.Engine(self.G, num_simulations=self.S, mcts_batch_size=self.B, cpuct=cpuct, widen_coeff=widen_coeff,
                             dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon, max_plies=max_plies,
@@ -208,6 +213,8 @@ class Rollout:
         self._pi_val = np.zeros((G, 256, max(1, self._pk)), np.float32)
         self._out = dict(n=np.zeros(G, np.int32), idx=np.zeros((G, E.RES_CAP), np.int32), val=np.zeros((G, E.RES_CAP), np.float32),
                          best_idx=np.zeros(G, np.int32), action=np.zeros(G, np.int32))
+        self.net_of_white = torch.zeros(G, dtype=torch.int32, device=self.device) if self.pair else None  # [slot]: 0 / 1 (start_games)
+        self._sel = torch.zeros(G, dtype=torch.int32, device=self.device) if self.pair else None
         self._watch_net()
         self._set_tail()
 
@@ -255,6 +262,10 @@ class Rollout:
         if self.tower_timing is not None:  # (one host thread drives every cohort: the buffer named here is the one this forward's launch gets)
             getattr(self.model, "net", self.model).tower_timing_buf = self.tower_timing
         want_probs = self.policy_kind == E.POLICY_PROBS
+        if self.pair:  # (inside every captured graph too: the selector reads the roots the enqueued turn has moved, no host copy)
+            self.eng.match_select(self.net_of_white.data_ptr(), self._sel.data_ptr(), self._stream())
+            logits, value = (self.model.forward_probs if want_probs else self.model)(self.nn_in, self._sel)
+            return logits.float().contiguous(), value.float().contiguous()
         fused = getattr(self.model, "forward_probs", None) if (want_probs and not self.autocast) else None
         with torch.no_grad():
             if self.step_tail:  # (logits, value_fc1's partial sums [16, G, 256]): _step_after hands both to the step kernel
@@ -341,10 +352,17 @@ class Rollout:
     # ---- game slots ---------------------------------------------------------------------------------
     @_on_main
     def start_games(self, slots: Sequence[int], game_ids: Sequence[int], rngs: Sequence, fens: Optional[Sequence] = None,
-                    moves: Optional[Sequence] = None):
-        self._start_games(slots, game_ids, rngs, fens, moves)
+                    moves: Optional[Sequence] = None, net_of_white: Optional[Sequence[int]] = None):
+        """net_of_white (a two-net evaluate stage only, and then required): per game, which net (0 / 1) plays white."""
+        self._start_games(slots, game_ids, rngs, fens, moves, net_of_white)
 
-    def _start_games(self, slots, game_ids, rngs, fens=None, moves=None):  # (on torch's current stream: the refill path runs it on the side stream)
+    def _start_games(self, slots, game_ids, rngs, fens=None, moves=None, net_of_white=None):  # (on torch's current stream: the refill path runs it on the side stream)
+        if self.pair:
+            if net_of_white is None or len(net_of_white) != len(slots) or any(v not in (0, 1) for v in net_of_white):
+                raise ValueError("Rollout.start_games: a two-net evaluate stage needs net_of_white (0 / 1) for every game")
+            # (ordered ahead of the slots' reset on this stream, which waits for it: done before any search of these games is enqueued)
+            self.net_of_white[torch.as_tensor(list(slots), dtype=torch.long, device=self.device)] = \
+                torch.as_tensor(list(net_of_white), dtype=torch.int32).to(self.device)
         self.eng.reset(list(slots), fens, moves, stream=self._stream())
         for i, s in enumerate(slots):
             fen = fens[i] if fens is not None else None
@@ -407,7 +425,7 @@ class Rollout:
                       (terminal[g] != 0 or self.games[g].plies >= self.max_game_moves)]
         self.host_seconds += time.perf_counter() - t0
         if done_slots:
-            new_slots, ids, rngs, fens = [], [], [], []
+            new_slots, ids, rngs, fens, mvs, nows = [], [], [], [], [], []
             for g in done_slots:
                 fin = self._finish(g, int(terminal[g]))
                 if on_finished is not None:
@@ -417,8 +435,9 @@ class Rollout:
                 nxt = refill(g) if refill is not None else None
                 if nxt is not None:
                     new_slots.append(g); ids.append(nxt[0]); rngs.append(nxt[1]); fens.append(nxt[2])
+                    mvs.append(nxt[3] if len(nxt) > 3 else None); nows.append(nxt[4] if len(nxt) > 4 else None)
             if new_slots:
-                self._start_games(new_slots, ids, rngs, fens)
+                self._start_games(new_slots, ids, rngs, fens, mvs if any(mvs) else None, nows if self.pair else None)
                 n_legal, terminal, ply = self.eng.root_info(self._stream())
         go = np.array([1 if (self.games[g] is not None and terminal[g] == 0) else 0 for g in range(self.G)], dtype=np.int32)
         if not go.any():
@@ -723,7 +742,8 @@ class Rollout:
         return n_moves
 
     def _finish_and_refill(self, done, term, on_finished, refill) -> None:
-        new_slots, ids, seeds, fens = [], [], [], []
+        """refill(slot) -> None or (game_id, rng, fen[, uci move prefix[, net_of_white]])."""
+        new_slots, ids, seeds, fens, mvs, nows = [], [], [], [], [], []
         for g in done:
             fin = self._finish(g, int(term[g]))
             if on_finished is not None:
@@ -733,8 +753,9 @@ class Rollout:
             nxt = refill(g) if refill is not None else None
             if nxt is not None:
                 new_slots.append(g); ids.append(nxt[0]); seeds.append(nxt[1]); fens.append(nxt[2])
-        if new_slots:
-            self._start_games(new_slots, ids, seeds, fens)  # (bo_games_reset synchronises its stream before it returns)
+                mvs.append(nxt[3] if len(nxt) > 3 else None); nows.append(nxt[4] if len(nxt) > 4 else None)
+        if new_slots:  # (bo_games_reset synchronises its stream before it returns)
+            self._start_games(new_slots, ids, seeds, fens, mvs if any(mvs) else None, nows if self.pair else None)
 
     def _finish(self, g: int, terminal: int) -> FinishedGame:
         gs = self.games[g]
@@ -781,7 +802,8 @@ class Rollout:
         self._active[g] = False
         nxt = refill(g) if refill is not None else None
         if nxt is not None:
-            self.start_games([g], [nxt[0]], [nxt[1]], [nxt[2]])  # its first search is begun by the next play_ply
+            self.start_games([g], [nxt[0]], [nxt[1]], [nxt[2]], [nxt[3]] if len(nxt) > 3 and nxt[3] else None,
+                             [nxt[4]] if self.pair else None)  # its first search is begun by the next play_ply
 
     @_on_main
     def swap_model(self, model: torch.nn.Module) -> None:
@@ -937,10 +959,11 @@ class CohortRollout:
             by.setdefault(int(s) // self.Gc, []).append(i)
         return by
 
-    def start_games(self, slots, game_ids, rngs, fens=None, moves=None):
+    def start_games(self, slots, game_ids, rngs, fens=None, moves=None, net_of_white=None):
         for k, pos in self._split(slots).items():
             pick = lambda seq: [seq[i] for i in pos] if seq is not None else None
-            self.parts[k].start_games([int(slots[i]) - k * self.Gc for i in pos], pick(game_ids), pick(rngs), pick(fens), pick(moves))
+            self.parts[k].start_games([int(slots[i]) - k * self.Gc for i in pos], pick(game_ids), pick(rngs), pick(fens), pick(moves),
+                                      pick(net_of_white))
 
     def _callbacks(self, k, on_finished, refill):
         base = k * self.Gc

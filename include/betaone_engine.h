@@ -444,6 +444,37 @@ int bo_nn_b1_status(bo_b1 *tower, int32_t *code_out, void *stream);
 int bo_nn_b1_word(bo_b1 *tower, void **dev_words_out);
 void bo_nn_b1_destroy(bo_b1 *tower);
 
+/* ---- (ABI 6, additions) two nets in one evaluate stage: head-to-head matches (betaone_amd/match.py) -------------------------------
+ * In a match the net that evaluates row g is the net of the side to move at game g's root; it changes every ply and differs between
+ * games.  sel_dev (int32 [batch], device): 0 = the first net, non-zero = the second.
+ * bo_nn_tower_pair_check: BO_OK if the two towers can share one launch -- both BO_TOWER_SPLIT_F16 or both BO_TOWER_SPLIT_F16_T16, same
+ * device, channels, fused head and identical layer descriptors and buffer sizes (every offset the kernel forms is then valid in both),
+ * BO_E_CONFIG otherwise.
+ * bo_nn_tower_forward_pair: bo_nn_tower_forward with the fused heads, board b on the weights of the tower sel_dev[b] names -- ONE launch,
+ * each workgroup streams the weights of its own board's net (csrc/bo_tower_s.h, bo_tower_s16.h: PAIR).  Results are bit-identical to
+ * each net's own launch.  A saturated activation sets BOTH towers' status words (bo_nn_tower_word).  Asynchronous on `stream`. */
+int bo_nn_tower_pair_check(bo_tower *tower0, bo_tower *tower1);
+int bo_nn_tower_forward_pair(bo_tower *tower0, bo_tower *tower1, const int32_t *sel_dev, const float *x_dev, void *head_a_dev,
+                             void *head_b_dev, int batch, void *stream);
+/* bo_nn_heads (flags 0 / 1 / 2; the rows are not left to bo_step_heads) with two nets' float32 head weights, row b on the set sel_dev[b]
+ * names.  A tile of boards that all use one net runs once; a tile that mixes the two runs once per net and stores only that net's rows
+ * (the cost stays in mixed tiles: keep each net's rows in contiguous runs).  Bit-identical to each net's own bo_nn_heads. */
+typedef struct bo_head_weights {
+    const float *wp, *bp;   /* policy_fc weight [4672,128] + bias [4672] */
+    const float *w1, *b1;   /* value_fc1 weight [256,2048] + bias [256] */
+    const float *w2, *b2;   /* value_fc2 weight [256] + bias [1] */
+} bo_head_weights;
+int bo_nn_heads_pair(const void *p_dev, const void *v_dev, const bo_head_weights *net0, const bo_head_weights *net1, const int32_t *sel_dev,
+                     float *policy_out_dev, float *value_out_dev, float *scratch_dev, int batch, int flags, void *stream);
+/* Every other pair of evaluate stages runs both nets over the whole batch; the rows are then merged: logits_out[b] / value_out[b] =
+ * those of net sel_dev[b].  logits [batch,width], value [batch], float32, device.  Asynchronous on `stream`. */
+int bo_nn_merge_rows(const int32_t *sel_dev, const float *logits0_dev, const float *value0_dev, const float *logits1_dev,
+                     const float *value1_dev, float *logits_out_dev, float *value_out_dev, int batch, int width, void *stream);
+/* sel_dev[g] = net_of_white_dev[g] ^ (the root of slot g has black to move), read from the engine's device state on `stream`: enqueue it
+ * behind the turn that moves the roots and ahead of the evaluation (a reference-semantics engine: NN row g = slot g).  Inactive slots
+ * get some value. */
+int bo_match_select(bo_engine *engine, const int32_t *net_of_white_dev, int32_t *sel_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
