@@ -9,6 +9,7 @@
 #include "bo_fastw.h"
 #include "bo_select_wide.h"
 #include "bo_replay.h"
+#include "bo_train.h"
 #include "bo_nn_fused.h"
 #include "bo_conv.h"
 #include "bo_tower.h"
@@ -29,6 +30,7 @@
 #include <vector>
 #include <algorithm>
 #include <deque>
+#include <type_traits>
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) {
@@ -1241,10 +1243,9 @@ extern "C" int bo_replay_size(bo_replay *r, int64_t *n_records, int64_t *n_games
     return BO_OK;
 }
 
-// A batch: record_index[i] in [0, records) counts the resident records oldest game first (ChessDataset's index space over
-// load_recent_data's concatenation, train.py:179-219); states [n,120,8,8], pi [n,4672], z [n] are written on `stream` (no wait).
-extern "C" int bo_replay_sample(bo_replay *r, int32_t n, const int64_t *record_index, float *states_dev, float *pi_dev, float *z_dev, void *stream) {
-    if (!r || n < 1 || !record_index || !states_dev || !pi_dev || !z_dev) return fail(BO_E_ARG, "bo_replay_sample: bad arguments");
+// A batch's ring slots and plies: record_index[i] in [0, records) counts the resident records oldest game first (ChessDataset's index
+// space over load_recent_data's concatenation, train.py:179-219), uploaded to r->s_slot / r->s_k on `stream`.
+static int replay_stage_indices(bo_replay *r, int32_t n, const int64_t *record_index, void *stream, const char *who) {
     if (r->prefix.empty()) {
         r->prefix.reserve(r->games.size() + 1);
         int64_t acc = 0;
@@ -1254,7 +1255,7 @@ extern "C" int bo_replay_sample(bo_replay *r, int32_t n, const int64_t *record_i
     r->h_slot.resize((size_t)n); r->h_k.resize((size_t)n);
     for (int i = 0; i < n; i++) {
         const int64_t q = record_index[i];
-        if (q < 0 || q >= r->n_records) return fail(BO_E_ARG, "bo_replay_sample: record index out of range");
+        if (q < 0 || q >= r->n_records) return fail(BO_E_ARG, std::string(who) + ": record index out of range");
         const size_t g = (size_t)(std::upper_bound(r->prefix.begin(), r->prefix.end(), q) - r->prefix.begin()) - 1;
         const int k = (int)(q - r->prefix[g]);
         r->h_slot[(size_t)i] = (int)(r->games[g].start + k);
@@ -1270,10 +1271,90 @@ extern "C" int bo_replay_sample(bo_replay *r, int32_t n, const int64_t *record_i
     }
     RT(rt_h2d(r->s_slot, r->h_slot.data(), (size_t)n * 4, stream));
     RT(rt_h2d(r->s_k, r->h_k.data(), (size_t)n * 4, stream));
+    return BO_OK;
+}
+
+// A batch: states [n,120,8,8], pi [n,4672], z [n] are written on `stream` (no wait).
+extern "C" int bo_replay_sample(bo_replay *r, int32_t n, const int64_t *record_index, float *states_dev, float *pi_dev, float *z_dev, void *stream) {
+    if (!r || n < 1 || !record_index || !states_dev || !pi_dev || !z_dev) return fail(BO_E_ARG, "bo_replay_sample: bad arguments");
+    const int rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample");
+    if (rc) return rc;
     RT(RT_LAUNCH(bo_k_replay_encode, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
                  (const float *)r->pi_val, (const float *)r->z, r->W, (const int *)r->s_slot, (const int *)r->s_k, states_dev, pi_dev, z_dev));
     // the pageable host index arrays are re-used by the next call: wait for their upload (the encode kernel itself is not waited for)
     RT(rt_sync(stream));
+    return BO_OK;
+}
+
+// The same batch with pi as the records keep it: pi_idx / pi_val [n, W] (W = the buffer's pi_width; unused slots -1 / 0).
+extern "C" int bo_replay_sample_sparse(bo_replay *r, int32_t n, const int64_t *record_index, float *states_dev, int32_t *pi_idx_dev,
+                                       float *pi_val_dev, float *z_dev, void *stream) {
+    if (!r || n < 1 || !record_index || !states_dev || !pi_idx_dev || !pi_val_dev || !z_dev) return fail(BO_E_ARG, "bo_replay_sample_sparse: bad arguments");
+    const int rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_sparse");
+    if (rc) return rc;
+    RT(RT_LAUNCH(bo_k_replay_encode_sparse, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
+                 (const float *)r->pi_val, (const float *)r->z, r->W, (const int *)r->s_slot, (const int *)r->s_k, states_dev, (int *)pi_idx_dev,
+                 pi_val_dev, z_dev));
+    RT(rt_sync(stream));
+    return BO_OK;
+}
+
+// ---- the sparse-target training loss (bo_train.h) -----------------------------------------------------------------------------
+// Calls f with a null pointer of the storage type of a BO_DTYPE_* code; false for an unknown code.
+template <class F> static bool train_dtype(int dt, F &&f) {
+    switch (dt) {
+    case BO_DTYPE_FLOAT32: f((float *)nullptr); return true;
+    case BO_DTYPE_BFLOAT16: f((bo_bf16 *)nullptr); return true;
+#if !defined(BO_WAVE_EMU)  // (the emulator's host compiler has no _Float16)
+    case BO_DTYPE_FLOAT16: f((_Float16 *)nullptr); return true;
+#endif
+    }
+    return false;
+}
+#define BO_TRAIN_TYPES(tl, tv) typedef std::remove_pointer_t<decltype(tl)> TL; typedef std::remove_pointer_t<decltype(tv)> TV
+
+static int train_loss_args(const char *who, int32_t n, int32_t W, const void *logits, const void *value, const int32_t *pi_idx,
+                           const float *pi_val, const float *z, const float *row_stats) {
+    if (n < 1 || W < 1 || W > BO_RES_CAP || !logits || !value || !pi_idx || !pi_val || !z || !row_stats) return fail(BO_E_ARG, std::string(who) + ": bad arguments");
+    return BO_OK;
+}
+
+extern "C" int bo_train_loss_forward(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
+                                     const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, float *row_stats_dev, float *loss3_dev,
+                                     void *stream) {
+    int rc = train_loss_args("bo_train_loss_forward", n, W, logits_dev, value_dev, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev);
+    if (rc) return rc;
+    if (!loss3_dev) return fail(BO_E_ARG, "bo_train_loss_forward: bad arguments");
+    bool ok = false;
+    train_dtype(logits_dtype, [&](auto *tl) {
+        ok = train_dtype(value_dtype, [&](auto *tv) {
+            BO_TRAIN_TYPES(tl, tv);
+            rc = RT_LAUNCH((bo_k_loss_fwd<TL, TV>), n, stream, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
+                           pi_val_dev, z_dev, row_stats_dev);
+        });
+    });
+    if (!ok) return fail(BO_E_CONFIG, "bo_train_loss_forward: unsupported dtype");
+    if (!rc) rc = RT_LAUNCH(bo_k_loss_reduce, 1, stream, (int)n, (const float *)row_stats_dev, loss3_dev);
+    if (rc) return fail(BO_E_HIP, std::string("bo_train_loss_forward: ") + rt_errstr(rc));
+    return BO_OK;
+}
+
+extern "C" int bo_train_loss_backward(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
+                                      const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, const float *row_stats_dev,
+                                      const float *grad_out_dev, void *dlogits_dev, void *dvalue_dev, void *stream) {
+    int rc = train_loss_args("bo_train_loss_backward", n, W, logits_dev, value_dev, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev);
+    if (rc) return rc;
+    if (!grad_out_dev || !dlogits_dev || !dvalue_dev) return fail(BO_E_ARG, "bo_train_loss_backward: bad arguments");
+    bool ok = false;
+    train_dtype(logits_dtype, [&](auto *tl) {
+        ok = train_dtype(value_dtype, [&](auto *tv) {
+            BO_TRAIN_TYPES(tl, tv);
+            rc = RT_LAUNCH((bo_k_loss_bwd<TL, TV>), n, stream, (int)n, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
+                           pi_val_dev, z_dev, row_stats_dev, grad_out_dev, (TL *)dlogits_dev, (TV *)dvalue_dev);
+        });
+    });
+    if (!ok) return fail(BO_E_CONFIG, "bo_train_loss_backward: unsupported dtype");
+    if (rc) return fail(BO_E_HIP, std::string("bo_train_loss_backward: ") + rt_errstr(rc));
     return BO_OK;
 }
 

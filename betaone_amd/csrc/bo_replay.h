@@ -11,6 +11,8 @@
 //                        key-equal positions in the WHOLE game minus one: what bo_k_encode_positions recomputes per encoded ply)
 //   bo_k_replay_encode   one wave per sample: 8 history blocks from the ply's own game (positions are stored game-contiguous),
 //                        scalar planes, dense pi row (zero fill + scatter), z
+//   bo_k_replay_encode_sparse  the same planes and z, pi as the record keeps it ([W] indices and values): for the sparse-target
+//                        loss of bo_train.h, which never needs the dense row
 #pragma once
 #include "bo_tree.h"
 
@@ -23,16 +25,23 @@ BO_KERNEL void bo_k_replay_counts(const DPos *pos, int n_pos, int *rep) {
     if (s == 0) rep[i] = c > 1 ? c - 1 : 0;
 }
 
-// sample i = the record in ring slot s_slot[i], the s_k[i]-th ply of its game (so slots s_slot - min(7, s_k) .. s_slot are its history)
-BO_KERNEL void bo_k_replay_encode(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val, const float *z,
-                                  int W, const int *s_slot, const int *s_k, float *states, float *pis, float *zs) {
-    const int b = bo_block(), s = bo_lane();
-    const int slot = s_slot[b], k = s_k[b];
+// the 120 planes of sample b: the record in ring slot `slot`, the k-th ply of its game (so slots slot - min(7, k) .. slot are its
+// history).  Shared by both samplers, so their states cannot drift apart.
+BO_DEV void replay_planes(float *states, int b, const DPos *pos, const int *rep, int slot, int k) {
+    const int s = bo_lane();
     float *row = states + (size_t)b * BO_ROW;
     const int nb = k < 7 ? k + 1 : 8, h0 = slot - (nb - 1);
     for (int pl = 0; pl < (8 - nb) * 14; pl++) row[pl * 64 + s] = 0.0f;
     for (int j = 0; j < nb; j++) encode_block(row, 8 - nb + j, pos[h0 + j], rep[h0 + j]);
     encode_scalars(row, pos[slot]);
+}
+
+// sample i = the record in ring slot s_slot[i], the s_k[i]-th ply of its game
+BO_KERNEL void bo_k_replay_encode(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val, const float *z,
+                                  int W, const int *s_slot, const int *s_k, float *states, float *pis, float *zs) {
+    const int b = bo_block(), s = bo_lane();
+    const int slot = s_slot[b];
+    replay_planes(states, b, pos, rep, slot, s_k[b]);
     // dense pi row: every address has ONE writer (lane = action mod 64), which looks its action up among the ply's few entries
     float *pr = pis + (size_t)b * BO_NUM_ACTIONS;
     const int n = pi_n[slot];
@@ -42,6 +51,22 @@ BO_KERNEL void bo_k_replay_encode(const DPos *pos, const int *rep, const int *pi
         float v = 0.0f;
         for (int e = 0; e < n; e++) v = ix[e] == a ? vx[e] : v;
         pr[a] = v;
+    }
+    if (s == 0) zs[b] = z[slot];
+}
+
+// the same sample with its pi as stored: out_idx / out_val [n, W], the record's entries first, then (-1, 0) in the unused slots
+BO_KERNEL void bo_k_replay_encode_sparse(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val,
+                                         const float *z, int W, const int *s_slot, const int *s_k, float *states, int *out_idx,
+                                         float *out_val, float *zs) {
+    const int b = bo_block(), s = bo_lane();
+    const int slot = s_slot[b];
+    replay_planes(states, b, pos, rep, slot, s_k[b]);
+    const int n = pi_n[slot];
+    for (int e = s; e < W; e += 64) {
+        const bool used = e < n;
+        out_idx[(size_t)b * W + e] = used ? pi_idx[(size_t)slot * W + e] : -1;
+        out_val[(size_t)b * W + e] = used ? pi_val[(size_t)slot * W + e] : 0.0f;
     }
     if (s == 0) zs[b] = z[slot];
 }

@@ -1,0 +1,129 @@
+// betaone_amd/csrc/bo_train.h -- the training loss of train.calculate_loss (/root/reference/train.py:222-249) with a SPARSE target.
+//
+// The reference's loss takes a dense pi row: F.cross_entropy(logits, target) + F.mse_loss(value, z).  A ply's pi has at most pi_width
+// non-zeros (2 with this engine's search), and the replay buffer keeps exactly those (bo_replay.h: bo_k_replay_encode_sparse), so the
+// loss and its gradient read them directly and the dense [B,4672] target is never built:
+//   policy_loss = (1/B) sum_b -sum_e t_be (x_b[i_be] - lse(x_b))    over the valid entries e of row b (0 <= i_be < 4672)
+//   value_loss  = (1/B) sum_b (v_b - z_b)^2
+//   dlogits[b,a] = g_p/B (softmax(x_b)_a sum_e t_be - t_ba),  dvalue[b] = 2/B (v_b - z_b) g_v
+//
+//   bo_k_loss_fwd     one wave per row.  A row is 4672 = 64 x 73 logits: lane s holds actions s, s + 64, ... in 73 registers, so the
+//                     row is read once and max / sum exp are wave butterflies (bo_wave.h, fixed order) -- no LDS, no barrier.  One
+//                     workgroup per row would add an LDS reduction and barriers for a row that one wave already holds, and a batch has
+//                     hundreds of rows to spread over the CUs.  Per row: [max, log sum exp(x - max), policy term, value term].
+//   bo_k_loss_reduce  one wave: lane s sums rows s, s + 64, ... in row order, then a butterfly -- the three losses in a fixed order
+//                     (bit-reproducible; no float atomics).  loss3 = [total, policy, value].
+//   bo_k_loss_bwd     one wave per row: the logits again, the gradient of loss3 from a DEVICE pointer (a GradScaler scale never
+//                     needs the host), softmax from the stored row statistics; dlogits / dvalue in the inputs' dtype.
+//
+// Arithmetic is float32 inside for every storage type, with expf / logf (strict libm, not exp2 approximations): parity with
+// PyTorch's float32 log_softmax.  fp16 and bf16 outputs are rounded once, to nearest even, so a value beyond the fp16 range
+// becomes inf where PyTorch's cast of its float32 gradient would (GradScaler skips the step on it).
+// Non-finite logits are not masked: a NaN or +inf logit makes the row's max NaN / inf, and its softmax and gradient NaN, as in
+// PyTorch; any non-finite logit makes the row's policy term NaN (PyTorch's dense target multiplies the -inf by a zero).  A row
+// with no valid entries adds 0 to the policy loss and gets a zero policy gradient.
+#pragma once
+#include "bo_wave.h"
+
+#define BO_LOSS_PER_LANE (BO_NUM_ACTIONS / 64)   // 73
+#define BO_LOSS_STATS 4                          // row_stats floats per row
+
+#if defined(BO_WAVE_EMU)
+#define BO_LOSS_KERNEL static
+#else
+#define BO_LOSS_KERNEL __global__ __launch_bounds__(64)
+#endif
+
+struct bo_bf16 { uint16_t u; };
+
+BO_DEV float bo_ld_f(const float *p) { return *p; }
+BO_DEV void bo_st_f(float *p, float v) { *p = v; }
+BO_DEV float bo_ld_f(const bo_bf16 *p) { return __builtin_bit_cast(float, (uint32_t)p->u << 16); }
+BO_DEV void bo_st_f(bo_bf16 *p, float v) {  // round to nearest even; NaN -> the canonical quiet NaN (c10::BFloat16's rounding)
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    p->u = v != v ? (uint16_t)0x7fc0 : (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+#if !defined(BO_WAVE_EMU)
+BO_DEV float bo_ld_f(const _Float16 *p) { return (float)*p; }
+BO_DEV void bo_st_f(_Float16 *p, float v) { *p = (_Float16)v; }  // v_cvt_f16_f32: round to nearest even, inf beyond the range
+#endif
+
+BO_DEV bool bo_loss_valid(int i) { return (unsigned)i < (unsigned)BO_NUM_ACTIONS; }
+
+template <typename TL, typename TV>
+BO_LOSS_KERNEL void bo_k_loss_fwd(int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z,
+                                  float *row_stats) {
+    const int b = bo_block(), s = bo_lane();
+    const TL *xr = logits + (size_t)b * BO_NUM_ACTIONS;
+    float x[BO_LOSS_PER_LANE];
+    float m = -__builtin_inff();
+    bool nan = false, nonfinite = false;
+    for (int j = 0; j < BO_LOSS_PER_LANE; j++) {
+        x[j] = bo_ld_f(xr + s + 64 * j);
+        nan |= x[j] != x[j];
+        nonfinite |= !(x[j] - x[j] == 0.0f);
+        m = x[j] > m ? x[j] : m;
+    }
+    float mx = bo_wave_max_f(m);
+    if (bo_ballot(nan)) mx = __builtin_nanf("");  // (PyTorch's max propagates NaN; the butterfly compare would drop it)
+    float se = 0.0f;
+    for (int j = 0; j < BO_LOSS_PER_LANE; j++) se += expf(x[j] - mx);
+    const float logsum = logf(bo_wave_sum_f(se));
+    float acc = 0.0f;
+    for (int e = s; e < W; e += 64) {
+        const int i = pi_idx[(size_t)b * W + e];
+        if (bo_loss_valid(i)) acc += pi_val[(size_t)b * W + e] * ((bo_ld_f(xr + i) - mx) - logsum);
+    }
+    acc = bo_wave_sum_f(acc);
+    const bool bad = bo_ballot(nonfinite) != 0;
+    if (s == 0) {
+        float *st = row_stats + (size_t)b * BO_LOSS_STATS;
+        const float d = bo_ld_f(value + b) - z[b];
+        st[0] = mx;
+        st[1] = logsum;
+        st[2] = bad ? __builtin_nanf("") : -acc;
+        st[3] = d * d;
+    }
+}
+
+BO_LOSS_KERNEL void bo_k_loss_reduce(int n, const float *row_stats, float *loss3) {
+    const int s = bo_lane();
+    float p = 0.0f, v = 0.0f;
+    for (int b = s; b < n; b += 64) {
+        p += row_stats[(size_t)b * BO_LOSS_STATS + 2];
+        v += row_stats[(size_t)b * BO_LOSS_STATS + 3];
+    }
+    p = bo_wave_sum_f(p);
+    v = bo_wave_sum_f(v);
+    if (s == 0) {
+        const float pl = p / (float)n, vl = v / (float)n;
+        loss3[0] = pl + vl;
+        loss3[1] = pl;
+        loss3[2] = vl;
+    }
+}
+
+template <typename TL, typename TV>
+BO_LOSS_KERNEL void bo_k_loss_bwd(int n, int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z,
+                                  const float *row_stats, const float *grad3, TL *dlogits, TV *dvalue) {
+    const int b = bo_block(), s = bo_lane();
+    const TL *xr = logits + (size_t)b * BO_NUM_ACTIONS;
+    TL *dr = dlogits + (size_t)b * BO_NUM_ACTIONS;
+    const int *ix = pi_idx + (size_t)b * W;
+    const float *vx = pi_val + (size_t)b * W;
+    // loss3 = [total, policy, value]: the policy term feeds total and policy, the value term total and value
+    const float gp = grad3[0] + grad3[1], gv = grad3[0] + grad3[2];
+    const float gb = gp / (float)n;
+    const float mx = row_stats[(size_t)b * BO_LOSS_STATS], logsum = row_stats[(size_t)b * BO_LOSS_STATS + 1];
+    float S = 0.0f;
+    for (int e = 0; e < W; e++) S += bo_loss_valid(ix[e]) ? vx[e] : 0.0f;  // (pi is normalised in float32: S need not be 1)
+    const float sgb = S * gb;
+    for (int j = 0; j < BO_LOSS_PER_LANE; j++) {
+        const int a = s + 64 * j;
+        float t = 0.0f;
+        for (int e = 0; e < W; e++) t = ix[e] == a ? vx[e] : t;  // one writer per address: the lane of the action looks it up
+        const float sm = expf((bo_ld_f(xr + a) - mx) - logsum);
+        bo_st_f(dr + a, sm * sgb - t * gb);
+    }
+    if (s == 0) bo_st_f(dvalue + b, (2.0f / (float)n) * (bo_ld_f(value + b) - z[b]) * gv);
+}

@@ -109,6 +109,7 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_replay_add_game": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(BoPosition), C.c_int32, _I32P, _I32P, _F32P, _F32P, C.POINTER(C.c_int64), C.c_void_p]),
     "bo_replay_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "bo_replay_sample": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bo_replay_sample_sparse": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)] + [C.c_void_p] * 5),
     "bo_replay_destroy": (None, [C.c_void_p]),
     "bo_nn_b1_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "bo_nn_b1_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -145,6 +146,8 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
                          + [C.c_int, C.c_int, C.c_void_p]),
     "bo_nn_merge_rows": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p]),
     "bo_match_select": (C.c_int, [C.c_void_p] * 4),
+    "bo_train_loss_forward": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6),
+    "bo_train_loss_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8),
 }
 # include/betaone_lab.h: introspection for the parity tests and in-kernel timing for bench.py / scripts/ (same library, not the boundary)
 _LAB_SYMBOLS = {

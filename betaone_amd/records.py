@@ -325,20 +325,34 @@ class GpuReplayBuffer:
                                               self._stream()))
         return states, pis, zs
 
+    def batch_sparse(self, record_index) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(states [n,120,8,8], pi_idx [n,W] int32, pi_val [n,W], values [n,1]) of the records with these indices: the states and
+        values of batch(), pi as the records keep it (W = pi_width; unused slots -1 / 0) for train.sparse_policy_value_loss."""
+        q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
+        n, W = int(q.size), self.pi_width
+        kw = dict(dtype=torch.float32, device=self.device)
+        states, zs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw)
+        idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
+        self._check(self.lib.bo_replay_sample_sparse(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), states.data_ptr(), idx.data_ptr(),
+                                                     val.data_ptr(), zs.data_ptr(), self._stream()))
+        return states, idx, val, zs
+
     def sample(self, batch_size: int, rng: Optional[np.random.Generator] = None):
         rng = rng if rng is not None else np.random.default_rng()
         return self.batch(rng.integers(0, len(self), size=int(batch_size)))
 
-    def loader(self, batch_size: int, steps: Optional[int] = None, seed: Optional[int] = None, shuffle: bool = True):
+    def loader(self, batch_size: int, steps: Optional[int] = None, seed: Optional[int] = None, shuffle: bool = True, sparse: bool = False):
         """An iterable with DataLoader's contract for train_network (train.py:252: `for states, t_policies, t_values in dataloader`):
         one epoch over the resident records in a random order (shuffle=True, the reference's DataLoader(shuffle=True)), or `steps` batches
-        drawn with replacement.  Batches are made on the buffer's device; the loop's `.to(config.DEVICE)` finds them there."""
-        return _ReplayLoader(self, int(batch_size), steps, seed, shuffle)
+        drawn with replacement.  Batches are made on the buffer's device; the loop's `.to(config.DEVICE)` finds them there.
+        sparse=True: the same batches as batch_sparse's (states, pi_idx, pi_val, values)."""
+        return _ReplayLoader(self, int(batch_size), steps, seed, shuffle, sparse)
 
 
 class _ReplayLoader:
-    def __init__(self, buf: GpuReplayBuffer, batch_size: int, steps, seed, shuffle):
+    def __init__(self, buf: GpuReplayBuffer, batch_size: int, steps, seed, shuffle, sparse=False):
         self.buf, self.batch_size, self.steps, self.seed, self.shuffle = buf, batch_size, steps, seed, shuffle
+        self.make = buf.batch_sparse if sparse else buf.batch
 
     def __len__(self) -> int:
         return self.steps if self.steps is not None else (len(self.buf) + self.batch_size - 1) // self.batch_size
@@ -348,11 +362,11 @@ class _ReplayLoader:
         n = len(self.buf)
         if self.steps is not None:
             for _ in range(self.steps):
-                yield self.buf.batch(rng.integers(0, n, size=self.batch_size))
+                yield self.make(rng.integers(0, n, size=self.batch_size))
             return
         order = rng.permutation(n) if self.shuffle else np.arange(n)
         for i in range(0, n, self.batch_size):
-            yield self.buf.batch(order[i:i + self.batch_size])
+            yield self.make(order[i:i + self.batch_size])
 
 
 def all_gather_bytes(payload: bytes, device: Optional[torch.device] = None, group=None) -> List[bytes]:

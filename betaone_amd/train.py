@@ -1,0 +1,295 @@
+"""betaone_amd/train.py -- the training stage of the AlphaZero loop: compact self-play records -> GpuReplayBuffer -> a new net.
+
+The reference trains in train.py (/root/reference/train.py:252-345 train_network, 386-481 run_training_iteration, main.py:96-127 resume):
+dense pickles read into one Python list, a DataLoader, F.cross_entropy against a dense [B,4672] target, and three .item() per step.
+Here the records stay in HBM (records.GpuReplayBuffer), a batch keeps pi as the records hold it (at most pi_width entries per ply) and
+the loss is a pair of HIP kernels that read that sparse target (csrc/bo_train.h): the dense row is never built.  The tower's forward and
+backward passes are PyTorch's (MIOpen); only the loss and its gradient are hand-written.
+
+    loss, p_loss, v_loss = sparse_policy_value_loss(logits, value, pi_idx, pi_val, z)     # train.calculate_loss, sparse target
+
+    python -m betaone_amd.train --iteration 3 --data-dir data --save-dir checkpoints --candidate cand.pth
+    python -m betaone_amd.match checkpoints/best_model.pth cand.pth --promote checkpoints/best_model.pth
+"""
+from __future__ import annotations
+
+import argparse
+import glob
+import json
+import math
+import os
+import re
+import sys
+import time
+from typing import Dict, List, Optional
+
+import torch
+import torch.nn.functional as F
+
+from . import engine as E
+from . import records as R
+
+DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # BO_DTYPE_* of include/betaone_engine.h
+ROW_STATS = 4
+
+
+def _stream(t: torch.Tensor) -> int:
+    return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else 0
+
+
+def _check(lib, rc: int):
+    if rc != 0:
+        raise E.EngineError(f"training loss: {lib.bo_last_error().decode()}")
+
+
+class _SparseLoss(torch.autograd.Function):
+    """loss3 = [total, policy, value] of bo_train_loss_forward; the backward is bo_train_loss_backward with the gradient of loss3 read
+    from the device (a GradScaler scale reaches the kernel without a host round trip)."""
+
+    @staticmethod
+    def forward(ctx, logits, value, pi_idx, pi_val, z):
+        lib = E.load_hip_library()
+        n, W = pi_idx.shape
+        if logits.dim() != 2 or logits.shape != (n, E.NUM_ACTIONS) or value.numel() != n or pi_val.shape != (n, W) or z.numel() != n:
+            raise ValueError(f"sparse loss: shapes logits {tuple(logits.shape)} value {tuple(value.shape)} pi_idx {tuple(pi_idx.shape)} "
+                             f"pi_val {tuple(pi_val.shape)} z {tuple(z.shape)}")
+        if logits.dtype not in DTYPE_CODES or value.dtype not in DTYPE_CODES:
+            raise TypeError(f"sparse loss: logits {logits.dtype} / value {value.dtype}: float32, float16 or bfloat16")
+        if pi_idx.dtype != torch.int32 or pi_val.dtype != torch.float32 or z.dtype != torch.float32:
+            raise TypeError("sparse loss: pi_idx int32, pi_val and z float32")
+        dev = logits.device
+        if any(t.device != dev for t in (value, pi_idx, pi_val, z)):
+            raise ValueError("sparse loss: all inputs on one device")
+        logits, value = logits.contiguous(), value.contiguous()
+        pi_idx, pi_val, z = pi_idx.contiguous(), pi_val.contiguous(), z.contiguous()
+        row_stats = torch.empty((n, ROW_STATS), dtype=torch.float32, device=dev)
+        loss3 = torch.empty(3, dtype=torch.float32, device=dev)
+        _check(lib, lib.bo_train_loss_forward(n, W, logits.data_ptr(), DTYPE_CODES[logits.dtype], value.data_ptr(), DTYPE_CODES[value.dtype],
+                                              pi_idx.data_ptr(), pi_val.data_ptr(), z.data_ptr(), row_stats.data_ptr(), loss3.data_ptr(),
+                                              _stream(logits)))
+        ctx.save_for_backward(logits, value, pi_idx, pi_val, z, row_stats)
+        ctx.value_shape = value.shape
+        return loss3
+
+    @staticmethod
+    def backward(ctx, g3):
+        lib = E.load_hip_library()
+        logits, value, pi_idx, pi_val, z, row_stats = ctx.saved_tensors
+        n, W = pi_idx.shape
+        g3 = g3.to(torch.float32).contiguous()
+        dlogits, dvalue = torch.empty_like(logits), torch.empty_like(value)
+        _check(lib, lib.bo_train_loss_backward(n, W, logits.data_ptr(), DTYPE_CODES[logits.dtype], value.data_ptr(), DTYPE_CODES[value.dtype],
+                                               pi_idx.data_ptr(), pi_val.data_ptr(), z.data_ptr(), row_stats.data_ptr(), g3.data_ptr(),
+                                               dlogits.data_ptr(), dvalue.data_ptr(), _stream(logits)))
+        return dlogits, dvalue.view(ctx.value_shape), None, None, None
+
+
+def sparse_policy_value_loss(logits, value, pi_idx, pi_val, z):
+    """(total, policy, value) of train.calculate_loss (train.py:222-249) with the target as [B,W] indices (-1 = unused) and values:
+    policy = mean_b -sum_e pi_val[b,e] * log_softmax(logits[b])[pi_idx[b,e]], value = mean_b (value[b] - z[b])^2, total = their sum.
+    logits [B,4672] and value [B,1] (or [B]) in float32, float16 or bfloat16 -- the net's outputs, under torch.autocast too; the three
+    losses are float32 tensors on the logits' device.  Computed on the current stream by two HIP kernels (csrc/bo_train.h)."""
+    loss3 = _SparseLoss.apply(logits, value, pi_idx, pi_val, z.reshape(-1))
+    return loss3[0], loss3[1], loss3[2]
+
+
+def dense_policy_value_loss(logits, value, target_policy, target_value):
+    """The reference's calculate_loss on a dense target (train.py:222-249): the A/B baseline of --dense-loss and the tests' yardstick."""
+    value_loss = F.mse_loss(value, target_value)
+    policy_loss = F.cross_entropy(logits, target_policy)
+    return value_loss + policy_loss, policy_loss, value_loss
+
+
+def train_steps(model, optimizer, scheduler, scaler, loader, *, sparse: bool = True, amp: bool = True, grad_clip: Optional[float] = None,
+                log_every: int = 0, log=None) -> Dict:
+    """One pass of train_network's loop (train.py:271-295) over `loader`'s batches: zero_grad, forward (under torch.autocast when amp),
+    scaler.scale(loss).backward(), unscale_, clip_grad_norm_(max_norm=GRAD_CLIP_MAX), scaler.step, scaler.update, scheduler.step.
+    sparse: batches are (states, pi_idx, pi_val, z) and the loss is sparse_policy_value_loss; otherwise (states, pi, z) and
+    dense_policy_value_loss.  The running losses stay on the device: the host reads them every `log_every` steps (0: never) and at the
+    end.  Returns {"steps", "samples", "loss": [total, policy, value] means, "losses": [steps][3] per step, "clipped": steps whose
+    gradient norm exceeded grad_clip}."""
+    if grad_clip is None:
+        from . import dropin
+
+        dropin.install()
+        import config
+
+        grad_clip = config.GRAD_CLIP_MAX
+    model.train()
+    per_step: List[torch.Tensor] = []
+    clipped: List[torch.Tensor] = []
+    samples = 0
+    for batch in loader:
+        states = batch[0]
+        dev = states.device
+        optimizer.zero_grad()
+        with torch.autocast(dev.type, enabled=amp):
+            logits, value = model(states)
+            if sparse:
+                loss, p_loss, v_loss = sparse_policy_value_loss(logits, value, batch[1], batch[2], batch[3])
+            else:
+                loss, p_loss, v_loss = dense_policy_value_loss(logits, value, batch[1], batch[2])
+        scaler.scale(loss).backward()
+        scaler.unscale_(optimizer)
+        norm = torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=grad_clip)
+        scaler.step(optimizer)
+        scaler.update()
+        scheduler.step()
+        per_step.append(torch.stack([loss.detach(), p_loss.detach(), v_loss.detach()]).float())
+        clipped.append(norm.detach() > grad_clip)
+        samples += int(states.shape[0])
+        if log is not None and log_every and len(per_step) % log_every == 0:
+            m = torch.stack(per_step[-log_every:]).mean(0).tolist()
+            log(f"step {len(per_step)}: loss {m[0]:.4f} policy {m[1]:.4f} value {m[2]:.4f} lr {optimizer.param_groups[0]['lr']:.3g}")
+    if not per_step:
+        return {"steps": 0, "samples": 0, "loss": [0.0, 0.0, 0.0], "losses": [], "clipped": 0}
+    losses = torch.stack(per_step)
+    host = losses.cpu()
+    return {"steps": len(per_step), "samples": samples, "loss": host.double().mean(0).tolist(), "losses": host.tolist(),
+            "clipped": int(torch.stack(clipped).sum().item())}
+
+
+# ---- the command line: one training iteration of main.py's loop ---------------------------------------------------------------
+
+def iteration_files(data_dir: str, iteration: int, past: int = 5):
+    """{iteration: [compact files]} for load_recent_data's window (train.py:187-193: iterations max(0, I - past) .. I), and the
+    iterations of the window that hold only the reference's pickles."""
+    found, pickles_only = {}, []
+    for it in range(max(0, iteration - past), iteration + 1):
+        d = os.path.join(data_dir, f"iter_{it}")
+        files = sorted(glob.glob(os.path.join(d, f"games_rank*{R.COMPACT_SUFFIX}")))
+        if files:
+            found[it] = files
+        elif glob.glob(os.path.join(d, "game_*.pkl")):
+            pickles_only.append(it)
+    return found, pickles_only
+
+
+def load_buffer(files: Dict[int, List[str]], device) -> R.GpuReplayBuffer:
+    games = [g for it in sorted(files) for f in files[it] for g in R.load_games(f)]
+    games = [g for g in games if int(g["n_plies"]) > 0]
+    if not games:
+        raise SystemExit("train: the compact files of the window hold no plies")
+    width = max(2, max(len(ix) for g in games for ix, _ in g["pis"]))
+    plies = sum(int(g["n_plies"]) + 1 for g in games)
+    buf = R.GpuReplayBuffer(capacity_plies=plies + 64, device=device, pi_width=width)
+    lost = buf.add(games)
+    if lost:
+        raise SystemExit(f"train: {lost} records did not fit the replay buffer")
+    return buf
+
+
+def checkpoint_iteration(path: str) -> int:
+    return int(re.search(r"checkpoint_iter_(\d+)\.pth$", path).group(1))
+
+
+def latest_checkpoint(save_dir: str) -> Optional[str]:
+    files = glob.glob(os.path.join(save_dir, "checkpoint_iter_*.pth"))
+    return max(files, key=checkpoint_iteration) if files else None
+
+
+def save_checkpoint(path: str, model, optimizer, scheduler, iteration: int):
+    """train.save_checkpoint's layout (train.py:484-520), loadable by train.load_checkpoint."""
+    torch.save({"iteration": iteration, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
+                "scheduler_state_dict": scheduler.state_dict()}, path)
+
+
+def main(argv=None) -> int:
+    from . import dropin
+    from . import match as M
+
+    dropin.install()
+    import config
+
+    ap = argparse.ArgumentParser(prog="python -m betaone_amd.train", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--iteration", type=int, default=None, help="the iteration to train (default: the one after the newest checkpoint)")
+    ap.add_argument("--data-dir", default=config.DATA_DIR)
+    ap.add_argument("--save-dir", default=config.SAVE_DIR)
+    ap.add_argument("--past", type=int, default=5, help="iterations before --iteration whose records are read too (load_recent_data)")
+    ap.add_argument("--epochs", type=int, default=config.EPOCHS_PER_ITERATION)
+    ap.add_argument("--batch", type=int, default=config.BATCH_SIZE)
+    ap.add_argument("--steps-per-epoch", type=int, default=None, help="batches drawn with replacement per epoch (default: one shuffled pass)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--init", default=None, help="initial weights (state_dict); the net takes its shape from their keys")
+    ap.add_argument("--candidate", default=None, help="write the new weights here and leave best_model.pth alone")
+    ap.add_argument("--out", default=None, help="JSON with per-epoch losses, learning rate, steps/s and samples/s")
+    ap.add_argument("--dense-loss", action="store_true", help="the reference's calculate_loss on dense batches (A/B comparisons)")
+    ap.add_argument("--no-amp", action="store_true", help="float32 forward (the reference trains under torch.autocast)")
+    ap.add_argument("--log-every", type=int, default=0)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    log = lambda s: print(f"[train] {s}", flush=True)  # noqa: E731
+
+    dev = E.runtime_device(a.device)
+    torch.manual_seed(a.seed)
+    best_path = os.path.join(a.save_dir, "best_model.pth")
+    # weights: --init, else best_model.pth, else a fresh net of config's shape (main.py:96-127 resumes from best + newest checkpoint)
+    if a.init:
+        model = M.build_net(M.load_state_dict(a.init), dev)
+    elif os.path.exists(best_path):
+        model = M.build_net(M.load_state_dict(best_path), dev)
+    else:
+        import network
+
+        model = network.PolicyValueNet().to(dev)
+    model.train()
+    optimizer = torch.optim.AdamW(model.parameters(), lr=config.LEARNING_RATE, weight_decay=config.WEIGHT_DECAY)
+    total_steps = config.NUM_ITERATIONS * config.EPOCHS_PER_ITERATION * math.ceil(config.GAME_BUFFER_SIZE / config.BATCH_SIZE)
+    scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=total_steps, eta_min=config.LR_MIN)
+    start_iter = 0
+    ck = latest_checkpoint(a.save_dir)
+    if ck:
+        state = torch.load(ck, map_location=dev)
+        model.load_state_dict(state["model_state_dict"])
+        optimizer.load_state_dict(state["optimizer_state_dict"])
+        scheduler.load_state_dict(state["scheduler_state_dict"])
+        start_iter = int(state["iteration"]) + 1
+        log(f"resumed from {ck}: iteration {start_iter}")
+    iteration = start_iter if a.iteration is None else a.iteration
+
+    files, pickles_only = iteration_files(a.data_dir, iteration, a.past)
+    for it in pickles_only:
+        log(f"iteration {it} has only pickles (game_*.pkl, written with --records pickle): its positions cannot be recovered from the "
+            f"planes; re-run its self-play with --records compact or both to train on it")
+    if not files:
+        log(f"no compact records for iterations {max(0, iteration - a.past)}..{iteration} under {a.data_dir}")
+        return 1
+    buf = load_buffer(files, dev)
+    log(f"iteration {iteration}: {len(buf)} records of {buf.n_games} games from iterations {sorted(files)} (pi_width {buf.pi_width})")
+
+    amp = not a.no_amp
+    scaler = torch.GradScaler(dev.type, enabled=amp)
+    epochs = []
+    for ep in range(a.epochs):
+        loader = buf.loader(a.batch, steps=a.steps_per_epoch, seed=a.seed * 1000003 + iteration * 1009 + ep, sparse=not a.dense_loss)
+        lr = optimizer.param_groups[0]["lr"]
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        r = train_steps(model, optimizer, scheduler, scaler, loader, sparse=not a.dense_loss, amp=amp, log_every=a.log_every, log=log)
+        dt = time.perf_counter() - t0  # (train_steps ends reading the losses: the device is done)
+        epochs.append({"epoch": ep, "steps": r["steps"], "samples": r["samples"], "loss": r["loss"][0], "policy_loss": r["loss"][1],
+                       "value_loss": r["loss"][2], "lr": lr, "clipped": r["clipped"], "seconds": dt,
+                       "steps_per_s": r["steps"] / dt if dt > 0 else None, "samples_per_s": r["samples"] / dt if dt > 0 else None})
+        log(f"epoch {ep + 1}/{a.epochs}: loss {r['loss'][0]:.4f} policy {r['loss'][1]:.4f} value {r['loss'][2]:.4f} "
+            f"({r['steps']} steps, {r['samples'] / dt if dt > 0 else 0:.0f} samples/s)")
+    buf.close()
+
+    os.makedirs(a.save_dir, exist_ok=True)
+    ck_path = os.path.join(a.save_dir, f"checkpoint_iter_{iteration}.pth")
+    save_checkpoint(ck_path, model, optimizer, scheduler, iteration)
+    weights = a.candidate or best_path
+    if os.path.dirname(weights):
+        os.makedirs(os.path.dirname(weights), exist_ok=True)
+    torch.save(model.state_dict(), weights)
+    log(f"checkpoint {ck_path}; weights {weights}")
+    if a.out:
+        summary = {"iteration": iteration, "records": sum(e["samples"] for e in epochs[:1]), "loss": "dense" if a.dense_loss else "sparse",
+                   "amp": amp, "batch": a.batch, "epochs": epochs, "checkpoint": ck_path, "weights": weights}
+        with open(a.out, "w") as f:
+            json.dump(summary, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -412,6 +412,11 @@ int bo_replay_add_game(bo_replay *rb, int32_t game_id, const bo_position *positi
 int bo_replay_size(bo_replay *rb, int64_t *n_records, int64_t *n_games);
 /* record_index[i] in [0, records): resident records, oldest game first.  states [n,120,8,8], pi [n,4672], z [n] (device, float32). */
 int bo_replay_sample(bo_replay *rb, int32_t n, const int64_t *record_index, float *states_dev, float *pi_dev, float *z_dev, void *stream);
+/* (ABI 6, addition) The same batch with pi as the records keep it, for the sparse-target loss below: states [n,120,8,8] bit-identical
+ * to bo_replay_sample's, pi_idx [n,W] int32 (unused slots -1), pi_val [n,W] float32 (unused slots 0), z [n]; W = the pi_width the
+ * buffer was created with.  Same checks as bo_replay_sample. */
+int bo_replay_sample_sparse(bo_replay *rb, int32_t n, const int64_t *record_index, float *states_dev, int32_t *pi_idx_dev, float *pi_val_dev,
+                            float *z_dev, void *stream);
 void bo_replay_destroy(bo_replay *rb);
 
 /* ---- (ABI 4) the residual tower of ONE board (a few boards) as ONE launch spread over the chip: csrc/bo_tower_b1.h ----------------
@@ -474,6 +479,22 @@ int bo_nn_merge_rows(const int32_t *sel_dev, const float *logits0_dev, const flo
  * behind the turn that moves the roots and ahead of the evaluation (a reference-semantics engine: NN row g = slot g).  Inactive slots
  * get some value. */
 int bo_match_select(bo_engine *engine, const int32_t *net_of_white_dev, int32_t *sel_dev, void *stream);
+
+/* ---- (ABI 6, additions) the training loss of train.calculate_loss with a sparse target: csrc/bo_train.h ---------------------------
+ * Replaces F.cross_entropy(logits, dense_pi) + F.mse_loss(value, z) (/root/reference/train.py:222-249) for targets of at most W entries
+ * per row: pi_idx [n,W] int32 (an entry is valid when 0 <= idx < 4672; the valid entries of a row are distinct), pi_val [n,W] float32,
+ * z [n] float32.  logits [n,4672] and value [n] in logits_dtype / value_dtype (BO_DTYPE_*); arithmetic is float32.
+ * row_stats [n,4] float32 (device): per row max, log sum exp(x - max), the policy and the value term -- written by the forward, read by
+ * the backward.  loss3 float32 [3] (device) = [policy + value, policy, value], each a mean over the rows, summed in a fixed order
+ * (bit-reproducible).  grad_out float32 [3] (device): the gradient of loss3 (e.g. [scale, 0, 0] for a backward from the total).
+ * dlogits / dvalue: the gradients in the inputs' dtypes.  Asynchronous on `stream`; capturable. */
+enum { BO_DTYPE_FLOAT32 = 0, BO_DTYPE_FLOAT16 = 1, BO_DTYPE_BFLOAT16 = 2 };
+int bo_train_loss_forward(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
+                          const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, float *row_stats_dev, float *loss3_dev,
+                          void *stream);
+int bo_train_loss_backward(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
+                           const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, const float *row_stats_dev,
+                           const float *grad_out_dev, void *dlogits_dev, void *dvalue_dev, void *stream);
 
 #ifdef __cplusplus
 }
