@@ -10,6 +10,7 @@
 #include "bo_select_wide.h"
 #include "bo_replay.h"
 #include "bo_train.h"
+#include "bo_pgn.h"
 #include "bo_nn_fused.h"
 #include "bo_conv.h"
 #include "bo_tower.h"
@@ -161,6 +162,13 @@ static bool parse_fen(const char *fen, DPos *out) {
     out->halfmove = half;
     out->fullmove = full;
     return true;
+}
+
+// a PGN game's root: its [FEN] (empty: the start position), with exactly one king per side (the move generator needs them)
+static bool pgn_fen_root(const std::string &fen, DPos *out) {
+    if (!parse_fen(fen.empty() ? START_FEN : fen.c_str(), out)) return false;
+    const uint64_t k = out->bb[BB_K];
+    return __builtin_popcountll(k & out->bb[BB_WHITE]) == 1 && __builtin_popcountll(k & out->bb[BB_BLACK]) == 1;
 }
 
 static bool parse_uci_moves(const char *s, std::vector<bo_mv> *out) {
@@ -1298,6 +1306,112 @@ extern "C" int bo_replay_sample_sparse(bo_replay *r, int32_t n, const int64_t *r
     RT(rt_sync(stream));
     return BO_OK;
 }
+
+// ---- PGN pretraining (bo_pgn.h) --------------------------------------------------------------------------------------------------
+static_assert(sizeof(DPos) == BO_PGN_POSITION_BYTES, "ring slot size");
+
+extern "C" int bo_pgn_parse(const char *text, int64_t n_bytes, int32_t final_chunk, int64_t max_games, int64_t max_tokens, int64_t *consumed,
+                            bo_pgn **out) {
+    if (!out || !consumed || n_bytes < 0 || (n_bytes && !text)) return fail(BO_E_ARG, "bo_pgn_parse: bad arguments");
+    bo_pgn *p = new bo_pgn();
+    *consumed = pgn_parse(p, text, n_bytes, final_chunk != 0, max_games, max_tokens);
+    *out = p;
+    return BO_OK;
+}
+
+extern "C" int bo_pgn_size(const bo_pgn *p, int64_t *n_games, int64_t *n_tokens, int64_t *scratch_bytes) {
+    if (!p) return fail(BO_E_ARG, "null handle");
+    const int64_t g = (int64_t)p->status.size(), t = (int64_t)p->tok.size();
+    if (n_games) *n_games = g;
+    if (n_tokens) *n_tokens = t;
+    // tokens, has_eval, target, then per game: token range [2], root, slot0, result[2] -- 16-byte aligned pieces
+    auto al = [](int64_t b) { return (b + 15) & ~(int64_t)15; };
+    if (scratch_bytes) *scratch_bytes = al(4 * t) + al(t) + al(4 * t) + al(8 * g) + al((int64_t)sizeof(DPos) * g) + al(4 * g) + al(8 * g) + 16;
+    return BO_OK;
+}
+
+extern "C" int bo_pgn_export(const bo_pgn *p, int32_t *status, int32_t *tok_off, bo_position *roots, uint32_t *tokens, int32_t *has_eval,
+                             float *target) {
+    if (!p) return fail(BO_E_ARG, "null handle");
+    const size_t g = p->status.size(), t = p->tok.size();
+    for (size_t i = 0; i < g; i++) {
+        if (status) status[i] = p->status[i];
+        if (roots) to_abi(p->root[i], &roots[i]);
+    }
+    if (tok_off) for (size_t i = 0; i <= g; i++) tok_off[i] = p->tok_off[i];
+    for (size_t i = 0; i < t; i++) {
+        if (tokens) tokens[i] = p->tok[i];
+        if (has_eval) has_eval[i] = p->has_eval[i];
+        if (target) target[i] = p->target[i];
+    }
+    return BO_OK;
+}
+
+extern "C" int bo_pgn_replay(const bo_pgn *p, const int64_t *slot0, int64_t capacity, void *scratch_dev, int64_t scratch_bytes, void *pos_dev,
+                             int32_t *act_dev, float *z_dev, int32_t *smp_dev, int32_t *n_plies_out, int32_t *status_out, void *stream) {
+    if (!p || !slot0 || capacity < 1 || capacity > (int64_t)0x7fffffff || !scratch_dev || !pos_dev || !act_dev || !z_dev || !smp_dev)
+        return fail(BO_E_ARG, "bo_pgn_replay: bad arguments");
+    int64_t need = 0;
+    bo_pgn_size(p, nullptr, nullptr, &need);
+    if (scratch_bytes < need) return fail(BO_E_ARG, "bo_pgn_replay: scratch smaller than bo_pgn_size's scratch_bytes");
+    const int G = (int)p->status.size();
+    // the games that go to the device (status ok so far, at least one token), each in its own slots of the ring
+    std::vector<int> launch, rng, s0;
+    std::vector<DPos> roots;
+    for (int g = 0; g < G; g++) {
+        const int nt = p->tok_off[g + 1] - p->tok_off[g];
+        if (n_plies_out) n_plies_out[g] = 0;
+        if (status_out) status_out[g] = p->status[g];
+        if (slot0[g] < 0 || nt == 0 || (p->status[g] != BO_PGN_OK && p->status[g] != BO_PGN_NULL_MOVE && p->status[g] != BO_PGN_UNSUPPORTED)) continue;
+        if (slot0[g] + nt > capacity) return fail(BO_E_ARG, "bo_pgn_replay: a game's slots run past the ring");
+        launch.push_back(g);
+        rng.push_back(p->tok_off[g]);
+        rng.push_back(p->tok_off[g + 1]);
+        s0.push_back((int)slot0[g]);
+        roots.push_back(p->root[g]);
+    }
+    if (launch.empty()) return BO_OK;
+    const int64_t t = (int64_t)p->tok.size();
+    auto al = [](int64_t b) { return (b + 15) & ~(int64_t)15; };
+    char *d = (char *)scratch_dev;
+    uint32_t *d_tok = (uint32_t *)d; d += al(4 * t);
+    int8_t *d_ev = (int8_t *)d; d += al(t);
+    float *d_tg = (float *)d; d += al(4 * t);
+    int *d_rng = (int *)d; d += al(8 * G);
+    DPos *d_root = (DPos *)d; d += al((int64_t)sizeof(DPos) * G);
+    int *d_s0 = (int *)d; d += al(4 * G);
+    int *d_res = (int *)d;
+    const int n = (int)launch.size();
+    std::vector<int> res((size_t)2 * n);
+    int rc = t ? rt_h2d(d_tok, p->tok.data(), (size_t)t * 4, stream) : 0;
+    if (!rc && t) rc = rt_h2d(d_ev, p->has_eval.data(), (size_t)t, stream);
+    if (!rc && t) rc = rt_h2d(d_tg, p->target.data(), (size_t)t * 4, stream);
+    if (!rc) rc = rt_h2d(d_rng, rng.data(), rng.size() * 4, stream);
+    if (!rc) rc = rt_h2d(d_root, roots.data(), roots.size() * sizeof(DPos), stream);
+    if (!rc) rc = rt_h2d(d_s0, s0.data(), s0.size() * 4, stream);
+    if (!rc) rc = RT_LAUNCH(bo_k_pgn_replay, n, stream, (const uint32_t *)d_tok, (const int *)d_rng, (const DPos *)d_root, (const int8_t *)d_ev,
+                            (const float *)d_tg, (const int *)d_s0, (DPos *)pos_dev, (int *)act_dev, z_dev, (int *)smp_dev, d_res);
+    if (!rc) rc = rt_d2h(res.data(), d_res, res.size() * 4, stream);
+    const int rc2 = rt_sync(stream);
+    if (rc || rc2) return fail(BO_E_HIP, std::string("bo_pgn_replay: ") + rt_errstr(rc ? rc : rc2));
+    for (int i = 0; i < n; i++) {
+        const int g = launch[i];
+        if (n_plies_out) n_plies_out[g] = res[2 * i];
+        if (status_out && res[2 * i + 1] != BO_PGN_OK) status_out[g] = res[2 * i + 1];
+    }
+    return BO_OK;
+}
+
+extern "C" int bo_pgn_sample(const void *pos_dev, const int32_t *act_dev, const float *z_dev, int32_t n, const int32_t *game_slot_dev,
+                             const int32_t *ply_dev, float *states_dev, int32_t *pi_idx_dev, float *pi_val_dev, float *z_out_dev, void *stream) {
+    if (!pos_dev || !act_dev || !z_dev || n < 1 || !game_slot_dev || !ply_dev || !states_dev || !pi_idx_dev || !pi_val_dev || !z_out_dev)
+        return fail(BO_E_ARG, "bo_pgn_sample: bad arguments");
+    RT(RT_LAUNCH(bo_k_pgn_sample, n, stream, (const DPos *)pos_dev, (const int *)act_dev, z_dev, (const int *)game_slot_dev, (const int *)ply_dev,
+                 states_dev, (int *)pi_idx_dev, pi_val_dev, z_out_dev));
+    return BO_OK;
+}
+
+extern "C" void bo_pgn_destroy(bo_pgn *p) { delete p; }
 
 // ---- the sparse-target training loss (bo_train.h) -----------------------------------------------------------------------------
 // Calls f with a null pointer of the storage type of a BO_DTYPE_* code; false for an unknown code.

@@ -27,13 +27,17 @@ BO_KERNEL void bo_k_replay_counts(const DPos *pos, int n_pos, int *rep) {
 
 // the 120 planes of sample b: the record in ring slot `slot`, the k-th ply of its game (so slots slot - min(7, k) .. slot are its
 // history).  Shared by both samplers, so their states cannot drift apart.
-BO_DEV void replay_planes(float *states, int b, const DPos *pos, const int *rep, int slot, int k) {
+// rep_of(h) = the repetition count of the board in slot h (the PGN sampler of bo_pgn.h counts it live).
+template <class RepOf> BO_DEV void replay_planes_rep(float *states, int b, const DPos *pos, int slot, int k, RepOf rep_of) {
     const int s = bo_lane();
     float *row = states + (size_t)b * BO_ROW;
     const int nb = k < 7 ? k + 1 : 8, h0 = slot - (nb - 1);
     for (int pl = 0; pl < (8 - nb) * 14; pl++) row[pl * 64 + s] = 0.0f;
-    for (int j = 0; j < nb; j++) encode_block(row, 8 - nb + j, pos[h0 + j], rep[h0 + j]);
+    for (int j = 0; j < nb; j++) encode_block(row, 8 - nb + j, pos[h0 + j], rep_of(h0 + j));
     encode_scalars(row, pos[slot]);
+}
+BO_DEV void replay_planes(float *states, int b, const DPos *pos, const int *rep, int slot, int k) {
+    replay_planes_rep(states, b, pos, slot, k, [rep](int h) { return rep[h]; });
 }
 
 // sample i = the record in ring slot s_slot[i], the s_k[i]-th ply of its game

@@ -148,6 +148,12 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_match_select": (C.c_int, [C.c_void_p] * 4),
     "bo_train_loss_forward": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6),
     "bo_train_loss_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8),
+    "bo_pgn_parse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]),
+    "bo_pgn_size": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int64)] * 3),
+    "bo_pgn_export": (C.c_int, [C.c_void_p, _I32P, _I32P, C.c_void_p, C.c_void_p, _I32P, _F32P]),
+    "bo_pgn_replay": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [_I32P, _I32P, C.c_void_p]),
+    "bo_pgn_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7),
+    "bo_pgn_destroy": (None, [C.c_void_p]),
 }
 # include/betaone_lab.h: introspection for the parity tests and in-kernel timing for bench.py / scripts/ (same library, not the boundary)
 _LAB_SYMBOLS = {

@@ -496,6 +496,48 @@ int bo_train_loss_backward(int32_t n, int32_t W, const void *logits_dev, int32_t
                            const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, const float *row_stats_dev,
                            const float *grad_out_dev, void *dlogits_dev, void *dvalue_dev, void *stream);
 
+/* ---- (ABI 6, additions) PGN pretraining: csrc/bo_pgn.h --------------------------------------------------------------------------
+ * Replaces the reference's PGNDataset (train.py:81-160: python-chess reads the games, parses SAN and encodes 120 planes per position in
+ * DataLoader workers).  Host: bo_pgn_parse tokenises PGN text -- per game the root ([FEN] if present, else the start position), one
+ * packed SAN token per mainline move, per move "has eval" and the float32 target -value of its eval comment, and a status.  Device:
+ * bo_pgn_replay replays the tokens (one wave per game; legal moves on the device, the token resolved by a ballot) into a ring of
+ * position slots that the caller owns; bo_pgn_sample encodes samples from it with the LIVE repetition tracker of the reference's parse.
+ * text: PGN bytes.  final_chunk = 0: the text after the last complete game is not consumed (*consumed says how far the games went; pass
+ * the rest again with the next chunk); 1: the text ends there.  max_games / max_tokens (< 0: no limit) stop before the game that would
+ * exceed them (one game is always taken).  The handle is host memory. */
+enum {
+    BO_PGN_OK = 0,           /* every token replayed */
+    BO_PGN_VARIANT = 1,      /* [Variant] other than standard / chess: skipped, no tokens */
+    BO_PGN_BAD_FEN = 2,      /* unparsable [FEN], or not one king per side: skipped, no tokens */
+    BO_PGN_UNSUPPORTED = 3,  /* a movetext word that is neither SAN nor castling: the tokens before it are kept */
+    BO_PGN_NULL_MOVE = 4,    /* a null move (--, Z0, 0000, @@@@): the tokens before it are kept */
+    BO_PGN_ILLEGAL = 5,      /* (bo_pgn_replay) a token no legal move matches: the plies before it are kept */
+    BO_PGN_AMBIGUOUS = 6     /* (bo_pgn_replay) a token several legal moves match: the plies before it are kept */
+};
+#define BO_PGN_POSITION_BYTES 80   /* one ring slot of pos_dev */
+typedef struct bo_pgn_s bo_pgn;
+int bo_pgn_parse(const char *text, int64_t n_bytes, int32_t final_chunk, int64_t max_games, int64_t max_tokens, int64_t *consumed,
+                 bo_pgn **out);
+/* games, tokens, and the device scratch bo_pgn_replay needs for this handle (any pointer may be NULL) */
+int bo_pgn_size(const bo_pgn *p, int64_t *n_games, int64_t *n_tokens, int64_t *scratch_bytes);
+/* host copies (any pointer may be NULL): status [games], tok_off [games + 1] (game g's tokens are tok_off[g] .. tok_off[g+1]), roots
+ * [games], tokens / has_eval / target [tokens].  A token: bits 0-5 destination square, 6-9 from-file + 1, 10-13 from-rank + 1, 14-16
+ * piece (0 none, 2..6 = N B R Q K), 17-19 promotion (0 none, 2..6), 20-21 kind (0 SAN, 1 O-O, 2 O-O-O). */
+int bo_pgn_export(const bo_pgn *p, int32_t *status, int32_t *tok_off, bo_position *roots, uint32_t *tokens, int32_t *has_eval, float *target);
+/* Replays game g into ring slots slot0[g] .. slot0[g] + its tokens - 1 (slot0 host int64 [games]; < 0: skip the game; every range
+ * inside [0, capacity); games must not share slots).  Per replayed ply t in slot s = slot0[g] + t: pos_dev[s] (the position before the
+ * move, BO_PGN_POSITION_BYTES), act_dev[s] (the move's action index), smp_dev[s] (1: ply t is a sample -- move t + 1 was replayed and
+ * has an eval), z_dev[s] (the sample's target, move t + 1's).  n_plies_out / status_out (host int32 [games], may be NULL): the plies
+ * replayed and the final status.  scratch_dev: >= bo_pgn_size's scratch_bytes of device memory.  Synchronises `stream`. */
+int bo_pgn_replay(const bo_pgn *p, const int64_t *slot0, int64_t capacity, void *scratch_dev, int64_t scratch_bytes, void *pos_dev,
+                  int32_t *act_dev, float *z_dev, int32_t *smp_dev, int32_t *n_plies_out, int32_t *status_out, void *stream);
+/* Sample i = ply ply_dev[i] of the game whose ply 0 is in slot game_slot_dev[i] (device int32 [n]): states [n,120,8,8] with the
+ * repetition counts of the game's plies 0 .. ply (the reference's live tracker), pi_idx [n] = act, pi_val [n] = 1, z [n].
+ * Asynchronous on `stream`. */
+int bo_pgn_sample(const void *pos_dev, const int32_t *act_dev, const float *z_dev, int32_t n, const int32_t *game_slot_dev, const int32_t *ply_dev,
+                  float *states_dev, int32_t *pi_idx_dev, float *pi_val_dev, float *z_out_dev, void *stream);
+void bo_pgn_destroy(bo_pgn *p);
+
 #ifdef __cplusplus
 }
 #endif
