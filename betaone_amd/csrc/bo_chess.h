@@ -319,7 +319,9 @@ BO_DEV bool index_to_move(int index, const DPos &p, bo_mv *out) {
 // ---- wave-parallel legal move generation ------------------------------------------------------------
 // All 64 lanes call this with the SAME position.  Writes the legal moves, in python-chess
 // generation order, to out[0..n) (LDS or global) and returns n; *in_check_out = side to move in check.
-BO_DEV_NOINLINE int bo_movegen(const DPos &P, bo_mv *out, bool *in_check_out) {
+// bo_movegen_inline is the body, for a kernel that must keep its position in registers (a call to the out-of-line bo_movegen
+// passes P by address, i.e. through scratch); every other caller takes the out-of-line one below.
+BO_DEV int bo_movegen_inline(const DPos &P, bo_mv *out, bool *in_check_out) {
     const int s = bo_lane();
     const uint64_t bit = BIT(s);
     const int us = pos_turn(P);
@@ -450,3 +452,4 @@ BO_DEV_NOINLINE int bo_movegen(const DPos &P, bo_mv *out, bool *in_check_out) {
     *in_check_out = nchk > 0;
     return total;
 }
+BO_DEV_NOINLINE int bo_movegen(const DPos &P, bo_mv *out, bool *in_check_out) { return bo_movegen_inline(P, out, in_check_out); }

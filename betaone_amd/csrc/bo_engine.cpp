@@ -11,6 +11,7 @@
 #include "bo_replay.h"
 #include "bo_train.h"
 #include "bo_pgn.h"
+#include "bo_san.h"
 #include "bo_nn_fused.h"
 #include "bo_conv.h"
 #include "bo_tower.h"
@@ -1412,6 +1413,61 @@ extern "C" int bo_pgn_sample(const void *pos_dev, const int32_t *act_dev, const 
 }
 
 extern "C" void bo_pgn_destroy(bo_pgn *p) { delete p; }
+
+// ---- PGN export (bo_san.h) -----------------------------------------------------------------------------------------------------
+extern "C" int bo_san_render(int32_t n_games, int32_t n_positions, const int32_t *game_off_dev, const void *positions_dev,
+                             const int32_t *moves_dev, void *san_dev, uint8_t *state_dev, int32_t *bad_dev, void *stream) {
+    if (n_games < 1 || n_positions < n_games || !game_off_dev || !positions_dev || !moves_dev || !san_dev || !state_dev || !bad_dev)
+        return fail(BO_E_ARG, "bo_san_render: bad arguments");
+    RT(RT_LAUNCH(bo_k_san_render, n_positions, stream, (const int *)game_off_dev, (int)n_games, (int)n_positions,
+                 (const bo_position *)positions_dev, (const int *)moves_dev, (uint64_t *)san_dev, state_dev));
+    RT(RT_LAUNCH(bo_k_san_status, n_games, stream, (const int *)game_off_dev, (int)n_positions, (const uint8_t *)state_dev, (int *)bad_dev));
+    return BO_OK;
+}
+
+// formatting only: the ep field is the position's ep_key, which the device resolved (python-chess Board.fen()'s "legal" e.p.)
+extern "C" int bo_position_fen(const bo_position *p, char *out, int32_t cap) {
+    if (!p || !out || cap < 1) return fail(BO_E_ARG, "bo_position_fen: bad arguments");
+    if (p->ep_key < -1 || p->ep_key > 63) return fail(BO_E_ARG, "bo_position_fen: ep_key must be resolved (-1 or a square)");
+    std::string f;
+    for (int r = 7; r >= 0; r--) {
+        int empty = 0;
+        for (int c = 0; c < 8; c++) {
+            const uint64_t b = BIT(r * 8 + c);
+            int t = -1;
+            for (int i = 0; i < 6; i++) if (p->bb[i] & b) t = i;
+            if (t < 0) { empty++; continue; }
+            if (empty) { f.push_back((char)('0' + empty)); empty = 0; }
+            const char l = "pnbrqk"[t];
+            f.push_back((p->bb[BB_WHITE] & b) ? (char)(l - 'a' + 'A') : l);
+        }
+        if (empty) f.push_back((char)('0' + empty));
+        if (r) f.push_back('/');
+    }
+    f += p->turn ? " w " : " b ";
+    const size_t c0 = f.size();
+    for (int i = 0; i < 4; i++) if (p->castling & (1u << i)) f.push_back("KQkq"[i]);
+    if (f.size() == c0) f.push_back('-');
+    f.push_back(' ');
+    if (p->ep_key >= 0) { f.push_back((char)('a' + (p->ep_key & 7))); f.push_back((char)('1' + (p->ep_key >> 3))); }
+    else f.push_back('-');
+    f += " " + std::to_string(p->halfmove_clock) + " " + std::to_string(p->fullmove_number);
+    if ((int64_t)f.size() + 1 > cap) return fail(BO_E_ARG, "bo_position_fen: buffer too small");
+    memcpy(out, f.c_str(), f.size() + 1);
+    return BO_OK;
+}
+
+extern "C" int bo_pgn_movetext(int32_t n_plies, const void *san, const uint8_t *state, int32_t root_turn, int32_t root_fullmove,
+                               const uint8_t *comments, const char *result, char *out, int64_t cap, int64_t *len_out) {
+    if (n_plies < 0 || (n_plies && !san) || !state || !result || !out || !len_out) return fail(BO_E_ARG, "bo_pgn_movetext: bad arguments");
+    std::string t;
+    if (!pgn_movetext(n_plies, (const uint8_t *)san, state, root_turn != 0, root_fullmove, comments, result, &t))
+        return fail(BO_E_ARG, "bo_pgn_movetext: a ply has no SAN");
+    *len_out = (int64_t)t.size();
+    if ((int64_t)t.size() > cap) return fail(BO_E_ARG, "bo_pgn_movetext: buffer too small");
+    memcpy(out, t.data(), t.size());
+    return BO_OK;
+}
 
 // ---- the sparse-target training loss (bo_train.h) -----------------------------------------------------------------------------
 // Calls f with a null pointer of the storage type of a BO_DTYPE_* code; false for an unknown code.

@@ -154,6 +154,10 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_pgn_replay": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [_I32P, _I32P, C.c_void_p]),
     "bo_pgn_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7),
     "bo_pgn_destroy": (None, [C.c_void_p]),
+    "bo_san_render": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 7),
+    "bo_position_fen": (C.c_int, [C.POINTER(BoPosition), C.c_char_p, C.c_int32]),
+    "bo_pgn_movetext": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int64,
+                                  C.POINTER(C.c_int64)]),
 }
 # include/betaone_lab.h: introspection for the parity tests and in-kernel timing for bench.py / scripts/ (same library, not the boundary)
 _LAB_SYMBOLS = {

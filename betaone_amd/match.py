@@ -2,7 +2,7 @@
 betaone_amd/match.py -- head-to-head matches between two networks on the GPU, and the AlphaGo Zero promotion gate.
 
     python -m betaone_amd.match BEST.pth CANDIDATE.pth --games N --slots G --cohorts K --sims S \\
-        [--openings FILE] [--open-plies P] [--t-final T] [--out match.json] [--promote DEST --threshold 0.55]
+        [--openings FILE] [--open-plies P] [--t-final T] [--out match.json] [--promote DEST --threshold 0.55] [--pgn games.pgn]
 
 Net A (the first checkpoint) and net B (the second) share ONE evaluate stage (fused_net.PairedNet): row g of every evaluation is
 evaluated by the net of the side to move at game g's root (bo_match_select sets the per-row selector on the device, right before each
@@ -250,9 +250,10 @@ def game_result(fin, net_of_white: int) -> Tuple[float, str]:
     return 0.5, ("draw" if fin.terminal == 2 else "move_limit")
 
 
-def play_match(ro, sched: MatchScheduler, step_of=None, seed_iteration: int = 0, log=None) -> Dict:
+def play_match(ro, sched: MatchScheduler, step_of=None, seed_iteration: int = 0, log=None, finished: Optional[Dict] = None) -> Dict:
     """Drive `ro` (a CohortRollout / Rollout over a PairedNet, or a stand-in with the same start_games / play_ply) until every game of
-    `sched` is finished.  step_of(slot) -> the cohort ply at which a game started in `slot` during play_ply makes its first search."""
+    `sched` is finished.  step_of(slot) -> the cohort ply at which a game started in `slot` during play_ply makes its first search.
+    finished: a dict that receives game_id -> FinishedGame (for write_match_pgn)."""
     from . import engine as E
     from .selfplay_main import game_seed
 
@@ -266,6 +267,8 @@ def play_match(ro, sched: MatchScheduler, step_of=None, seed_iteration: int = 0,
     def on_finished(fin):
         g = by_slot.pop(fin.slot)
         r, how = game_result(fin, g.net_of_white)
+        if finished is not None:
+            finished[g.game_id] = fin
         games[g.game_id] = {"game_id": g.game_id, "opening": g.opening, "fen": g.fen or START_FEN, "prefix": g.moves,
                             "white": "AB"[g.net_of_white], "black": "AB"[1 - g.net_of_white],
                             "moves": [E.move_to_uci(m) for m in fin.moves], "result_b": r, "termination": how,
@@ -298,6 +301,19 @@ def play_match(ro, sched: MatchScheduler, step_of=None, seed_iteration: int = 0,
     seconds = time.perf_counter() - t0
     return {"games": [games[k] for k in sorted(games)], "seconds": seconds, "plies": ro.n_plies - plies0, "sims": ro.n_sims - sims0,
             "lane_breaks": sched.lane_breaks}
+
+
+def write_match_pgn(fh, played: Dict, finished: Dict, a: str, b: str, device="cuda:0", date: Optional[str] = None) -> int:
+    """Every game of a match as PGN, in game-id order: White / Black "A (path)" or "B (path)", Round "<opening + 1>.<1|2>", the
+    opening's prefix moves with a {book} comment."""
+    from . import pgn_write
+
+    games = played["games"]
+    names = {"A": f"A ({a})", "B": f"B ({b})"}
+    tags = [{"Event": "BetaOne match", "Date": date or pgn_write.today(), "Round": f"{g['opening'] + 1}.{g['game_id'] % 2 + 1}",
+             "White": names[g["white"]], "Black": names[g["black"]]} for g in games]
+    fins = [finished[g["game_id"]] for g in games]
+    return pgn_write.write_pgn(fh, fins, tags=tags, device=device, book_plies=[int(getattr(f, "first_ply", 0)) for f in fins])
 
 
 def summarize(played: Dict, with_pairs: bool) -> Dict:
@@ -344,6 +360,7 @@ def main(argv=None) -> int:
     ap.add_argument("--promote", default=None, metavar="DEST")
     ap.add_argument("--threshold", type=float, default=0.55)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--pgn", default=None, metavar="FILE", help="also write every game as PGN (SAN rendered on the GPU)")
     args = ap.parse_args(argv)
 
     import torch
@@ -361,11 +378,15 @@ def main(argv=None) -> int:
                        dirichlet_alpha=0.0, temperature=(args.open_plies, 1.0, args.t_final), max_game_moves=args.max_game_moves,
                        rng_mode="native", device=str(dev))
     sched = MatchScheduler(openings, args.games, args.slots, args.cohorts)
+    finished: Optional[Dict] = {} if args.pgn else None
     try:
-        played = play_match(ro, sched, seed_iteration=args.seed_iteration, log=print)
+        played = play_match(ro, sched, seed_iteration=args.seed_iteration, log=print, finished=finished)
         pair.check_overflow()
     finally:
         ro.close()
+    if args.pgn:
+        with open(args.pgn, "w", encoding="utf-8", newline="\n") as fh:
+            write_match_pgn(fh, played, finished, args.a, args.b, device=str(dev))
     st = summarize(played, with_pairs=args.openings is not None)
     st["route"] = pair.route
     st["promoted"] = promote(sd_b, args.promote, st["score"], args.threshold) if args.promote else False

@@ -31,7 +31,7 @@ import torch
 
 from . import engine as E
 
-STATUS_NAMES = ["ok", "variant", "bad_fen", "unsupported", "null_move", "illegal", "ambiguous"]  # BO_PGN_* of include/betaone_engine.h
+STATUS_NAMES = ["ok", "variant", "bad_fen", "unsupported", "null_move", "illegal", "ambiguous", "mismatch"]  # BO_PGN_* of include/betaone_engine.h
 POSITION_BYTES = 80  # BO_PGN_POSITION_BYTES
 MAX_READER_THREADS = 16  # host threads a pretraining run may use
 
@@ -168,8 +168,7 @@ class _Reader:
             raise self.err
         return b
 
-    def close(self):
-        self.stop = True
+    def _drain(self):
         try:
             while True:
                 b = self.q.get_nowait()
@@ -177,6 +176,27 @@ class _Reader:
                     b.close()
         except queue.Empty:
             pass
+
+    def close(self):
+        """Stops the thread and waits for it: it may be inside the library's parser, and an interpreter that exits meanwhile frees
+        memory under it.  The thread sees `stop` within one block's parse or one 0.2 s queue wait; draining the queue lets its final
+        put go through.  (Bounded at 60 s.)"""
+        self.stop = True
+        for _ in range(600):
+            self._drain()
+            self.t.join(timeout=0.1)
+            if not self.t.is_alive():
+                break
+        self._drain()
+
+
+def _close_readers(readers):
+    for r in readers:  # (stop them all first: they wind down together)
+        if r is not None:
+            r.stop = True
+    for r in readers:
+        if r is not None:
+            r.close()
 
 
 class _Block:
@@ -302,8 +322,7 @@ class PgnIngest:
                         break
                     self._ingest(blk, keep=False)
         finally:
-            for r in readers:
-                r.close()
+            _close_readers(readers)
         return self.counts["samples"]
 
     # ---- batches ----
@@ -370,9 +389,7 @@ class PgnIngest:
                         continue
                     yield got
         finally:
-            for r in readers:
-                if r is not None:
-                    r.close()
+            _close_readers(readers)
 
     def _refs_shuffle(self, B: int):
         rng = np.random.default_rng(self.seed)

@@ -512,7 +512,8 @@ enum {
     BO_PGN_UNSUPPORTED = 3,  /* a movetext word that is neither SAN nor castling: the tokens before it are kept */
     BO_PGN_NULL_MOVE = 4,    /* a null move (--, Z0, 0000, @@@@): the tokens before it are kept */
     BO_PGN_ILLEGAL = 5,      /* (bo_pgn_replay) a token no legal move matches: the plies before it are kept */
-    BO_PGN_AMBIGUOUS = 6     /* (bo_pgn_replay) a token several legal moves match: the plies before it are kept */
+    BO_PGN_AMBIGUOUS = 6,    /* (bo_pgn_replay) a token several legal moves match: the plies before it are kept */
+    BO_PGN_MISMATCH = 7      /* (bo_san_render) a legal move whose position after it is not the game's next position */
 };
 #define BO_PGN_POSITION_BYTES 80   /* one ring slot of pos_dev */
 typedef struct bo_pgn_s bo_pgn;
@@ -537,6 +538,33 @@ int bo_pgn_replay(const bo_pgn *p, const int64_t *slot0, int64_t capacity, void 
 int bo_pgn_sample(const void *pos_dev, const int32_t *act_dev, const float *z_dev, int32_t n, const int32_t *game_slot_dev, const int32_t *ply_dev,
                   float *states_dev, int32_t *pi_idx_dev, float *pi_val_dev, float *z_out_dev, void *stream);
 void bo_pgn_destroy(bo_pgn *p);
+
+/* ---- (ABI 6, additions) PGN export: csrc/bo_san.h ----------------------------------------------------------------------------
+ * The inverse of the replay above: games held as positions P_0..P_n and moves m_0..m_{n-1} (P_{i+1} the position after m_i -- what
+ * FinishedGame and the compact records hold) rendered as PGN movetext.  The SAN is rendered on the device, one wave per position.
+ *
+ * bo_san_render: positions_dev (bo_position [n_positions], device) hold the games back to back, game g in positions
+ * game_off_dev[g] .. game_off_dev[g + 1] - 1 (device int32 [n_games + 1], increasing, game_off[0] = 0, game_off[n_games] =
+ * n_positions; every game has at least its root).  moves_dev (device int32 [n_positions]): moves_dev[k] = the move played from
+ * position k (from | to << 6 | promo << 12), ignored for a game's last position.  Positions need resolved ep_key fields or -2.
+ * Per position k: san_dev[k] (8 bytes) = the SAN of the move played from it, without the check suffix, NUL-padded (at most 6
+ * characters; all zero for a game's last position and a bad ply); state_dev[k] = bit 0 the side to move is in check, bit 1 it has
+ * no legal move, bits 4-7 the status of the move played from it (BO_PGN_OK, BO_PGN_ILLEGAL: not a legal move, BO_PGN_MISMATCH:
+ * legal, but the position after it differs from position k + 1 in its key or counters).  The suffix of move i is '#' if state of
+ * position i + 1 has bits 0 and 1, '+' if bit 0 only.  bad_dev (device int32 [2 * n_games]): per game the first bad ply (-1 none)
+ * and its status.  Asynchronous on `stream`. */
+int bo_san_render(int32_t n_games, int32_t n_positions, const int32_t *game_off_dev, const void *positions_dev, const int32_t *moves_dev,
+                  void *san_dev, uint8_t *state_dev, int32_t *bad_dev, void *stream);
+/* FEN of a position, as python-chess Board.fen() writes it: the en-passant field is ep_key (an ep square only when an ep capture
+ * is legal; -2 is refused: resolve it first).  Writes a NUL-terminated string of at most cap bytes.  Host only. */
+int bo_position_fen(const bo_position *p, char *out, int32_t cap);
+/* Movetext of one game from bo_san_render's output (host copies): san [n_plies * 8], state [n_plies + 1], the root's side to move
+ * (1 white) and fullmove number, comments [n_plies] (bit 0: "{book}" after the move; NULL: none) and the result token.  Move numbers
+ * "N." before white's moves and "N..." before a black move that opens the game or follows a comment; lines of at most 79
+ * characters, no token split; ends with the result token and '\n'.  *len_out = the text's length; BO_E_ARG if it does not fit
+ * in cap bytes (nothing is written then) or a ply has no SAN.  Host only. */
+int bo_pgn_movetext(int32_t n_plies, const void *san, const uint8_t *state, int32_t root_turn, int32_t root_fullmove, const uint8_t *comments,
+                    const char *result, char *out, int64_t cap, int64_t *len_out);
 
 #ifdef __cplusplus
 }
