@@ -94,6 +94,12 @@ struct bo_engine {
     std::vector<double> turn_pw_host;
     double turn_pw_tfinal = 0.0;  // the T_final the table was built for (0: none yet)
     int *d_turn_action = nullptr, *d_turn_state = nullptr, *d_turn_cres = nullptr;
+    float *d_turn_rv = nullptr;                          // info row 15: v_i (the searched roots' q_value)
+    int *d_turn_resigned = nullptr, *d_turn_rnext = nullptr;  // info rows 16, 17 (row 17 stays on the device)
+    std::vector<int> resign_en;                          // bo_selfplay_resign: per slot, resignation enabled (flag bit 3)
+    float resign_t = 0.0f;
+    int resign_k = 1;
+    float *d_root_value = nullptr;                       // bo_search_root_value's staging [G]
     std::vector<int> turn_want;
     bool turn_outstanding = false, ev_turn_made = false;
     rt_event ev_turn{};
@@ -255,6 +261,7 @@ extern "C" int bo_engine_create(const bo_config *cfg, int device, bo_engine **ou
     c.root_m = root_m;
     c.profile = 0;
     { const char *v = getenv("BETAONE_BURST_TWO_PATHS"); c.burst_two = (v && v[0] == '0') ? 0 : 1; }
+    c.root_q = 0;
     const size_t G = (size_t)c.G, N = G * (size_t)c.NCAP;
     Eng &d = e->d;
     int rc = 0;
@@ -264,7 +271,7 @@ extern "C" int bo_engine_create(const bo_config *cfg, int device, bo_engine **ou
                      &d.trk_n, &d.n_hist, &d.ctx_mode, &d.root_nch, &d.stat_evals,
                      &d.stat_flushes, &d.stat_term_sims, &d.stat_levels, &d.stat_children_scanned, &e->d_go, &e->d_action};
     for (int **p : iscal) rc |= e->alloc(p, G);
-    const size_t res_ints = G * (4 + 2 * (size_t)BO_RES_CAP) + 4, info_ints = G * 15;  // (+ 4: the watched status word, bo_engine_watch; info rows 5..14: bo_selfplay_autoturn's outputs)
+    const size_t res_ints = G * (4 + 2 * (size_t)BO_RES_CAP) + 4, info_ints = G * 18;  // (+ 4: the watched status word, bo_engine_watch; info rows 5..17: bo_selfplay_autoturn's outputs)
     rc |= e->alloc(&e->d_res_blk, res_ints); rc |= e->alloc(&e->d_info_blk, info_ints);
     if (!rc) {
         d.res_n = e->d_res_blk; d.res_best_idx = e->d_res_blk + G; d.res_best_mv = e->d_res_blk + 2 * G; d.res_total = e->d_res_blk + 3 * G;
@@ -273,6 +280,8 @@ extern "C" int bo_engine_create(const bo_config *cfg, int device, bo_engine **ou
         d.phase = e->d_info_blk; d.req_node = e->d_info_blk + G; d.root_nlegal = e->d_info_blk + 2 * G; d.root_term = e->d_info_blk + 3 * G;
         d.ply = e->d_info_blk + 4 * G;
         e->d_turn_action = e->d_info_blk + 5 * G; e->d_turn_state = e->d_info_blk + 6 * G; e->d_turn_cres = e->d_info_blk + 7 * G;
+        e->d_turn_rv = reinterpret_cast<float *>(e->d_info_blk + 15 * G); e->d_turn_resigned = e->d_info_blk + 16 * G;
+        e->d_turn_rnext = e->d_info_blk + 17 * G;
         rt_memset(e->d_res_blk, 0, res_ints * 4, nullptr); rt_memset(e->d_info_blk, 0, info_ints * 4, nullptr);
     }
     rc |= rt_host_alloc((void **)&e->h_res, res_ints * 4); rc |= rt_host_alloc((void **)&e->h_info, info_ints * 4);
@@ -293,6 +302,8 @@ extern "C" int bo_engine_create(const bo_config *cfg, int device, bo_engine **ou
     rc |= e->alloc(&d.root_child_rank, G * 2 * BO_CH_CAP); rc |= e->alloc(&d.noise, G * BO_MAX_MOVES);
     rc |= e->alloc(&d.played, G * c.PLY_CAP);
     rc |= e->alloc(&d.prof, G * BO_PROF_SLOTS);
+    rc |= e->alloc(&d.resign_cnt, 2 * G); rc |= e->alloc(&e->d_root_value, G);
+    if (!rc) rt_memset(d.resign_cnt, 0, 2 * G * 4, nullptr);
     d.played_now = nullptr;
     if (fast) {
         FastW &f = e->f;
@@ -1027,6 +1038,7 @@ extern "C" int bo_selfplay_autoturn(bo_engine *e, const int32_t *active, const i
             const double temp = move_number[g] < threshold ? t_initial : t_final;
             int fl = (active[g] ? 1 : 0) | (want_next[g] ? 4 : 0);
             if (active[g] && !(fabs(temp - 1.0) < 1e-6)) fl |= 2;
+            if (active[g] && (int)e->resign_en.size() == G && e->resign_en[g]) fl |= 8;
             e->h_turn_flags[g] = fl;
             if (active[g]) e->h_turn_u[g] = hr_double(&e->rng[g]);  // RandomState.choice's random_sample() (self_play.py:73)
         }
@@ -1035,12 +1047,14 @@ extern "C" int bo_selfplay_autoturn(bo_engine *e, const int32_t *active, const i
     TurnArgs a;
     a.u = e->h_turn_u; a.flags = e->h_turn_flags; a.pw = e->d_turn_pw;
     a.action = e->d_turn_action; a.state = e->d_turn_state; a.cres = e->d_turn_cres;
+    a.root_value = e->d_turn_rv; a.resigned = e->d_turn_resigned; a.resign_next = e->d_turn_rnext;
+    a.resign_t = e->resign_t; a.resign_k = e->resign_k;
     e->prefetch_valid = false;
     e->nl_valid = false;
     RT(RT_LAUNCH(bo_k_turn_sample, G, stream, e->d, a));
     RT(RT_LAUNCH(bo_k_turn_play, G, stream, e->d, a, nn_in_dev));
     const size_t Gs = (size_t)G, watch_off = Gs * (4 + 2 * (size_t)BO_RES_CAP);
-    int rc = ship(e, e->h_info + 2 * Gs, (const int *)e->d_info_blk + 2 * Gs, 13 * Gs, e->h_res + watch_off, (const int *)e->d_res_blk + watch_off, 4, stream);
+    int rc = ship(e, e->h_info + 2 * Gs, (const int *)e->d_info_blk + 2 * Gs, 15 * Gs, e->h_res + watch_off, (const int *)e->d_res_blk + watch_off, 4, stream);
     if (rc) return rc;
     if (!e->ev_turn_made) { RT(rt_event_create(&e->ev_turn)); e->ev_turn_made = true; }
     RT(rt_event_record(e->ev_turn, stream));
@@ -1064,8 +1078,9 @@ extern "C" int bo_selfplay_autoturn_ready(bo_engine *e, int32_t *ready_out) {
     return BO_OK;
 }
 
-extern "C" int bo_selfplay_autoturn_collect(bo_engine *e, int32_t *res_n, int32_t *res_idx, float *res_val, int32_t *best_idx, int32_t *action_out,
-                                            int32_t *n_legal_out, int32_t *terminal_out, int32_t *go_out, int32_t *completed) {
+extern "C" int bo_selfplay_autoturn_collect_ex(bo_engine *e, int32_t *res_n, int32_t *res_idx, float *res_val, int32_t *best_idx,
+                                               int32_t *action_out, int32_t *n_legal_out, int32_t *terminal_out, int32_t *go_out,
+                                               float *root_value_out, int32_t *resigned_out, int32_t *completed) {
     if (!e || !res_n || !res_idx || !res_val || !action_out || !completed) return fail(BO_E_ARG, "null argument");
     if (!e->turn_outstanding) return fail(BO_E_STATE, "no bo_selfplay_autoturn outstanding");
     RT(rt_event_sync(e->ev_turn));
@@ -1073,7 +1088,7 @@ extern "C" int bo_selfplay_autoturn_collect(bo_engine *e, int32_t *res_n, int32_
     *completed = 0;
     const int G = e->d.c.G;
     const size_t Gs = (size_t)G;
-    const int *act = e->h_info + 5 * Gs, *st = e->h_info + 6 * Gs, *cres = e->h_info + 7 * Gs;
+    const int *act = e->h_info + 5 * Gs, *st = e->h_info + 6 * Gs, *cres = e->h_info + 7 * Gs, *rsg = e->h_info + 16 * Gs;
     e->watch_seen |= e->h_res[Gs * (4 + 2 * (size_t)BO_RES_CAP)];
     bool running = false;
     for (int g = 0; g < G; g++) {
@@ -1094,16 +1109,56 @@ extern "C" int bo_selfplay_autoturn_collect(bo_engine *e, int32_t *res_n, int32_
         } else res_n[g] = 0;
         e->h_nl[g] = e->h_info[2 * Gs + g];
         e->h_term[g] = e->h_info[3 * Gs + g];
-        const int go = e->turn_want[g] && e->h_term[g] == 0;
+        const int go = e->turn_want[g] && e->h_term[g] == 0 && !rsg[g];  // (a game that resigned begins no search)
         e->h_go[g] = go;
         if (e->turn_want[g]) e->noise_pending[g] = 0;
         if (go && alpha > 0) e->noise_pending[g] = 1;
         if (n_legal_out) n_legal_out[g] = e->h_nl[g];
         if (terminal_out) terminal_out[g] = e->h_term[g];
         if (go_out) go_out[g] = go;
+        if (root_value_out) memcpy(&root_value_out[g], &e->h_info[15 * Gs + g], 4);
+        if (resigned_out) resigned_out[g] = rsg[g];
     }
     e->nl_valid = true;
     *completed = 1;
+    return BO_OK;
+}
+
+extern "C" int bo_selfplay_autoturn_collect(bo_engine *e, int32_t *res_n, int32_t *res_idx, float *res_val, int32_t *best_idx, int32_t *action_out,
+                                            int32_t *n_legal_out, int32_t *terminal_out, int32_t *go_out, int32_t *completed) {
+    return bo_selfplay_autoturn_collect_ex(e, res_n, res_idx, res_val, best_idx, action_out, n_legal_out, terminal_out, go_out, nullptr, nullptr,
+                                           completed);
+}
+
+// The root's q_value kept exact in every backup (ABI 7): v_i of bo_search_root_value / bo_selfplay_autoturn_collect_ex
+extern "C" int bo_engine_root_values(bo_engine *e, int32_t on) {
+    if (!e) return fail(BO_E_ARG, "null engine");
+    e->d.c.root_q = on ? 1 : 0;
+    return BO_OK;
+}
+
+// Resignation in the device turn (ABI 7): enable[g] != 0 sets flag bit 3 for slot g's next turns (NULL: off for every slot).
+extern "C" int bo_selfplay_resign(bo_engine *e, const int32_t *enable, float threshold, int32_t plies) {
+    if (!e) return fail(BO_E_ARG, "null engine");
+    if (plies < 1) return fail(BO_E_ARG, "bo_selfplay_resign: plies must be >= 1");
+    if (enable && !(threshold == threshold)) return fail(BO_E_ARG, "bo_selfplay_resign: the threshold is NaN");
+    if (enable && e->fast) return fail(BO_E_CONFIG, "bo_selfplay_resign: reference-semantics engines only");
+    if (enable && !e->d.c.root_q) return fail(BO_E_STATE, "bo_selfplay_resign: call bo_engine_root_values(e, 1) first");
+    const int G = e->d.c.G;
+    if (enable) e->resign_en.assign(enable, enable + G);
+    else e->resign_en.clear();
+    e->resign_t = threshold;
+    e->resign_k = plies;
+    return BO_OK;
+}
+
+// v_i of the host-made turn: the root's q_value of every slot (meaningful for the slots whose search has finished).  Synchronises.
+extern "C" int bo_search_root_value(bo_engine *e, float *out, void *stream) {
+    if (!e || !out) return fail(BO_E_ARG, "null argument");
+    const int G = e->d.c.G;
+    RT(RT_LAUNCH(bo_k_root_value, (G + 63) / 64, stream, e->d, e->d_root_value));
+    RT(rt_d2h(out, e->d_root_value, (size_t)G * 4, stream));
+    RT(rt_sync(stream));
     return BO_OK;
 }
 
@@ -1465,6 +1520,23 @@ extern "C" int bo_pgn_movetext(int32_t n_plies, const void *san, const uint8_t *
         return fail(BO_E_ARG, "bo_pgn_movetext: a ply has no SAN");
     *len_out = (int64_t)t.size();
     if ((int64_t)t.size() > cap) return fail(BO_E_ARG, "bo_pgn_movetext: buffer too small");
+    memcpy(out, t.data(), t.size());
+    return BO_OK;
+}
+
+extern "C" int bo_pgn_movetext_text(int32_t n_plies, const void *san, const uint8_t *state, int32_t root_turn, int32_t root_fullmove,
+                                    const char *text, const int32_t *text_off, const char *final_comment, const char *result, char *out,
+                                    int64_t cap, int64_t *len_out) {
+    if (n_plies < 0 || (n_plies && !san) || !state || !result || !out || !len_out || (text && !text_off))
+        return fail(BO_E_ARG, "bo_pgn_movetext_text: bad arguments");
+    if (text)
+        for (int i = 0; i < n_plies; i++)
+            if (text_off[i] < 0 || text_off[i + 1] < text_off[i]) return fail(BO_E_ARG, "bo_pgn_movetext_text: text_off is not increasing");
+    std::string t;
+    if (!pgn_movetext(n_plies, (const uint8_t *)san, state, root_turn != 0, root_fullmove, nullptr, result, &t, text, text_off, final_comment))
+        return fail(BO_E_ARG, "bo_pgn_movetext_text: a ply has no SAN");
+    *len_out = (int64_t)t.size();
+    if ((int64_t)t.size() > cap) return fail(BO_E_ARG, "bo_pgn_movetext_text: buffer too small");
     memcpy(out, t.data(), t.size());
     return BO_OK;
 }

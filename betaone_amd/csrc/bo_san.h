@@ -187,7 +187,8 @@ BO_KERNEL void bo_k_san_status(const int *game_off, int n_pos, const uint8_t *st
 // the root's side to move and fullmove number, per-ply comment flags (bit 0: "{book}" after the move; may be null) and the result
 // token.  false when a ply has no SAN (a bad ply: render it first).
 static bool pgn_movetext(int n, const uint8_t *san, const uint8_t *state, bool white_first, int fullmove, const uint8_t *comments,
-                         const char *result, std::string *out) {
+                         const char *result, std::string *out, const char *text = nullptr, const int32_t *text_off = nullptr,
+                         const char *final_comment = nullptr) {
     out->clear();
     std::string line;
     auto emit = [&](const char *tok, size_t len) {
@@ -216,6 +217,15 @@ static bool pgn_movetext(int n, const uint8_t *san, const uint8_t *state, bool w
         emit(buf, (size_t)len);
         after_comment = comments && (comments[i] & 1);
         if (after_comment) emit("{book}", 6);
+        if (text && text_off[i + 1] > text_off[i]) {  // (bo_pgn_movetext_text: the ply's comment text)
+            std::string c = "{" + std::string(text + text_off[i], (size_t)(text_off[i + 1] - text_off[i])) + "}";
+            emit(c.data(), c.size());
+            after_comment = true;
+        }
+    }
+    if (final_comment && final_comment[0]) {
+        std::string c = "{" + std::string(final_comment) + "}";
+        emit(c.data(), c.size());
     }
     emit(result, strlen(result));
     out->append(line);

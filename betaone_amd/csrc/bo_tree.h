@@ -52,6 +52,7 @@ struct EngCfg {
     int root_m;                  // children admitted by one root expand call: int(WIDEN*sqrt(1))
     int profile;                 // bo_debug_profile: accumulate per-phase shader cycles (s_memtime) per game
     int burst_two;               // terminal_burst keeps the previous burst's path in a second register set (0: off -- BETAONE_BURST_TWO_PATHS=0, for A/B tests)
+    int root_q;                  // terminal_burst also updates the root's q_value (bo_engine_root_values: v_i is wanted); 0: the root keeps its count only
 };
 
 struct Eng {
@@ -90,6 +91,7 @@ struct Eng {
     int *watch, *res_watch;           // bo_engine_watch: a device status word of the evaluate stage (NULL: none); the result kernels copy it behind
                                       // the result block, so the ply's one host round trip brings it along
     int *played_now;                  // [G] or NULL: bo_k_play notes the move it played (0: refused) -- read by the fast mode's re-rooting
+    int *resign_cnt;                  // [G][2] resignation: consecutive own searches below the threshold, per ply parity (committed by bo_k_turn_play)
     unsigned long long *prof;         // [G][BO_PROF_SLOTS] cycles: apply, select, first-visit (movegen+draw rules), terminal backups, encode, flush, total; steps,
                                       // loop iterations, first visits.  profile = N > 1 counts only game-steps longer than N cycles
 };
@@ -515,6 +517,8 @@ BO_DEV int terminal_burst(const Eng &e, int g, const int *path, int d, float v, 
     uint64_t last_bits = d > 0 ? (0xFFFFull << (16 * (d - 1))) : 0ull;
     bool last_l = last;
     int pv = pvl;  // parent-side visits of this lane's level on the CURRENT path; + 1 per simulation through it
+    const bool root_q = e.c.root_q != 0;
+    float rq = root_q ? e.q[no + path[0]] : 0.0f;  // the root's own q_value (uniform): MCTSNode.update of the root, the value the turn reports (v_i)
     for (;;) {
         pv += 1;
         // (levels <= c: the parent-side node is common to both paths and `pv` counts for both; deeper levels keep one count per path)
@@ -530,8 +534,12 @@ BO_DEV int terminal_burst(const Eng &e, int g, const int *path, int d, float v, 
         }
 #pragma unroll
         for (int k = 0; k <= BO_BURST_LEVELS; k++) nv[k] += k <= d ? 1 : 0;
-        // (the root's own q_value is not maintained here: nothing reads it -- select_child scores children only, the
-        //  reference keeps it as a Python float that no code path looks at)
+        // (select_child never reads the root's q_value: it is maintained only when v_i is wanted -- bo_engine_root_values)
+        if (root_q) {  // the root sees v at an even distance from the leaf, -v at an odd one
+            const float val = (d & 1) ? -v_cur : v_cur;
+            const float dd = val - rq;
+            rq = rq + (nv[0] <= S + 2 ? bo_div_count(dd, (float)nv[0], BO_RC(nv[0])) : bo_div_general(dd, (float)nv[0]));
+        }
         done++;
         if (done >= sims_left) break;
         // ---- re-evaluate the descent from the registers (select_child at every level of the path) ----
@@ -633,7 +641,7 @@ BO_DEV int terminal_burst(const Eng &e, int g, const int *path, int d, float v, 
     // ---- write the path(s) back ----
     if (have) { e.n_visits[no + my_fc + j] = cn; e.q[no + my_fc + j] = cq; }
     if (two && b_have) { e.n_visits[no + b_fc + j] = b_cn; e.q[no + b_fc + j] = b_cq; }
-    if (lane == 0) e.n_visits[no] = nv[0];
+    if (lane == 0) { e.n_visits[no] = nv[0]; if (root_q) e.q[no] = rq; }
     bo_sync();
     return done;
 }
@@ -1150,6 +1158,7 @@ BO_KERNEL void bo_k_setup(Eng e, SetupArgs a) {
             e.trk_n[g] = ply + 1;
         }
         e.stat_evals[g] = e.stat_flushes[g] = e.stat_term_sims[g] = e.stat_levels[g] = e.stat_children_scanned[g] = 0;
+        e.resign_cnt[2 * g] = e.resign_cnt[2 * g + 1] = 0;
     }
     bo_sync();
     root_prepare(e, g, sh);
@@ -1297,12 +1306,17 @@ BO_KERNEL void bo_k_play(Eng e, const int *action) {
 struct TurnArgs {
     const double *u;      // [G] host memory (pinned, device-mapped): this game's choice() uniform
     const int *flags;     // [G] host memory: bit 0 the game searched this ply (sample + play), bit 1 its temperature is not 1 (fullmove >= threshold,
-                          //     self_play.py:66): p ** (1 / T) from `pw`, bit 2 a next search is wanted
+                          //     self_play.py:66): p ** (1 / T) from `pw`, bit 2 a next search is wanted, bit 3 resignation is enabled
     const double *pw;     // [S + 1] device: pow((double)f32(c / S), 1 / T_final)
     int *action;          // [G] out: the sampled action index, -1 = the game did not search
     int *state;           // [G] out: 0 ok, 1 the game's search is still running, 2 a pi this sampler does not cover (the host raises), 3 the evaluate
                           //     stage's watched fault word is set (bo_engine_watch: no move is played from an invalid evaluation; the host raises)
     int *cres;            // [G][8] out: n, best action index, best move, total visits, index 0, index 1, value 0 bits, value 1 bits (pi order of bo_k_result)
+    float *root_value;    // [G] out: v_i = the root's q_value after the search (side to move at the root), 0 where the game did not search
+    int *resigned;        // [G] out: 1 = the game resigns instead of playing (flag bit 3; action -1, state 0)
+    int *resign_next;     // [G] the counter bo_k_turn_play commits for this ply (-1: none)
+    float resign_t;       // resignation threshold t: a search with v_i < t counts
+    int resign_k;         // K: resign at the K-th consecutive own search that counts
 };
 
 // hr_select_action on (index, visit count) pairs; *ok = false where hr_select_action returns -1 (or the table does not apply)
@@ -1340,7 +1354,8 @@ BO_KERNEL void bo_k_turn_sample(Eng e, TurnArgs a) {
     const int g = bo_block(), lane = bo_lane();
     result_body(e, g);
     const int fl = a.flags[g], ph = e.phase[g];
-    int st = 0, act = -1, n = 0, ia = -1, ib = -1, ca = 0, cb = 0, total = 0;
+    int st = 0, act = -1, n = 0, ia = -1, ib = -1, ca = 0, cb = 0, total = 0, rsg = 0, rnext = -1;
+    float rv = 0.0f;
     if (e.watch && (e.watch[0] != 0 || (e.watch_n > 1 && e.watch[1] != 0))) st = 3;
     else if (ph == PH_RUN) st = 1;
     else if ((fl & 1) && ph == PH_DONE) {
@@ -1356,8 +1371,15 @@ BO_KERNEL void bo_k_turn_sample(Eng e, TurnArgs a) {
         bool ok;
         act = turn_sample(n, ia, ca, ib, cb, total, e.c.S, (fl & 2) != 0, a.pw, a.u[g], &ok);
         if (!ok) { st = 2; act = -1; }
+        rv = e.q[no];
+        if (fl & 8) {  // decided from the COMMITTED counter of this side (ply parity): a redo of this turn decides the same
+            const int cnt = e.resign_cnt[2 * g + (e.ply[g] & 1)];
+            rnext = rv < a.resign_t ? cnt + 1 : 0;
+            if (st == 0 && rnext >= a.resign_k) { rsg = 1; act = -1; }
+        }
     }
     if (lane == 0) {
+        a.root_value[g] = rv; a.resigned[g] = rsg; a.resign_next[g] = rnext;
         a.action[g] = act; a.state[g] = st;
         int *c = a.cres + (size_t)g * 8;
         c[0] = n; c[1] = e.res_best_idx[g]; c[2] = e.res_best_mv[g]; c[3] = total; c[4] = ia; c[5] = ib;
@@ -1374,11 +1396,19 @@ BO_KERNEL void bo_k_turn_play(Eng e, TurnArgs a, float *nn_in) {
     bool bad = false;
     for (int j0 = 0; j0 < e.c.G; j0 += 64) bad = bad || bo_ballot(j0 + lane < e.c.G && a.state[j0 + lane] != 0) != 0;
     if (bad) return;
+    if (lane == 0 && a.resign_next[g] >= 0) e.resign_cnt[2 * g + (e.ply[g] & 1)] = a.resign_next[g];  // (ply read before play_body moves it)
+    if (a.resigned[g]) return;  // no move, and no next search even if one was wanted
     int t = play_body(e, g, a.action[g], sh);
     if (t < 0) t = e.root_term[g];  // (the root did not change in this launch)
     if (!(a.flags[g] & 4) || t != 0) return;
     encode_static(e, g, nn_in + (size_t)g * BO_ROW);
     if (lane == 0) e.phase[g] = PH_RUN;
+}
+
+// The root's q_value of every game (bo_search_root_value: the host-made turn's v_i)
+BO_KERNEL void bo_k_root_value(Eng e, float *out) {
+    const int g = bo_block() * 64 + bo_lane();
+    if (g < e.c.G) out[g] = e.q[NOFF(e, g)];
 }
 
 // Final training encodings of a finished game (self_play.py:200-208): record i uses

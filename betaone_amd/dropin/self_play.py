@@ -50,7 +50,7 @@ def _cohorts(n_slots: int, rng_mode: str) -> int:
     return max(k, 1)
 
 
-def _rollout(model, n_slots: int, rng_mode: str = "python"):
+def _rollout(model, n_slots: int, rng_mode: str = "python", **extra):
     dev = E.runtime_device(config.DEVICE)
     k = _cohorts(n_slots, rng_mode)
     model = _inference_copy(model, n_slots // k)
@@ -61,7 +61,7 @@ def _rollout(model, n_slots: int, rng_mode: str = "python"):
               temperature=(config.TEMPERATURE_THRESHOLD, config.TEMPERATURE_INITIAL, config.TEMPERATURE_FINAL),
               device=dev, autocast=config.AUTOCAST, rng_mode=rng_mode,
               policy_kind="probs" if config.POLICY_SOFTMAX == "torch" else "logits",
-              fast=config.SEARCH_MODE == "fast", leaves_per_step=config.FAST_LEAVES)
+              fast=config.SEARCH_MODE == "fast", leaves_per_step=config.FAST_LEAVES, **extra)
     return CohortRollout(model, n_slots, cohorts=k, **kw) if k > 1 else Rollout(model, n_slots, **kw)
 
 
@@ -77,7 +77,7 @@ def _records(ro: Rollout, fin: FinishedGame) -> List[SelfPlayData]:
 
 def run_self_play_games(model, game_ids: Sequence[int], seeds: Optional[Sequence[int]] = None,
                         n_slots: Optional[int] = None, start_fens: Optional[Sequence[Optional[str]]] = None,
-                        on_game=None, dense: bool = True, reload_model=None, on_records=None
+                        on_game=None, dense: bool = True, reload_model=None, on_records=None, rollout_kw: Optional[dict] = None
                         ) -> Dict[int, Optional[List[SelfPlayData]]]:
     """Play len(game_ids) games, n_slots at a time, on one GPU.  Game i draws its Dirichlet noise and its
     moves from numpy.random.RandomState(seeds[i]) -- the stream the reference consumes after
@@ -88,11 +88,11 @@ def run_self_play_games(model, game_ids: Sequence[int], seeds: Optional[Sequence
     as they exist (selfplay_main pickles them there and keeps an empty list, so an iteration's tuples never pile up in memory).
     reload_model() -> None | a new PolicyValueNet: polled once per ply; a returned model replaces the evaluate stage for every
     evaluation from the next ply on (main.py:147-148 hands weights to its workers through best_model.pth: betaone_amd.selfplay_main
-    watches that file)."""
+    watches that file).  rollout_kw: further Rollout arguments (resign_threshold, resign_plies, resign_check_fraction, record_values)."""
     ids = list(game_ids)
     seeds = list(seeds) if seeds is not None else ids
     n_slots = min(n_slots or len(ids), len(ids))
-    ro = _rollout(model, n_slots, rng_mode="native")  # RandomState(seed)-compatible streams kept inside the engine
+    ro = _rollout(model, n_slots, rng_mode="native", **(rollout_kw or {}))  # RandomState(seed)-compatible streams kept inside the engine
     results: Dict[int, Optional[List[SelfPlayData]]] = {}
     queue = list(range(len(ids)))
 

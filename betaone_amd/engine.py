@@ -98,6 +98,12 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_selfplay_autoturn": (C.c_int, [C.c_void_p, _I32P, _I32P, C.c_int32, C.c_double, C.c_double, _I32P, C.c_void_p, C.c_int32, C.c_void_p]),
     "bo_selfplay_autoturn_ready": (C.c_int, [C.c_void_p, _I32P]),
     "bo_selfplay_autoturn_collect": (C.c_int, [C.c_void_p, _I32P, _I32P, _F32P, _I32P, _I32P, _I32P, _I32P, _I32P, _I32P]),
+    "bo_selfplay_autoturn_collect_ex": (C.c_int, [C.c_void_p, _I32P, _I32P, _F32P, _I32P, _I32P, _I32P, _I32P, _I32P, _F32P, _I32P, _I32P]),
+    "bo_engine_root_values": (C.c_int, [C.c_void_p, C.c_int32]),
+    "bo_selfplay_resign": (C.c_int, [C.c_void_p, _I32P, C.c_float, C.c_int32]),
+    "bo_search_root_value": (C.c_int, [C.c_void_p, _F32P, C.c_void_p]),
+    "bo_pgn_movetext_text": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, _I32P, C.c_char_p, C.c_char_p,
+                                       C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "bo_search_result_prefetch": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bo_selfplay_begun": (C.c_int, [C.c_void_p, _I32P, _I32P, _I32P]),
     "bo_selfplay_begin": (C.c_int, [C.c_void_p, _I32P, C.c_void_p, _I32P, _I32P, _I32P, C.c_void_p]),
@@ -187,7 +193,7 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 6   # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 7   # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
 
 
@@ -492,14 +498,33 @@ class Engine:
 
     def autoturn_collect(self, out):
         """(out, (n_legal, terminal, go)) of the device's turn, or (None, None) if a search was still running when it came up (nothing
-        was played: step once more and enqueue selfplay_autoturn(redo=True))."""
+        was played: step once more and enqueue selfplay_autoturn(redo=True)).  out["root_value"] (float32 [G]) and out["resigned"]
+        (int32 [G]), where present, receive v_i and the games that resigned (bo_selfplay_autoturn_collect_ex)."""
         nl, tm, go = (np.zeros(self.G, dtype=np.int32) for _ in range(3))
         done = C.c_int32(0)
-        self._check(self.lib.bo_selfplay_autoturn_collect(self.h, _p(out["n"]), _p(out["idx"]), _p(out["val"], _F32P), _p(out["best_idx"]),
-                                                          _p(out["action"]), _p(nl), _p(tm), _p(go), C.byref(done)))
+        rv, rs = out.get("root_value"), out.get("resigned")
+        self._check(self.lib.bo_selfplay_autoturn_collect_ex(self.h, _p(out["n"]), _p(out["idx"]), _p(out["val"], _F32P), _p(out["best_idx"]),
+                                                             _p(out["action"]), _p(nl), _p(tm), _p(go),
+                                                             _p(rv, _F32P) if rv is not None else None, _p(rs) if rs is not None else None,
+                                                             C.byref(done)))
         if done.value < 0:
             return None, None
         return out, (nl, tm, go)
+
+    def root_values(self, on: bool = True) -> None:
+        """Keep the root's q_value exact in every backup (bo_engine_root_values): needed for v_i; before any step is captured."""
+        self._check(self.lib.bo_engine_root_values(self.h, 1 if on else 0))
+
+    def selfplay_resign(self, enable, threshold: float, plies: int = 1) -> None:
+        """Resignation in the device turn (bo_selfplay_resign): enable [G] per slot, or None for off."""
+        e = _i32(enable) if enable is not None else None
+        self._check(self.lib.bo_selfplay_resign(self.h, _p(e) if e is not None else None, float(threshold), int(plies)))
+
+    def search_root_value(self, stream: int = 0) -> np.ndarray:
+        """v = the root's q_value of every slot (float32 [G]; bo_search_root_value).  Synchronises."""
+        out = np.zeros(self.G, dtype=np.float32)
+        self._check(self.lib.bo_search_root_value(self.h, _p(out, _F32P), stream))
+        return out
 
     def selfplay_begin(self, want, nn_in_ptr: int, stream: int = 0):
         w = _i32(want)

@@ -10,7 +10,12 @@ one, is an error).  The movetext is assembled by the library's host code (bo_pgn
     python -m betaone_amd.pgn_write DATA_DIR/iter_7/ -o iter7.pgn --date 2026.10.15
 
 Results: terminal 1 (the side to move in the final position is mated; the device must confirm it) gives 1-0 / 0-1, terminal 2 gives
-1/2-1/2, both with Termination "normal"; terminal 0 (the move limit) gives "*" and "unterminated".
+1/2-1/2, both with Termination "normal"; terminal 0 (the move limit) gives "*" and "unterminated"; terminal 3 (the side to move in the
+final position resigned) gives the winner's result, Termination "normal" and a last comment "{White resigns}" / "{Black resigns}".
+
+Eval comments: a game with root values (FinishedGame.root_values, BOG2 records) gets after each move m_i the comment
+"{<e>/<S> 0.00s}", e = 2 ln((1 + v_i) / (1 - v_i)) pawns (the inverse of eval_to_value, train.py), "%+.2f" clamped to +-99.99, S the
+simulations per search -- the pattern pretrain's PGN reader parses (DESIGN "Eval comments").
 """
 from __future__ import annotations
 
@@ -41,6 +46,22 @@ def _fields(g):
     if isinstance(g, dict):
         return int(g["game_id"]), g["positions"], g["moves"], int(g["terminal"])
     return int(g.game_id), g.positions, g.moves, int(g.terminal)
+
+
+def _root_values(g):
+    return g.get("root_values") if isinstance(g, dict) else getattr(g, "root_values", None)
+
+
+def eval_text(v, sims: int) -> str:
+    """The eval comment of a root value v (float32, side to move): e = 2 ln((1 + v) / (1 - v)) pawns, %+.2f, clamped to +-99.99."""
+    v = float(np.float32(v))
+    if v >= 1.0:
+        e = 99.99
+    elif v <= -1.0:
+        e = -99.99
+    else:
+        e = min(99.99, max(-99.99, 2.0 * np.log((1.0 + v) / (1.0 - v))))
+    return f"{e:+.2f}/{int(sims)} 0.00s"
 
 
 def _position_bytes(positions, n: int) -> bytes:
@@ -138,11 +159,27 @@ def position_fen(position, lib=None) -> str:
     return buf.value.decode()
 
 
-def movetext(r: Rendered, root_turn: int, root_fullmove: int, result: str, book_plies: int = 0, lib=None) -> str:
+def movetext(r: Rendered, root_turn: int, root_fullmove: int, result: str, book_plies: int = 0, lib=None, comments=None,
+             final_comment: Optional[str] = None) -> str:
+    """comments: a text per ply (written as "{text}" after the move; "" none) -- bo_pgn_movetext_text; else bo_pgn_movetext."""
     lib = lib or E.load_hip_library()
     n = len(r.san)
     san = np.ascontiguousarray(r.san, dtype=np.uint8)
     state = np.ascontiguousarray(r.state, dtype=np.uint8)
+    if comments is not None or final_comment:
+        texts = [(comments[i] if comments is not None and i < len(comments) else "").encode() for i in range(n)]
+        off = np.zeros(n + 1, np.int32)
+        np.cumsum([len(t) for t in texts], out=off[1:])
+        blob = b"".join(texts)
+        cap = 24 * n + int(off[-1]) + 3 * n + len(final_comment or "") + 64
+        buf = C.create_string_buffer(cap)
+        ln = C.c_int64()
+        rc = lib.bo_pgn_movetext_text(n, san.ctypes.data, state.ctypes.data, int(root_turn), int(root_fullmove), blob,
+                                      off.ctypes.data_as(C.POINTER(C.c_int32)), (final_comment or "").encode(), result.encode(), buf, cap,
+                                      C.byref(ln))
+        if rc != 0:
+            raise E.EngineError(f"bo_pgn_movetext_text: {lib.bo_last_error().decode()}")
+        return buf.raw[:ln.value].decode()
     com = None
     if book_plies:
         com = np.zeros(max(n, 1), np.uint8)
@@ -169,18 +206,30 @@ def result_of(gid: int, positions, terminal: int, r: Rendered):
         return ("0-1" if positions[len(r.san)].turn == 1 else "1-0"), "normal"
     if terminal == 2:
         return "1/2-1/2", "normal"
+    if terminal == 3:  # the side to move in the final position resigned
+        return ("0-1" if positions[len(r.san)].turn == 1 else "1-0"), "normal"
     return "*", "unterminated"
+
+
+def _default_sims() -> int:
+    from . import dropin
+
+    dropin.install()
+    import config
+
+    return int(config.NUM_SIMULATIONS)
 
 
 def today() -> str:
     return time.strftime("%Y.%m.%d", time.gmtime())
 
 
-def write_pgn(fh, games: Sequence, tags=None, device="cuda:0", lib=None, book_plies: Optional[Sequence[int]] = None) -> int:
+def write_pgn(fh, games: Sequence, tags=None, device="cuda:0", lib=None, book_plies: Optional[Sequence[int]] = None,
+              sims: Optional[int] = None) -> int:
     """Writes `games` to the text file fh; returns the characters written.  tags: one dict for every game, or one dict per game;
     the Seven Tag Roster comes first (missing ones are "?", Date defaults to today's UTC date), then SetUp / FEN when the root is not
     the standard start, Termination, PlyCount, and any other tag given.  book_plies[i]: the first moves of game i that get a
-    "{book}" comment."""
+    "{book}" comment.  sims: S of the eval comments of games with root values (default config.NUM_SIMULATIONS of the drop-in)."""
     lib = lib or E.load_hip_library()
     games = list(games)
     per_game = isinstance(tags, (list, tuple))
@@ -204,7 +253,19 @@ def write_pgn(fh, games: Sequence, tags=None, device="cuda:0", lib=None, book_pl
         head["Termination"], head["PlyCount"] = termination, len(moves)
         head.update(t)
         text = "".join(f'[{k} "{escape(v)}"]\n' for k, v in head.items()) + "\n"
-        text += movetext(r, root.turn, root.fullmove_number, result, book_plies[i] if book_plies else 0, lib) + "\n"
+        rv = _root_values(g)
+        if rv is not None or terminal == 3:
+            if sims is None:
+                sims = _default_sims()
+            com = [eval_text(v, sims) for v in rv[:len(moves)]] if rv is not None else None
+            if com is not None and book_plies and book_plies[i]:
+                com = ["book"] * min(book_plies[i], len(com)) + com[book_plies[i]:]
+            fin = None
+            if terminal == 3:
+                fin = ("White" if positions[len(moves)].turn == 1 else "Black") + " resigns"
+            text += movetext(r, root.turn, root.fullmove_number, result, 0, lib, comments=com, final_comment=fin) + "\n"
+        else:
+            text += movetext(r, root.turn, root.fullmove_number, result, book_plies[i] if book_plies else 0, lib) + "\n"
         fh.write(text)
         written += len(text)
     return written
@@ -222,7 +283,7 @@ def bog_paths(args: Sequence[str]) -> List[str]:
 
 
 def convert(paths: Sequence[str], fh, event="BetaOne self-play", player="BetaOne", date=None, device="cuda:0", lib=None,
-            batch_plies: int = MAX_BATCH_POSITIONS) -> Dict:
+            batch_plies: int = MAX_BATCH_POSITIONS, sims: Optional[int] = None) -> Dict:
     """Every game of the compact files `paths`, in (path, game_id) order, to fh; batches of about batch_plies plies."""
     from . import records
 
@@ -241,7 +302,7 @@ def convert(paths: Sequence[str], fh, event="BetaOne self-play", player="BetaOne
                 j += 1
             games = records.unpack_games(b"".join(buf[o:o + s] for _, _, o, s in idx[k:j]))
             tags = [{"Event": event, "Date": date, "Round": g["game_id"], "White": player, "Black": player} for g in games]
-            n_chars += write_pgn(fh, games, tags=tags, device=device, lib=lib)
+            n_chars += write_pgn(fh, games, tags=tags, device=device, lib=lib, sims=sims)
             n_games += len(games)
             n_plies += sum(int(g["n_plies"]) for g in games)
             k = j
@@ -259,10 +320,11 @@ def main(argv=None) -> int:
     ap.add_argument("--player", default="BetaOne", help="the White and Black tags")
     ap.add_argument("--date", default=None, help="the Date tag (default: today, UTC), e.g. 2026.10.15")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--sims", type=int, default=None, help="S of the eval comments of BOG2 games (default: config.NUM_SIMULATIONS)")
     args = ap.parse_args(argv)
     t0 = time.perf_counter()
     with open(args.out, "w", encoding="utf-8", newline="\n") as fh:
-        st = convert(args.paths, fh, event=args.event, player=args.player, date=args.date, device=args.device)
+        st = convert(args.paths, fh, event=args.event, player=args.player, date=args.date, device=args.device, sims=args.sims)
     st["seconds"] = time.perf_counter() - t0
     st["bytes"] = os.path.getsize(args.out)
     print(json.dumps(st))

@@ -15,6 +15,10 @@ Wire format of one game (little endian):
   bo_position positions[n_plies + 1]                      (88 B each)
   int32 moves[n_plies]
   int32 pi_ptr[n_plies + 1] | int32 pi_idx[n_pi_entries] | float32 pi_val[n_pi_entries]
+A game with root values (resignation on, or selfplay_main --record-values) is a 'BOG2' record: the same header with magic 'BOG2',
+then int32 flags (bit 0 resignation was on in the run, bit 1 a check game: resignation disabled for it), then the BOG1 body, then
+  float32 root_value[n_plies]                             (v_i: the root's q_value after the search at ply i, side to move)
+Every reader takes both; a game without root values is written as BOG1, byte for byte as before.
 """
 from __future__ import annotations
 
@@ -28,6 +32,8 @@ from . import engine as E
 from . import sampling
 
 MAGIC = 0x31474F42  # 'BOG1'
+MAGIC2 = 0x32474F42  # 'BOG2'
+FLAG_RESIGN, FLAG_CHECK = 1, 2
 POS_BYTES = C.sizeof(E.BoPosition)
 
 
@@ -44,12 +50,20 @@ def pack_game(fin) -> bytes:
             ptr[i + 1] = ptr[i] + len(ix)
         idx = np.concatenate([np.asarray(i, dtype=np.int32) for i, _ in fin.pis]) if n else np.zeros(0, np.int32)
         val = np.concatenate([np.asarray(v, dtype=np.float32) for _, v in fin.pis]) if n else np.zeros(0, np.float32)
-    head = np.array([MAGIC, fin.game_id, n, fin.terminal, 0, len(idx)], dtype=np.int32)
+    rv = getattr(fin, "root_values", None)
+    head = np.array([MAGIC if rv is None else MAGIC2, fin.game_id, n, fin.terminal, 0, len(idx)], dtype=np.int32)
     head[4:5].view(np.float32)[0] = fin.outcome
     raw = getattr(fin.positions, "raw", None)  # engine.PositionList: one ctypes array, no per-position objects
     pos = bytes(raw)[:(n + 1) * POS_BYTES] if raw is not None else b"".join(bytes(p) for p in fin.positions[:n + 1])
-    return b"".join([head.tobytes(), pos, np.asarray(fin.moves[:n], dtype=np.int32).tobytes(), ptr.tobytes(),
-                     idx.tobytes(), val.tobytes()])
+    parts = [head.tobytes(), pos, np.asarray(fin.moves[:n], dtype=np.int32).tobytes(), ptr.tobytes(), idx.tobytes(), val.tobytes()]
+    if rv is not None:
+        rv = np.asarray(rv, dtype=np.float32)
+        if len(rv) != n:
+            raise ValueError(f"pack_game: game {fin.game_id}: {len(rv)} root values for {n} plies")
+        flags = (FLAG_RESIGN if getattr(fin, "resign", False) else 0) | (FLAG_CHECK if getattr(fin, "resign_check", False) else 0)
+        parts.insert(1, np.array([flags], dtype=np.int32).tobytes())
+        parts.append(rv.tobytes())
+    return b"".join(parts)
 
 
 def unpack_games(buf: bytes) -> List[dict]:
@@ -57,19 +71,28 @@ def unpack_games(buf: bytes) -> List[dict]:
     mv = memoryview(buf)
     while off + 24 <= len(buf):
         head = np.frombuffer(mv[off:off + 24], dtype=np.int32)
-        if head[0] != MAGIC:
+        if head[0] != MAGIC and head[0] != MAGIC2:
             break
+        v2 = head[0] == MAGIC2
         gid, n, term, nent = int(head[1]), int(head[2]), int(head[3]), int(head[5])
         outcome = float(head[4:5].view(np.float32)[0])
         off += 24
+        flags = 0
+        if v2:
+            flags = int(np.frombuffer(mv[off:off + 4], dtype=np.int32)[0])
+            off += 4
         positions = (E.BoPosition * (n + 1)).from_buffer_copy(mv[off:off + POS_BYTES * (n + 1)])
         off += POS_BYTES * (n + 1)
         moves = np.frombuffer(mv[off:off + 4 * n], dtype=np.int32).copy(); off += 4 * n
         ptr = np.frombuffer(mv[off:off + 4 * (n + 1)], dtype=np.int32).copy(); off += 4 * (n + 1)
         idx = np.frombuffer(mv[off:off + 4 * nent], dtype=np.int32).copy(); off += 4 * nent
         val = np.frombuffer(mv[off:off + 4 * nent], dtype=np.float32).copy(); off += 4 * nent
+        rv = None
+        if v2:
+            rv = np.frombuffer(mv[off:off + 4 * n], dtype=np.float32).copy(); off += 4 * n
         out.append(dict(game_id=gid, n_plies=n, terminal=term, outcome=outcome, positions=positions, moves=moves,
-                        pis=[(idx[ptr[i]:ptr[i + 1]], val[ptr[i]:ptr[i + 1]]) for i in range(n)]))
+                        pis=[(idx[ptr[i]:ptr[i + 1]], val[ptr[i]:ptr[i + 1]]) for i in range(n)], root_values=rv,
+                        resign=bool(flags & FLAG_RESIGN), resign_check=bool(flags & FLAG_CHECK)))
     return out
 
 
@@ -156,10 +179,10 @@ def scan_games(buf) -> List[Tuple[int, int, int, int]]:
     out, off, mv = [], 0, memoryview(buf)
     while off + 24 <= len(mv):
         head = np.frombuffer(mv[off:off + 24], dtype=np.int32)
-        if head[0] != MAGIC:
+        if head[0] != MAGIC and head[0] != MAGIC2:
             break
         n, nent = int(head[2]), int(head[5])
-        size = 24 + POS_BYTES * (n + 1) + 4 * n + 4 * (n + 1) + 8 * nent
+        size = 24 + POS_BYTES * (n + 1) + 4 * n + 4 * (n + 1) + 8 * nent + ((4 + 4 * n) if head[0] == MAGIC2 else 0)
         if n < 0 or nent < 0 or off + size > len(mv):
             break
         out.append((int(head[1]), n, off, size))

@@ -47,6 +47,7 @@ class GameState:
     plies: int = 0                   # moves on the game's stack (incl. a prefix handed to start_games)
     first_ply: int = 0               # length of that prefix: the first ply searched here
     pis: List = field(default_factory=list)   # per searched ply: (action indices, float32 probabilities)
+    root_values: List = field(default_factory=list)  # per searched ply: v_i (rng_mode "python" with root values on)
 
     def fullmove_number(self) -> int:          # board.fullmove_number of the current root (self_play.py:104)
         return self.start_fullmove + (self.plies + (0 if self.start_white else 1)) // 2
@@ -88,11 +89,20 @@ class FinishedGame:
     positions: List[E.BoPosition]    # positions[i] = position before moves[i]; last = final position
     pis: List                        # sparse pi of ply first_ply + i
     outcome: float                   # utils.get_game_outcome of the final board, 0.0 if not over (self_play.py:190-197)
-    terminal: int                    # 0 stopped by move limit, 1 checkmate, 2 draw
+    terminal: int                    # 0 stopped by move limit, 1 checkmate, 2 draw, 3 the side to move resigned (outcome as if mated)
     first_ply: int = 0               # plies before it were handed to start_games(moves=...), not searched here
+    root_values: Optional[np.ndarray] = None  # float32 v_i per recorded ply (the root's q_value, side to move), when recorded
+    resign_check: bool = False       # a check game: resignation was disabled for it (resign_check_game)
+    resign: bool = False             # the run resigned games (resign_threshold was set)
 
     def z(self, i: int) -> float:    # self_play.py:202, for record i (ply first_ply + i)
         return self.outcome if self.positions[self.first_ply + i].turn == 1 else -self.outcome
+
+
+def resign_check_game(game_id: int, fraction: float) -> bool:
+    """The deterministic subset of game ids that never resign (the no-resign control, DESIGN "Resignation"): game_id is a check game
+    when ((game_id * 0x9E3779B1) mod 2**32) / 2**32 < fraction.  Depends on the id alone, not on rank, cohort or slot."""
+    return ((int(game_id) * 0x9E3779B1) & 0xFFFFFFFF) < float(fraction) * 4294967296.0
 
 
 def _fen_meta(fen: Optional[str]):
@@ -131,7 +141,28 @@ class Rollout:
                  dirichlet_epsilon: float = 0.25, max_plies: Optional[int] = None, max_game_moves: int = 16384,
                  temperature=(30, 1.0, 0.1), device: str = "cuda:0", use_graph: bool = True, autocast: bool = False,
                  rng_mode: str = "python", policy_kind: str = "logits", fast: bool = False, leaves_per_step: int = 16,
-                 fast_arena_granules: int = 0, stream: Optional["torch.cuda.Stream"] = None, time_tower: bool = False):
+                 fast_arena_granules: int = 0, stream: Optional["torch.cuda.Stream"] = None, time_tower: bool = False,
+                 resign_threshold: Optional[float] = None, resign_plies: int = 1, resign_check_fraction: float = 0.1,
+                 record_values: bool = False):
+        # resignation (DESIGN "Resignation"): a game resigns at ply i, before it plays, when v_i < resign_threshold at that ply and at its
+        # side's previous resign_plies - 1 searches; check games (resign_check_game) never resign.  None: today's code path exactly.
+        # record_values: keep v_i per ply (FinishedGame.root_values) with resignation off.
+        if resign_threshold is not None or record_values:
+            if fast:
+                raise ValueError("Rollout: resignation and root values need the reference search semantics (fast=False)")
+            if getattr(model, "is_pair", False):
+                raise ValueError("Rollout: resignation and root values are not supported in two-net matches")
+        if resign_threshold is not None:
+            if not (-1.0 <= float(resign_threshold) <= 1.0):
+                raise ValueError(f"Rollout: resign_threshold {resign_threshold} outside [-1, 1]")
+            if int(resign_plies) < 1:
+                raise ValueError("Rollout: resign_plies must be >= 1")
+            if not (0.0 <= float(resign_check_fraction) <= 1.0):
+                raise ValueError("Rollout: resign_check_fraction must lie in [0, 1]")
+        self.resign = resign_threshold is not None
+        self.resign_t = np.float32(resign_threshold) if self.resign else None
+        self.resign_k, self.resign_f = int(resign_plies), float(resign_check_fraction)
+        self.values = self.resign or bool(record_values)
         self.device = E.runtime_device(device)
         # `stream`: every launch of this Rollout goes to that HIP stream (CohortRollout: one stream per cohort of games, so that
         # one cohort's tower runs while another's tree step / head kernels / host turn are in progress); None = torch's current one
@@ -161,6 +192,8 @@ class Rollout:
                             device=dev_index, fast=fast, leaves_per_step=leaves_per_step, fast_arena_granules=fast_arena_granules)
         # fast=True: csrc/bo_fast.h (virtual loss, L leaves per game per step) -- NOT the reference's search semantics
         self.fast, self.L = bool(fast), self.eng.L
+        if self.values:
+            self.eng.root_values(True)  # (before any step is captured)
         self.nn_in = torch.zeros((self.G * self.L, E.INPUT_CHANNELS, 8, 8), dtype=torch.float32, device=self.device)
         # evaluations per search before the first poll: reference semantics = root + one per batch; fast mode = one per L
         # simulations (a root kept from the previous search needs no evaluation of its own; a fresh one costs one more round)
@@ -213,6 +246,13 @@ class Rollout:
         self._pi_val = np.zeros((G, 256, max(1, self._pk)), np.float32)
         self._out = dict(n=np.zeros(G, np.int32), idx=np.zeros((G, E.RES_CAP), np.int32), val=np.zeros((G, E.RES_CAP), np.float32),
                          best_idx=np.zeros(G, np.int32), action=np.zeros(G, np.int32))
+        if self.values:
+            self._out.update(root_value=np.zeros(G, np.float32), resigned=np.zeros(G, np.int32))
+        self._rv = np.zeros((G, 256 if self.values else 0), np.float32)   # v_i per slot and searched ply (native mode)
+        self._resigned = np.zeros(G, dtype=bool)       # the slot's game resigned at its last turn (finished by the next ply_begin)
+        self._renable = np.zeros(G, dtype=np.int32)    # resignation enabled for the slot's game (not a check game)
+        self._rcheck = np.zeros(G, dtype=bool)
+        self._rcnt = np.zeros((G, 2), dtype=np.int64)  # the host-made turn's counters (per ply parity; the device turn keeps its own)
         self.net_of_white = torch.zeros(G, dtype=torch.int32, device=self.device) if self.pair else None  # [slot]: 0 / 1 (start_games)
         self._sel = torch.zeros(G, dtype=torch.int32, device=self.device) if self.pair else None
         self._watch_net()
@@ -377,6 +417,10 @@ class Rollout:
             self._plies[s] = self._first_ply[s] = self.games[s].plies
             self._start_full[s], self._start_black[s] = full, 0 if white else 1
             self._start_step[s] = self._step
+            self._resigned[s] = False
+            self._rcnt[s] = 0
+            self._rcheck[s] = self.resign and resign_check_game(game_ids[i], self.resign_f)
+            self._renable[s] = 1 if (self.resign and not self._rcheck[s]) else 0
             if self.rng_mode == "native":
                 self.eng.rng_seed(s, int(rngs[i]))
 
@@ -422,12 +466,13 @@ class Rollout:
         n_legal, terminal, ply = self.eng.root_info(self._stream())
         t0 = time.perf_counter()
         done_slots = [g for g in range(self.G) if self.games[g] is not None and
-                      (terminal[g] != 0 or self.games[g].plies >= self.max_game_moves)]
+                      (terminal[g] != 0 or self._resigned[g] or self.games[g].plies >= self.max_game_moves)]
         self.host_seconds += time.perf_counter() - t0
         if done_slots:
             new_slots, ids, rngs, fens, mvs, nows = [], [], [], [], [], []
             for g in done_slots:
-                fin = self._finish(g, int(terminal[g]))
+                fin = self._finish(g, 3 if self._resigned[g] else int(terminal[g]))
+                self._resigned[g] = False
                 if on_finished is not None:
                     on_finished(fin)
                 self.games[g] = None
@@ -445,6 +490,8 @@ class Rollout:
                 while_searching()
             return 0
         res = self.search(go, n_legal, terminal)
+        rv = self.eng.search_root_value(self._stream()) if self.values else None
+        resigned = self._resign_decide(go, rv, np.array([0 if gs is None else gs.plies for gs in self.games], np.int64))
         t0 = time.perf_counter()
         actions = np.full(self.G, -1, dtype=np.int32)
         th, ti, tf = self.temperature
@@ -452,16 +499,36 @@ class Rollout:
             gs = self.games[g]
             n = int(res["n"][g])
             idx, val = res["idx"][g, :n].copy(), res["val"][g, :n].copy()
+            actions[g] = sampling.select_action_sparse(idx, val, gs.fullmove_number(), gs.rng, th, ti, tf)  # (drawn either way)
+            if resigned[g]:  # no move, no record for this search
+                actions[g] = -1
+                self._resigned[g] = True
+                continue
             gs.pis.append((idx, val))
-            actions[g] = sampling.select_action_sparse(idx, val, gs.fullmove_number(), gs.rng, th, ti, tf)
+            if rv is not None:
+                gs.root_values.append(rv[g])
             gs.plies += 1
         self.host_seconds += time.perf_counter() - t0
         self.eng.play(actions, self._stream())
         if while_searching is not None:
             while_searching()
-        n_moves = int(np.count_nonzero(go))
+        n_moves = int(np.count_nonzero(go & ~resigned))
         self.n_plies += n_moves
         return n_moves
+
+    def _resign_decide(self, go, rv, plies) -> np.ndarray:
+        """The host-made turn's resignation rule (the device turn's, bo_k_turn_sample / bo_k_turn_play): per enabled game that searched,
+        the counter of its side (ply parity) counts searches with v_i < t and is reset by one that does not; the game resigns when it
+        reaches resign_plies.  Called once per turn that happens (never for a turn that is made again)."""
+        out = np.zeros(self.G, dtype=bool)
+        if not self.resign:
+            return out
+        for g in np.nonzero(np.asarray(go, bool) & (self._renable != 0))[0]:
+            par = int(plies[g]) & 1
+            c = self._rcnt[g, par] + 1 if np.float32(rv[g]) < self.resign_t else 0
+            self._rcnt[g, par] = c
+            out[g] = c >= self.resign_k
+        return out
 
     def _forward_only(self):
         """The network forward alone (root evaluations of searches whose Dirichlet noise is still being drawn)."""
@@ -540,6 +607,8 @@ class Rollout:
             self._pp_t = t0
         want = self._active & (self._plies < self.max_game_moves)
         limit_done = np.nonzero(self._active & ~want)[0]
+        resign_done = np.nonzero(want & self._resigned)[0]  # (games that resigned at the last turn: over, no search)
+        want &= ~self._resigned
         self.host_seconds += time.perf_counter() - t0
         lazy = False
         if self._begun is not None:  # the previous turn already began these searches (bo_selfplay_turn)
@@ -564,7 +633,10 @@ class Rollout:
         if lazy:
             nl, term, go = self._run_search_steps(poll=False)
         if self.ply_profile is not None: self._pp("enqueue_search")
-        done = [int(g) for g in limit_done] + [int(g) for g in np.nonzero(want & (term != 0))[0]]
+        if len(resign_done):
+            term = np.array(term, copy=True)
+            term[resign_done] = 3
+        done = [int(g) for g in limit_done] + [int(g) for g in resign_done] + [int(g) for g in np.nonzero(want & (term != 0))[0]]
         for g in done:
             self._active[g] = False
         if not go.any():
@@ -608,6 +680,8 @@ class Rollout:
         move_number = self._start_full + (self._plies + self._start_black) // 2   # board.fullmove_number, self_play.py:104
         want_next = self._active & ((self._plies + go) < self.max_game_moves)     # (finished games' slots have been refilled by now)
         self._auto_want = want_next
+        if self.resign:
+            self.eng.selfplay_resign(self._renable, float(self.resign_t), self.resign_k)
         self.eng.selfplay_autoturn(go, move_number, self.temperature, want_next.astype(np.int32), self.nn_in.data_ptr(), self._stream(), redo=redo)
         self._auto = True
         self._prefetched = False
@@ -676,6 +750,25 @@ class Rollout:
                     self._turn_due = go
                     self._mark_enqueued()
                     return None
+        resigned = np.zeros(G, dtype=bool)
+        if out is not None and self.values:
+            resigned = (self._out["resigned"] != 0) & (go != 0)
+        elif out is None and self.values:
+            # the host-made turn with root values: wait for the searches, read v_i (bo_search_root_value), decide resignation, then
+            # sample (every searched game draws its uniform, as on the device), play and leave the next begin to ply_begin
+            while True:
+                running, _, _ = eng.poll(stream, want_mask=False)
+                if running == 0:
+                    break
+                self._eval_and_step()
+                if not block:
+                    self._turn_due = go
+                    self._mark_enqueued()
+                    return None
+            self._prefetched = False
+            self._out["root_value"][:] = eng.search_root_value(stream)
+            resigned = self._resign_decide(go, self._out["root_value"], self._plies)
+            out, begun = eng.selfplay_sample(go, move_number, self.temperature, self._out, stream), None
         while out is None:  # one native call per ply: "all searches finished?" + sample + play + begin the next searches
             out, begun = eng.selfplay_turn(go, move_number, self.temperature, self._out, want_next.astype(np.int32), self.nn_in.data_ptr(), stream,
                                            defer_noise=not self.fast, poll_first=True, lazy_begin=not self.fast, prefetched=self._prefetched)
@@ -701,6 +794,7 @@ class Rollout:
                 th, ti, tf = self.temperature
                 actions[g] = sampling.select_action_sparse(out["idx"][g, :n], out["val"][g, :n], int(move_number[g]), rs, th, ti, tf)
                 eng.rng_set_state(int(g), rs.get_state())
+            actions[resigned] = -1
             eng.play(actions, stream)
         else:
             self._begun, self._begun_want, self._noise_pending = begun, want_next.copy(), not self.fast
@@ -728,13 +822,21 @@ class Rollout:
             self._pi_val[rows, cols] = out["val"][rows, :self._pk]
         elif self._pk:
             self._pk = 0  # a denser pi than the reference's search produces: fall back to the per-step history
+        if self.values:  # v_i of every searched game into its slot's row (a resigned game's last one lies beyond its records)
+            rows = np.nonzero(go)[0]
+            cols = (self._plies[rows] - self._first_ply[rows]).astype(np.int64)
+            if len(cols) and cols.max() >= self._rv.shape[1]:
+                grow = max(2 * self._rv.shape[1], int(cols.max()) + 1)
+                self._rv = np.concatenate([self._rv, np.zeros((G, grow - self._rv.shape[1]), np.float32)], axis=1)
+            self._rv[rows, cols] = self._out["root_value"][rows]
+            self._resigned |= resigned
         self._step += 1
-        self._plies += go  # GameState.plies of the native mode is brought up to date when the game is finished
+        self._plies += go & ~resigned  # GameState.plies of the native mode is brought up to date when the game is finished
         lo = int(self._start_step[self._active].min()) if self._active.any() else self._step
         for st in [st for st in self._hist if st < lo]:
             del self._hist[st]
         self.host_seconds += time.perf_counter() - t0
-        n_moves = int(np.count_nonzero(go))
+        n_moves = int(np.count_nonzero(go & ~resigned))
         self.n_plies += n_moves
         if self.ply_profile is not None:
             self._pp("bookkeeping")
@@ -746,6 +848,7 @@ class Rollout:
         new_slots, ids, seeds, fens, mvs, nows = [], [], [], [], [], []
         for g in done:
             fin = self._finish(g, int(term[g]))
+            self._resigned[g] = False
             if on_finished is not None:
                 on_finished(fin)
             self.games[g] = None
@@ -762,7 +865,7 @@ class Rollout:
         if self.rng_mode == "native":
             gs.plies = int(self._plies[g])
         positions, moves = self.eng.export_game(g, self._stream(), n_plies=gs.plies)
-        outcome = 1.0 if terminal == 1 else 0.0
+        outcome = 1.0 if terminal in (1, 3) else 0.0  # (3: resigned -- as if the side to move at the last position had been mated)
         pis = gs.pis
         if self.rng_mode == "native" and self._pk:  # this game's sparse pis: three slices of its slot's rows
             t = max(0, len(moves) - gs.first_ply)
@@ -776,8 +879,13 @@ class Rollout:
         # one (state, pi) per move actually played (self_play.py:122,171): a start position that is already over yields
         # none, and a move the engine refused (no room left in the slot's position stack) leaves no record either
         pis = pis[:max(0, len(moves) - gs.first_ply)]
+        rv = None
+        if self.values:
+            t = max(0, len(moves) - gs.first_ply)
+            rv = self._rv[g, :t].copy() if self.rng_mode == "native" else np.asarray(gs.root_values[:t], dtype=np.float32)
         return FinishedGame(game_id=gs.game_id, slot=g, moves=moves, positions=positions, pis=pis, outcome=outcome,
-                            terminal=terminal, first_ply=gs.first_ply)
+                            terminal=terminal, first_ply=gs.first_ply, root_values=rv, resign_check=bool(self._rcheck[g]),
+                            resign=self.resign)
 
     # ---- training records ---------------------------------------------------------------------------------
     def encode_finished_in_slot(self, g: int, n_records: int, first_ply: int = 0) -> torch.Tensor:
@@ -797,7 +905,8 @@ class Rollout:
         if self.games[g] is None:
             return
         if on_finished is not None:
-            on_finished(self._finish(g, 0))
+            on_finished(self._finish(g, 3 if self._resigned[g] else 0))
+        self._resigned[g] = False
         self.games[g] = None
         self._active[g] = False
         nxt = refill(g) if refill is not None else None

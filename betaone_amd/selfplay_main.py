@@ -90,11 +90,13 @@ class ModelFileWatcher:
 
 
 def run_iteration(model, iteration: int, n_games: int, n_slots: int, rank: int = 0, world: int = 1,
-                  log: Callable[[str], None] = print, records: str = "pickle", reload_model=None) -> Dict[int, int]:
+                  log: Callable[[str], None] = print, records: str = "pickle", reload_model=None,
+                  rollout_kw: Optional[dict] = None) -> Dict[int, int]:
     """Play the games of `iteration` that are not on disk yet.  records: "pickle" = the reference's one pickle per game
     (self_play.py:220-231), "compact" = ~100 B/ply records appended to DATA_DIR/iter_{i}/games_rank{rank}.bog
     (betaone_amd.records, read back by records.CompactDataset with ChessDataset's item contract), "both".
-    Returns {game_id: plies}."""
+    rollout_kw: resignation / root-value arguments of the Rollout (--resign-threshold, --resign-plies, --resign-check-fraction,
+    --record-values; compact records then are BOG2 with the per-ply root values).  Returns {game_id: plies}."""
     from betaone_amd import dropin
 
     dropin.install()
@@ -125,7 +127,8 @@ def run_iteration(model, iteration: int, n_games: int, n_slots: int, rank: int =
 
     results = self_play.run_self_play_games(model, todo, seeds=[game_seed(iteration, j) for j in todo],
                                             n_slots=min(n_slots, len(todo)), on_game=on_game, dense=records != "compact",
-                                            reload_model=reload_model, on_records=on_records if records != "compact" else None)
+                                            reload_model=reload_model, on_records=on_records if records != "compact" else None,
+                                            rollout_kw=rollout_kw)
     for j, data in results.items():
         if data is None:
             done.pop(j, None)  # aborted game (self_play.py:167): no record
@@ -164,9 +167,21 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--records", default="pickle", choices=["pickle", "compact", "both"],
                     help="pickle: the reference's game_{id}.pkl; compact: games_rank{r}.bog (~100 B/ply, records.CompactDataset); both")
     ap.add_argument("--watch-model", action="store_true", help="reload the state_dict file whenever it changes on disk (checked every 8 plies)")
+    ap.add_argument("--resign-threshold", type=float, default=None, metavar="T",
+                    help="resign a game when the root value of the side to move stays below T (DESIGN \"Resignation\"); default: never resign")
+    ap.add_argument("--resign-plies", type=int, default=1, metavar="K", help="consecutive own searches below T before resigning (default 1)")
+    ap.add_argument("--resign-check-fraction", type=float, default=0.1, metavar="F",
+                    help="fraction of game ids that never resign, to calibrate T (python -m betaone_amd.resign; default 0.1)")
+    ap.add_argument("--record-values", action="store_true", help="keep the per-ply root values in compact records with resignation off")
     args = ap.parse_args(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, ["-m", "betaone_amd.selfplay_main"] + list(sys.argv[1:] if argv is None else argv)))
+    rollout_kw = {}
+    if args.resign_threshold is not None:
+        rollout_kw.update(resign_threshold=args.resign_threshold, resign_plies=args.resign_plies,
+                          resign_check_fraction=args.resign_check_fraction)
+    if args.record_values:
+        rollout_kw["record_values"] = True
     import torch
 
     from betaone_amd import dropin
@@ -189,7 +204,7 @@ def main(argv: Optional[List[str]] = None):
     model.eval()
     watcher = ModelFileWatcher(path, network.PolicyValueNet, config.DEVICE) if args.watch_model else None
     run_iteration(model, args.iteration, args.games or config.GAMES_MINIMUM, args.slots, rank, world, records=args.records,
-                  reload_model=watcher.poll if watcher else None)
+                  reload_model=watcher.poll if watcher else None, rollout_kw=rollout_kw or None)
     if watcher:
         print(f"[rank {rank}] weights reloaded {watcher.n_reloads} time(s) from {path}")
 

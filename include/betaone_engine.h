@@ -26,9 +26,10 @@ extern "C" {
 
 /* Bumped whenever an output size, a struct, or the layout a caller has to produce changes (2: bo_debug_profile (betaone_lab.h) returns
  * [G][BO_PROF_SLOTS = 16] counters, the BO_TOWER_WINOGRAD packed-weight K order for 128 filters is winograd_k_order's;
- * 3: fast-mode arenas are allocated in 128-byte granules of 8 records, bo_fast_stats counts granules).  A caller checks
+ * 3: fast-mode arenas are allocated in 128-byte granules of 8 records, bo_fast_stats counts granules; 7: resignation and root values,
+ * additions only).  A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 6
+#define BO_ABI_VERSION 7
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -229,6 +230,28 @@ int bo_selfplay_autoturn_ready(bo_engine *e, int32_t *ready_out);
  * evaluation + bo_step, then bo_selfplay_autoturn(redo = 1).  A result the device sampler does not cover is BO_E_STATE. */
 int bo_selfplay_autoturn_collect(bo_engine *e, int32_t *res_n, int32_t *res_idx, float *res_val, int32_t *best_idx, int32_t *action_out,
                                  int32_t *n_legal_out, int32_t *terminal_out, int32_t *go_out, int32_t *completed);
+
+/* ---- (ABI 7, additions) root values and resignation ----------------------------------------------------------------------------
+ * v_i = the root's q_value after the search at ply i (float32 as the tree holds it; mcts.py:120-144 update_recursive, the value from the
+ * perspective of the side to move at the root).  Both turns report the same bits.
+ * bo_engine_root_values(e, 1): keep the root's q_value exact in every backup (the step kernel's run of terminal simulations otherwise
+ * updates the root's visit count only: selection never reads the root's q).  Off by default; v_i below is meaningful only with it on.
+ * Call it before the first bo_step a graph captures (a captured launch keeps the engine state it was captured with).
+ * bo_selfplay_autoturn_collect_ex: bo_selfplay_autoturn_collect plus, per slot, root_value_out[g] = v_i (0 where the game did not search)
+ * and resigned_out[g] (1: the game resigned at this ply; action -1, no move played, no next search begun, go_out 0).  Either may be NULL.
+ * bo_selfplay_resign: resignation in the device turn from the next bo_selfplay_autoturn on.  enable [G] (NULL: off for every slot):
+ * per slot, resignation enabled.  An enabled game resigns at ply i, before it plays, when v_i < threshold (float32 compare) at that ply
+ * and at its side's previous plies - 1 searches (i - 2, i - 4, ...): a counter per slot and ply parity, reset by bo_games_reset*,
+ * decided by the turn's first kernel from the committed value and committed by the second one only when the turn happens (a redo
+ * after *completed == -1 counts nothing twice).  plies >= 1.  Reference-semantics engines with root values on (BO_E_STATE otherwise).
+ * bo_search_root_value: out [G] = the root's q_value of every slot (v_i for a finished search) -- the host-made turn's v_i.
+ * Synchronises. */
+int bo_selfplay_autoturn_collect_ex(bo_engine *e, int32_t *res_n, int32_t *res_idx, float *res_val, int32_t *best_idx, int32_t *action_out,
+                                    int32_t *n_legal_out, int32_t *terminal_out, int32_t *go_out, float *root_value_out,
+                                    int32_t *resigned_out, int32_t *completed);
+int bo_engine_root_values(bo_engine *e, int32_t on);
+int bo_selfplay_resign(bo_engine *e, const int32_t *enable, float threshold, int32_t plies);
+int bo_search_root_value(bo_engine *e, float *out, void *stream);
 
 /* ---- records ------------------------------------------------------------------------------------
  * The game in `slot` as plain data: its positions[0..n_plies] and moves[0..n_plies). */
@@ -565,6 +588,11 @@ int bo_position_fen(const bo_position *p, char *out, int32_t cap);
  * in cap bytes (nothing is written then) or a ply has no SAN.  Host only. */
 int bo_pgn_movetext(int32_t n_plies, const void *san, const uint8_t *state, int32_t root_turn, int32_t root_fullmove, const uint8_t *comments,
                     const char *result, char *out, int64_t cap, int64_t *len_out);
+/* (ABI 7) The same with a comment TEXT per ply: comment i is text[text_off[i] .. text_off[i + 1]) (text_off [n_plies + 1]; an empty
+ * range: none), written as "{...}" after move i -- e.g. the eval comments "+0.12/100 0.00s" of self-play records.  final_comment (may
+ * be NULL or empty) is written as one more "{...}" after the last move (e.g. "White resigns").  Same layout rules. */
+int bo_pgn_movetext_text(int32_t n_plies, const void *san, const uint8_t *state, int32_t root_turn, int32_t root_fullmove, const char *text,
+                         const int32_t *text_off, const char *final_comment, const char *result, char *out, int64_t cap, int64_t *len_out);
 
 #ifdef __cplusplus
 }
