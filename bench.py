@@ -2,7 +2,7 @@
 """
 bench.py -- headline benchmark of the self-play rollout path on MI355X (contract: see the task statement).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Metric (BASELINE.json): MCTS nodes/sec (+ self-play plies / games per hour) at 800 simulations per move
@@ -16,12 +16,15 @@ runs its own 256 games (game id -> rank by id mod world); the only collective is
 The timed region is STEADY-STATE self-play: before it, `--preroll` plies are played (untimed, staggered slot starts, same
 engine, same settings) so that the resident games are at every stage of a game, finished games leave and new ones start
 in every step, and games/hour is measured, not extrapolated.  The opening-only figure (all games at the start position) is
-reported as the labelled extra `opening_phase`.
+reported as the labelled extra `opening_phase` (--full).
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a torch.distributed.run child
 process, started before this process touches a GPU) and relays rank 0's JSON line.
 
-Also measured live, per the contract:
+A plain run does only what the headline needs: set up (pre-roll included), warm up, time the K steps, write --dump-outputs,
+print the line.  With --full it also measures, after the timed steps and the dump (so neither depends on it):
+  long_run      the confirmation leg: 2000 more plies of the default workload under the same brackets
+  opening_phase the labelled opening-only extra
   roofline      the dominant kernel of the timed workload: the evaluate stage's residual-tower kernel (MFMA-bound, HIP events
                 on its stream); with --fast the select + backup kernel on the trees the run grew (HBM, engine byte counters)
   roofline_select_wide_synthetic
@@ -29,6 +32,7 @@ Also measured live, per the contract:
   roofline_step the in-loop tree-step kernel (latency-bound, cache-resident; reported for honesty)
   cpu_baseline  the CPU oracle (oracle/, a C port of the reference) + the same net under torch-CPU: one game per core on
                 the box's host cores (the reference's mp.Pool, main.py:168), bounded sample; per-core and x cores
+`--long-run-steps` / `--opening-steps` given by name run their leg without --full too.
 """
 from __future__ import annotations
 
@@ -77,7 +81,8 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-cores", type=int, default=0, help="0 = the box's CPU share (affinity mask, at most 16)")
     ap.add_argument("--preroll", type=int, default=None, help="untimed plies played before warm-up to reach steady state (0 = opening phase; default 640, --fast: 10)")
-    ap.add_argument("--opening-steps", type=int, default=20, help="plies of the labelled opening-only extra measurement (0 = skip)")
+    ap.add_argument("--opening-steps", type=int, default=None,
+                    help="plies of the labelled opening-only extra measurement (0 = skip; default 20 with --full, else 0; --fast: 0)")
     ap.add_argument("--softmax", default="torch", choices=["torch", "engine"],
                     help="policy softmax: in the evaluate stage (torch: torch.softmax as in the reference, or the stage's own head kernel bo_k_heads_rows: the "
                          "seam the oracle replays are recorded at) or in the tree kernel that consumes the row (engine; with the hand-written float32 heads the "
@@ -92,8 +97,8 @@ def parse():
     ap.add_argument("--leaves", type=int, default=4, help="FAST mode: leaves per game per step")
     ap.add_argument("--select-games-per-halfwave", type=int, default=None, help="FAST mode: bo_fast_options games_per_halfwave (2 or 4)")
     ap.add_argument("--select-flags", type=int, default=None, help="FAST mode: bo_fast_options select_flags (1 nt, 2 root in registers, 4 dense)")
-    ap.add_argument("--select-sweep", action="store_true", help="FAST mode: time every variant of the select + backup kernel on this run's trees")
-    ap.add_argument("--roofline-steps", type=int, default=48, help="FAST mode: evaluate -> step iterations run eagerly for the select kernel's event timing")
+    ap.add_argument("--select-sweep", action="store_true", help="FAST mode with --full: time every variant of the select + backup kernel on this run's trees")
+    ap.add_argument("--roofline-steps", type=int, default=48, help="FAST mode with --full: evaluate -> step iterations run eagerly for the select kernel's event timing")
     ap.add_argument("--arena-granules-per-expansion", type=int, default=12, help="FAST mode: arena size per game = this x (sims + leaves + 2) granules of 128 B")
     ap.add_argument("--max-game-moves", type=int, default=None, help="config.MAX_GAME_MOVES (small values make games finish: record path; default 16384, --fast: 510)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="gloo: rehearsal of the N>1 path on one GPU")
@@ -101,7 +106,10 @@ def parse():
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0")
     ap.add_argument("--long-run-steps", type=int, default=None,
                     help="plies of the confirmation leg run AFTER the timed steps (same workload, same timing brackets; reported as long_run); "
-                         "default 2000 at N=1 with the default workload (~5.5 s of GPU work: longer than a 5-second utilisation sampler's period), 0 elsewhere")
+                         "default with --full 2000 at N=1 with the default workload (~5.5 s of GPU work: longer than a 5-second utilisation sampler's period), 0 elsewhere")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline, after the timed steps: long_run, opening_phase, the rooflines "
+                         "(--fast: the select + backup kernel's) and the CPU baseline; --no-roofline / --no-cpu-baseline still leave theirs out")
     args = ap.parse_args()
     # --fast is priced on its own workload: enough resident games for the select + backup kernel to be
     # bandwidth-bound (a descent is a chain of dependent reads), a small fp16 net so that the evaluate stage does not starve it
@@ -120,11 +128,13 @@ def parse():
         args.warmup = 0 if args.fast else 3
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
-    if args.fast and args.opening_steps == 20:
-        args.opening_steps = 0          # (the opening-only extra would be twenty such plies)
+    if args.select_sweep and not args.full:
+        ap.error("--select-sweep is part of the fast mode's roofline: give --full with it")
+    if args.opening_steps is None:      # (--fast: the opening-only extra would be twenty plies of 32768 games)
+        args.opening_steps = 20 if (args.full and not args.fast) else 0
     if args.long_run_steps is None:     # ~5.5 s of the default workload; off for other workloads, N > 1 and with measurement switches off
         default_workload = (not args.fast and args.gpus == 1 and (args.games, args.sims, args.net, args.net_dtype) == (256, 800, "10x128", "fp32"))
-        args.long_run_steps = 2000 if (default_workload and args.preroll > 0 and not args.no_roofline) else 0
+        args.long_run_steps = 2000 if (args.full and default_workload and args.preroll > 0 and not args.no_roofline) else 0
     return args
 
 
@@ -760,6 +770,7 @@ def main():
                  rng_mode="native", max_game_moves=args.max_game_moves, fast=args.fast, leaves_per_step=args.leaves,
                  fast_arena_granules=(args.arena_granules_per_expansion * (args.sims + args.leaves + 2) if args.fast else 0),
                  policy_kind="probs" if args.softmax == "torch" else "logits",
+                 # (the tower's launches note their own durations in every run, --full or not: the timed steps are the same ones either way)
                  time_tower=(not args.no_roofline and not args.fast and args.net_dtype == "fp32"))
     ro = CohortRollout(net, G, cohorts=args.cohorts, cu_masks=args.cu_masks, **ro_kw) if args.cohorts > 1 else Rollout(net, G, **ro_kw)
     if args.fast and G * args.leaves > 65536:
@@ -811,7 +822,8 @@ def main():
     if args.dump_outputs:  # (before anything after the timed steps plays on: the state is the last timed step's)
         dump_outputs(args.dump_outputs, ro, drv, rank)
     timed = None
-    if timing_on:  # the tower launches of the timed region, timed by the kernel itself
+    roof = args.full and not args.no_roofline  # (the roofline legs: --full only)
+    if timing_on and roof:  # the tower launches of the timed region, timed by the kernel itself
         khz = C_INT32(0)
         E.load_hip_library().bo_device_wall_clock_khz(device.index or 0, ctypes.byref(khz))
         timed = tower_timings(parts, seq0, float(khz.value or 100000))
@@ -897,7 +909,7 @@ def main():
                    "steps": args.opening_steps, "note": "all games within their first ~25 plies; not the headline"}
 
     fast_roof = rn = sweep = None
-    if rank == 0 and args.fast and not args.no_roofline and dist is None:
+    if rank == 0 and args.fast and roof and dist is None:
         if args.select_sweep:
             sweep = fast_select_sweep(ro, drv)
             best = max(sweep, key=lambda r: r["frac"]) if sweep else None
@@ -906,7 +918,7 @@ def main():
         fast_roof = fast_select_roofline(ro, drv, args.roofline_steps)
         if fast_roof is not None and args.select_sweep:
             fast_roof["variants"] = sweep
-    if rank == 0 and not args.no_roofline and not args.fast and args.net_dtype == "fp32":
+    if rank == 0 and roof and not args.fast and args.net_dtype == "fp32":
         rn = nn_roofline(net, G // args.cohorts, device, timed, dt * 1e6, all_boards=G, launches_per_ply=fwd / args.steps / max(args.cohorts, 1),
                          ply_us=(long_run["ms_per_step"] * 1e3 if long_run else dt / args.steps * 1e6))
 
@@ -964,7 +976,7 @@ def main():
                                       "hardware_coverage": "the builder's pool hands out one-GPU boxes: RCCL between DISTINCT GPUs has never run before this "
                                                            "command; covered so far: gloo world 2/4/8 on CPU, RCCL at N=1, two gloo ranks sharing one GPU"}
             out["per_rank_ms_per_step"] = {"min": min(per_rank_ms), "max": max(per_rank_ms), "ranks": per_rank_ms}
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roof:
         sr = step_roofline(ro, args.steps)
         out["roofline_step"] = {"bound": "latency", "note": "parity-mode trees are cache-resident (a few KB per game)",
                                 "select_alg_bytes_total": sr["levels"] * 8 + sr["children_scanned"] * 12, **sr}
@@ -974,7 +986,7 @@ def main():
     if dump is not None:
         with open(args.dump_games if world == 1 else f"{args.dump_games}.rank{rank}", "w") as f:
             json.dump(dump, f)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roof:
         # `roofline` = the DOMINANT kernel of the timed workload.  Reference semantics: the evaluate stage's tower kernel
         # (~80 % of a ply, MFMA-bound).  Fast mode: its select + backup kernel on the trees this run grew (what SURVEY.md
         # section 8f asks to price).  The north star's select target on the section-8d synthetic wide workload
@@ -990,9 +1002,9 @@ def main():
                 wide["kernel"] = "bo_k_select_wide (lab kernel: select only, static synthetic trees; no search runs it)"
                 out["roofline_select_wide_synthetic"] = wide
             out["roofline"] = rn if rn else wide
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.fast:  # "on rank 0 at N=1 only"
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline and not args.fast:  # "on rank 0 at N=1 only"
         out["cpu_baseline"] = cpu_baseline(args)
-    elif rank == 0 and args.fast:
+    elif rank == 0 and args.full and args.fast:
         out["cpu_baseline"] = None  # the fast mode is not the reference's algorithm: nothing of the reference to time beside it
     if dist is not None:
         dist.barrier()
