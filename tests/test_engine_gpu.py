@@ -406,7 +406,10 @@ def test_fp16_tower_matches_half_precision_net(backend, size, tile, monkeypatch)
         half = net.for_inference(dtype=torch.float16, channels_last=False)
         z = np.load(__import__("os").path.join(__import__("os").path.dirname(__file__), "golden", "g1_net.npz"))
         base = torch.from_numpy(z["inputs"]).to("cuda:0")
-        for nb in (1, 2, 7, 300):  # odd counts: the last workgroup holds one board; 300 > 2 x 128 pairs loop
+        n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+        # odd counts: the last workgroup holds one board.  The grid is min(pairs, n_cu) workgroups: 300 boards are 150 pairs, one pass
+        # at 256 CUs; 2 n_cu + 75 (odd) and 4 n_cu + 3 boards make the workgroups loop (the latter: three passes, the fp16 heads kernel)
+        for nb in (1, 2, 7, 300, 2 * n_cu + 75, 4 * n_cu + 3):
             x = (base.repeat(nb // 3 + 1, 1, 1, 1)[:nb] * torch.linspace(0.5, 1.0, nb, device="cuda:0")[:, None, None, None]).contiguous()
             with torch.no_grad():
                 l0, v0 = net(x)

@@ -65,7 +65,8 @@ def _check_pair_bitwise(shape, route, tile=None):
         assert fa.split_tile == fb.split_tile == tile
     pair = PairedNet(fa, fb, batch=64, device=DEV)
     assert pair.route == ("pair:tower_split" if route == "tower_split" else "pair:merge")
-    for B in (64, 256):
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    for B in (64, 256, 2 * n_cu + 37):  # (the shared launch's grid is min(B, n_cu) workgroups: the last batch takes three passes)
         x = _inputs(B)
         for probs in (False, True):
             with torch.no_grad():

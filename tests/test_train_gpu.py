@@ -161,9 +161,11 @@ def test_one_step_sparse_equals_dense(games):
 def test_twenty_amp_steps_follow_the_dense_loss(games):
     """torch.autocast + GradScaler, AdamW at the reference's learning rate, 20 steps from the same weights on the same batches.  The first
     step's losses agree to the kernels' precision (measured: 2e-5 relative).  After it the runs are trajectories: under autocast even the
-    dense path against itself differs by 3.7e-3 relative within 20 steps, and when GradScaler skips an overflowing step in one run and
-    not in the other the curves part by a step's worth (measured up to 6.6e-2).  The whole curve is held to a band that a wrong gradient
-    would leave."""
+    dense path against itself differs by 3.7e-3 relative within 20 steps.  The scaler starts at 2^10, not at its default 2^16: at 2^16
+    the first steps' overflow check sits at the edge, so that of two identical runs of the dense path one skipped a step and the other
+    did not, and the curves parted by a step's worth (measured: 7e-2 relative in the total loss, 0.8 in the value loss against the
+    band's 1e-1).  At 2^10 no run skips a step (asserted), and sparse against dense stayed within 7e-3 for every order of the games
+    tried.  The whole curve is held to a band that a wrong gradient would leave."""
     from betaone_amd.train import train_steps
 
     buf = _buffer(games)
@@ -172,9 +174,10 @@ def test_twenty_amp_steps_follow_the_dense_loss(games):
         net = _net(8, 2, 128, seed=4).train()
         opt = torch.optim.AdamW(net.parameters(), lr=1e-3, weight_decay=1e-4)
         sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=1000, eta_min=5e-7)
-        scaler = torch.GradScaler("cuda")
+        scaler = torch.GradScaler("cuda", init_scale=2.0 ** 10)
         r = train_steps(net, opt, sched, scaler, buf.loader(256, steps=20, seed=9, sparse=sparse), sparse=sparse, amp=True)
         assert r["steps"] == 20
+        assert scaler.get_scale() == 2.0 ** 10  # no step was skipped (and 20 steps are far from the scaler's growth interval)
         curves.append(np.array(r["losses"]))
     assert np.isfinite(curves[0]).all()
     rel = np.abs(curves[0] - curves[1]) / np.abs(curves[1])
