@@ -20,8 +20,12 @@
 // PyTorch's float32 log_softmax.  fp16 and bf16 outputs are rounded once, to nearest even, so a value beyond the fp16 range
 // becomes inf where PyTorch's cast of its float32 gradient would (GradScaler skips the step on it).
 // Non-finite logits are not masked: a NaN or +inf logit makes the row's max NaN / inf, and its softmax and gradient NaN, as in
-// PyTorch; any non-finite logit makes the row's policy term NaN (PyTorch's dense target multiplies the -inf by a zero).  A row
-// with no valid entries adds 0 to the policy loss and gets a zero policy gradient.
+// PyTorch; any non-finite logit makes the row's policy term NaN (PyTorch's dense target multiplies the -inf by a zero; with the -inf
+// under a target entry PyTorch's term is +inf, here it is NaN all the same).  A -inf logit leaves the max and the sum alone: its
+// softmax is 0 and the row's gradient finite, -g_p/B t at that action if it is a target, as in PyTorch (a row of nothing but
+// -inf has max -inf, x - max NaN, and a NaN gradient throughout).  A row with no valid entries adds 0 to the policy loss and gets
+// a zero policy gradient.  Entries whose index is not an action (-1 or anything else outside 0..4671) are skipped, values
+// included; an action twice in a row is not defined.
 #pragma once
 #include "bo_wave.h"
 

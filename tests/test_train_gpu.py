@@ -1,10 +1,14 @@
 """GPU tests of the training stage on the MI355X: the sparse-target loss kernels (csrc/bo_train.h) against PyTorch on the device in
-float32 and fp16, one training step of the bench's 10x128 net on sparse batches against the reference's dense loss, and the loop
-self-play -> train --candidate -> match end to end."""
+float32 and fp16 and, element by element, against the float64 reference and envelope of tests/loss_cases.py on every case and
+dtype pair (with the non-finite rows, guard rows, row independence and the replay samplers at wide rows), one training step of the
+bench's 10x128 net on sparse batches against the reference's dense loss, and the loop self-play -> train --candidate -> match end
+to end."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import loss_cases as LC
 
 pytestmark = pytest.mark.gpu
 
@@ -81,6 +85,8 @@ def test_loss_kernels_match_torch_float32(B, W):
     assert (gx - gx_ref).abs().max().item() <= 1e-6 and (gv - gv_ref).abs().max().item() <= 1e-6
     l2, gx2, _ = _sparse(*case, gscale)
     assert torch.equal(l.view(torch.int32), l2.view(torch.int32)) and torch.equal(gx.view(torch.int32), gx2.view(torch.int32))
+    ref = LC.reference64(*case, (0.75, 0.0, 0.0))  # every element, the small ones too, against float64
+    LC.check_against_reference((l, gx, gv.reshape(-1)), ref, LC.envelope(ref), f"B={B} W={W}")
 
 
 def _ulp16(t):
@@ -105,6 +111,50 @@ def test_loss_kernels_match_torch_fp16(B, W):
             assert bool(((mine.float() - ref.float()).abs()[fin] <= _ulp16(ref)[fin]).all())
         if gscale > 2.0 ** 20:
             assert bool(torch.isinf(gx).any()) and bool(torch.isfinite(gx).any())
+
+
+CASES = LC.cases()
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c.name)
+def test_every_case_and_dtype_pair_against_float64(case):
+    """sparse_policy_value_loss and its backward on every dtype pair (logits, value) against reference64 with the conditions of
+    tests/loss_cases.py, and a second call bit for bit.  Prints the worst error / envelope of every pair."""
+    for pair in LC.PAIRS:
+        t = LC.cast(case, pair, DEV)
+        out = LC.run_loss(*t, case.w3)
+        assert out[1].dtype == pair[0] and out[2].dtype == pair[1]
+        ref = LC.reference64(*t, case.w3)
+        what = f"{case.name} {LC.short(pair[0])}/{LC.short(pair[1])}"
+        r = LC.check_against_reference(out, ref, LC.envelope(ref), what)
+        if case.name.startswith("overflow_fp16") and pair[0] == torch.float16:
+            assert bool(torch.isinf(out[1]).any()) and bool(torch.isfinite(out[1]).any())
+        again = LC.run_loss(*t, case.w3)
+        assert all(LC.same_bits(a, b) for a, b in zip(out, again)), what + ": a second call differs"
+        print(f"RATIO gpu {what} loss {r['loss']:.3f} dlogits {r['dlogits']:.3f} dvalue {r['dvalue']:.3f}")
+
+
+@pytest.mark.parametrize("case", LC.nonfinite_cases(), ids=lambda c: c.name)
+def test_non_finite_logits_as_the_header_states(case):
+    for pair in ((torch.float32, torch.float32), (torch.float16, torch.float16), (torch.bfloat16, torch.float32)):
+        LC.check_nonfinite(case, pair, DEV)
+
+
+@pytest.mark.parametrize("name", ["B65_W63_dom90_last_empty_rows", "B127_W63_randn001_invalid", "B4097_W2_pos80_edges"])
+def test_rows_do_not_depend_on_their_place_in_the_batch(name):
+    case = next(c for c in CASES if c.name == name)
+    for pair in ((torch.float32, torch.float32), (torch.float16, torch.bfloat16)):
+        LC.check_row_independence(case, pair, DEV)
+
+
+@pytest.mark.parametrize("name", ["B65_W2_dom60_first_full", "B65_W63_dom90_last_empty_rows", "B4097_W2_pos80_edges",
+                                  "B4097_W64_randn3_invalid"])
+def test_loss_kernels_write_no_row_past_the_batch(name):
+    """bo_train_loss_forward / bo_train_loss_backward called directly at B = 65 and 4097 with row_stats, dlogits and dvalue 64 guard
+    rows longer than the batch: the guard keeps its NaN payload, every row below B is written, and the results are the reference's."""
+    case = next(c for c in CASES if c.name == name)
+    for pair in ((torch.float32, torch.float32), (torch.float16, torch.float16), (torch.bfloat16, torch.float16)):
+        LC.check_guard_rows(case, pair, DEV)
 
 
 @pytest.fixture(scope="module")
@@ -135,6 +185,14 @@ def _buffer(games):
     buf = R.GpuReplayBuffer(20000, device=DEV, pi_width=2)
     buf.add(games)
     return buf
+
+
+@pytest.mark.parametrize("W", [1, 64, 65, LC.res_cap()])
+def test_replay_samplers_at_wide_rows(games, W):
+    """GpuReplayBuffer(pi_width=W) over the fixture's games with seeded synthetic pis of 0..W entries: batch_sparse equals the records
+    entry for entry, its scatter equals batch bit for bit, and one loss forward and backward on that batch meets the reference."""
+    r = LC.check_wide_replay(games, W, DEV, seed=11)
+    print(f"RATIO gpu replay W={W} f32/f32 loss {r['loss']:.3f} dlogits {r['dlogits']:.3f} dvalue {r['dvalue']:.3f}")
 
 
 def test_one_step_sparse_equals_dense(games):
