@@ -12,6 +12,7 @@
 #include "bo_train.h"
 #include "bo_pgn.h"
 #include "bo_san.h"
+#include "bo_analyse.h"
 #include "bo_nn_fused.h"
 #include "bo_conv.h"
 #include "bo_tower.h"
@@ -1468,6 +1469,60 @@ extern "C" int bo_pgn_sample(const void *pos_dev, const int32_t *act_dev, const 
 }
 
 extern "C" void bo_pgn_destroy(bo_pgn *p) { delete p; }
+
+// ---- analysis of games that are already on the device (bo_analyse.h; ABI 8) ------------------------------------------------------
+static_assert(sizeof(bo_analysis) == BO_ANALYSIS_WORDS * 4, "bo_analysis is BO_ANALYSIS_WORDS words");
+static_assert(BO_ST_BAD_RANGE == ST_BAD_RANGE, "status bits");
+
+// bo_games_reset for roots that bo_pgn_replay left in HBM.  Asynchronous: every array is read by the kernel when it runs.
+extern "C" int bo_games_reset_dev(bo_engine *e, int n, const int32_t *slots_dev, const void *pos_dev, int64_t capacity, const int64_t *first_dev,
+                                  const int32_t *ply_dev, void *stream) {
+    if (!e || n < 1 || !slots_dev || !pos_dev || !first_dev || !ply_dev) return fail(BO_E_ARG, "bo_games_reset_dev: bad arguments");
+    if (e->fast) return fail(BO_E_CONFIG, "bo_games_reset_dev: reference-semantics engines only");
+    if (n > e->d.c.G) return fail(BO_E_ARG, "bo_games_reset_dev: more slots than the engine has");
+    if (capacity < 1) return fail(BO_E_ARG, "bo_games_reset_dev: the position array is empty");
+    SetupDevArgs a;
+    a.slots = slots_dev; a.pos = (const DPos *)pos_dev; a.capacity = capacity; a.first = (const long long *)first_dev; a.ply = ply_dev;
+    e->nl_valid = false;
+    e->prefetch_valid = false;
+    RT(RT_LAUNCH(bo_k_setup_dev, n, stream, e->d, a));
+    return BO_OK;
+}
+
+// The begin of the device turn as an entry point: a wanted slot whose root is not terminal searches (mcts.py:160-162).  No Dirichlet
+// noise can be handed in this way: engines created with dirichlet_alpha <= 0 only.  Asynchronous.
+extern "C" int bo_search_begin_dev(bo_engine *e, const int32_t *want_dev, float *nn_in_dev, void *stream) {
+    if (!e || !want_dev || !nn_in_dev) return fail(BO_E_ARG, "bo_search_begin_dev: null argument");
+    if (e->fast) return fail(BO_E_CONFIG, "bo_search_begin_dev: reference-semantics engines only");
+    if (e->d.c.use_noise) return fail(BO_E_CONFIG, "bo_search_begin_dev: the roots get no Dirichlet noise (create the engine with dirichlet_alpha <= 0)");
+    e->nl_valid = false;
+    RT(RT_LAUNCH(bo_k_search_begin_want, e->d.c.G, stream, e->d, (const int *)want_dev, nn_in_dev));
+    return BO_OK;
+}
+
+// bo_k_result + bo_k_analysis: one bo_analysis record per slot into out[G].  Asynchronous.
+extern "C" int bo_analysis_result(bo_engine *e, const int32_t *played_dev, bo_analysis *out, void *stream) {
+    if (!e || !out) return fail(BO_E_ARG, "bo_analysis_result: null argument");
+    if (e->fast) return fail(BO_E_CONFIG, "bo_analysis_result: reference-semantics engines only");
+    if (!e->d.c.root_q) return fail(BO_E_STATE, "bo_analysis_result: call bo_engine_root_values(e, 1) first");
+    RT(RT_LAUNCH(bo_k_result, e->d.c.G, stream, e->d));
+    RT(RT_LAUNCH(bo_k_analysis, e->d.c.G, stream, e->d, (const int *)played_dev, (int *)out));
+    return BO_OK;
+}
+
+extern "C" int bo_pgn_after(const void *pos_dev, const int32_t *act_dev, int64_t capacity, int32_t n, const int64_t *idx_dev, void *pos_out_dev,
+                            int32_t *move_out_dev, void *stream) {
+    if (!pos_dev || !act_dev || capacity < 1 || n < 1 || !idx_dev || (!pos_out_dev && !move_out_dev)) return fail(BO_E_ARG, "bo_pgn_after: bad arguments");
+    RT(RT_LAUNCH(bo_k_pgn_after, (n + 63) / 64, stream, (const DPos *)pos_dev, (const int *)act_dev, (long long)capacity, (int)n, (const long long *)idx_dev,
+                 (DPos *)pos_out_dev, (int *)move_out_dev));
+    return BO_OK;
+}
+
+extern "C" int bo_pgn_spans(const bo_pgn *p, int64_t *begin, int64_t *end) {
+    if (!p || !begin || !end) return fail(BO_E_ARG, "bo_pgn_spans: bad arguments");
+    for (size_t g = 0; g < p->status.size(); g++) { begin[g] = p->span[2 * g]; end[g] = p->span[2 * g + 1]; }
+    return BO_OK;
+}
 
 // ---- PGN export (bo_san.h) -----------------------------------------------------------------------------------------------------
 extern "C" int bo_san_render(int32_t n_games, int32_t n_positions, const int32_t *game_off_dev, const void *positions_dev,

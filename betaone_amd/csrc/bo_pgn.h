@@ -133,6 +133,7 @@ struct bo_pgn_s {
     std::vector<uint32_t> tok;
     std::vector<int8_t> has_eval;
     std::vector<float> target;
+    std::vector<int64_t> span;  // per game: [begin, end) of its text in the buffer it was parsed from (bo_pgn_spans)
 };
 
 static bool pgn_ws(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f' || (c >= 0x1c && c <= 0x1f); }
@@ -253,6 +254,7 @@ static int64_t pgn_parse(bo_pgn_s *p, const char *t, int64_t n, bool final, int6
         std::string fen, variant;
         bool have_fen = false, in_moves = false, any = false, stopped = false, complete = false;
         int status = BO_PGN_OK, depth = 0;
+        int64_t first = -1;  // the first byte the game's text proper starts at: its first tag, word or variation (bo_pgn_spans)
         std::vector<uint32_t> toks;
         std::vector<std::string> com;
         int64_t k = i;
@@ -271,12 +273,13 @@ static int64_t pgn_parse(bo_pgn_s *p, const char *t, int64_t n, bool final, int6
                 k = e + 1 - t;
                 continue;
             }
-            if (c == '(') { depth++; k++; any = true; continue; }
+            if (c == '(') { if (first < 0) first = k; depth++; k++; any = true; continue; }
             if (c == ')') { if (depth) depth--; k++; continue; }
             if (c == '}') { k++; continue; }  // (a stray closing brace)
             if (c == '[' && depth == 0) {
                 if (in_moves) { complete = true; break; }  // the next game's headers: this one ended without a result
                 any = true;
+                if (first < 0) first = k;
                 int64_t q = k + 1;
                 while (q < n && pgn_ws(t[q])) q++;
                 const int64_t n0 = q;
@@ -304,6 +307,7 @@ static int64_t pgn_parse(bo_pgn_s *p, const char *t, int64_t n, bool final, int6
             while (k < n && !pgn_ws(t[k]) && t[k] != '{' && t[k] != '}' && t[k] != '(' && t[k] != ')' && t[k] != ';' && t[k] != '[') k++;
             if (k == w0) { k++; continue; }  // ('[' inside a variation)
             if (k == n && !final) break;      // the word may go on in the next chunk
+            if (first < 0) first = w0;
             any = true;
             in_moves = true;
             if (depth > 0) continue;
@@ -349,6 +353,8 @@ static int64_t pgn_parse(bo_pgn_s *p, const char *t, int64_t n, bool final, int6
             p->target.push_back(ev ? tg : 0.0f);
         }
         p->tok_off.push_back((int32_t)p->tok.size());
+        p->span.push_back(first < 0 ? k : first);  // ('%' lines, ';' comments and blanks in front of the game are not part of it)
+        p->span.push_back(k);
         i = consumed = k;
     }
     return consumed;

@@ -25,7 +25,7 @@ RES_CAP = 256
 POLICY_NONE, POLICY_LOGITS, POLICY_PROBS = 0, 1, 2
 
 STATUS_BITS = {1: "node overflow", 2: "depth overflow", 4: "NaN PUCT score", 8: "ply overflow",
-               16: "illegal action", 32: "leaf cache overflow", 64: "tracker overflow"}
+               16: "illegal action", 32: "leaf cache overflow", 64: "tracker overflow", 128: "position range outside the array"}
 ST_PLY_OVERFLOW, ST_ILLEGAL_ACTION = 8, 16   # per-GAME conditions (the reference aborts that game only); the rest are engine faults
 ST_NODE_OVERFLOW = 1  # reference mode: a fault (the node arrays are sized for the search).  Fast mode: the game's arena was full at an
 #                       expansion or a re-root -- the leaf stayed unexpanded (its value was still backed up) / the subtree that did not
@@ -60,6 +60,23 @@ class BoB1LayerDesc(C.Structure):
 class BoNode(C.Structure):
     _fields_ = [("parent", C.c_int32), ("n_visits", C.c_int32), ("first_child", C.c_int32), ("n_children", C.c_int32),
                 ("q_value", C.c_float), ("prior", C.c_float), ("move", C.c_int32), ("terminal", C.c_int32)]
+
+
+PV_CAP = 16  # BO_PV_CAP
+
+
+class BoAnalysis(C.Structure):  # bo_analysis: one slot's record of bo_analysis_result (32 words)
+    _fields_ = [("terminal", C.c_int32), ("n_legal", C.c_int32), ("total_visits", C.c_int32), ("best_move", C.c_int32),
+                ("root_value", C.c_float), ("played_is_child", C.c_int32), ("played_visits", C.c_int32), ("played_q", C.c_float),
+                ("pv_len", C.c_int32), ("pv", C.c_int32 * PV_CAP), ("phase", C.c_int32), ("status", C.c_int32), ("ply", C.c_int32),
+                ("sims_done", C.c_int32), ("watch", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+ANALYSIS_DTYPE = np.dtype([("terminal", "<i4"), ("n_legal", "<i4"), ("total_visits", "<i4"), ("best_move", "<i4"), ("root_value", "<f4"),
+                           ("played_is_child", "<i4"), ("played_visits", "<i4"), ("played_q", "<f4"), ("pv_len", "<i4"),
+                           ("pv", "<i4", (PV_CAP,)), ("phase", "<i4"), ("status", "<i4"), ("ply", "<i4"), ("sims_done", "<i4"),
+                           ("watch", "<i4"), ("reserved", "<i4", (2,))])  # the same record as a NumPy dtype (a [G, 32] int32 buffer .view()ed)
+PH_IDLE, PH_RUN, PH_DONE = 0, 1, 2
 
 
 class BoHeadWeights(C.Structure):  # bo_head_weights: device addresses of one net's head Linear weights (bo_nn_heads_pair)
@@ -162,6 +179,11 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_pgn_destroy": (None, [C.c_void_p]),
     "bo_san_render": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 7),
     "bo_position_fen": (C.c_int, [C.POINTER(BoPosition), C.c_char_p, C.c_int32]),
+    "bo_games_reset_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bo_search_begin_dev": (C.c_int, [C.c_void_p] * 4),
+    "bo_analysis_result": (C.c_int, [C.c_void_p] * 4),
+    "bo_pgn_after": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 4),
+    "bo_pgn_spans": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "bo_pgn_movetext": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int64,
                                   C.POINTER(C.c_int64)]),
 }
@@ -193,7 +215,7 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 7   # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 8   # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
 
 
@@ -363,6 +385,19 @@ class Engine:
         tc = _i32(cnts if cnts else [0])
         self._check(self.lib.bo_games_reset_ex(self.h, n, _p(s), self._strs(fens, n), self._strs(moves, n), harr, _p(nh),
                                                tarr, _p(tc), _p(off), stream))
+
+    def reset_dev(self, n: int, slots_ptr: int, pos_ptr: int, capacity: int, first_ptr: int, ply_ptr: int, stream: int = 0):
+        """bo_games_reset_dev: slot slots[i] = the game whose ply 0 is entry first[i] (int64) of the position array, at ply ply[i]; every
+        pointer is device memory, nothing waits."""
+        self._check(self.lib.bo_games_reset_dev(self.h, int(n), slots_ptr, pos_ptr, int(capacity), first_ptr, ply_ptr, stream))
+
+    def search_begin_dev(self, want_ptr: int, nn_in_ptr: int, stream: int = 0):
+        """bo_search_begin_dev: every slot with want[g] != 0 (device int32 [G]) whose root is not terminal starts its search."""
+        self._check(self.lib.bo_search_begin_dev(self.h, want_ptr, nn_in_ptr, stream))
+
+    def analysis_result(self, played_ptr: int, out_ptr: int, stream: int = 0):
+        """bo_analysis_result: G records of ANALYSIS_DTYPE into out (device or pinned memory); played: device int32 [G] or 0."""
+        self._check(self.lib.bo_analysis_result(self.h, played_ptr or None, out_ptr, stream))
 
     def root_info(self, stream: int = 0):
         nl, tm, ply = (np.zeros(self.G, dtype=np.int32) for _ in range(3))

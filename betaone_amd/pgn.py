@@ -34,6 +34,7 @@ from . import engine as E
 STATUS_NAMES = ["ok", "variant", "bad_fen", "unsupported", "null_move", "illegal", "ambiguous", "mismatch"]  # BO_PGN_* of include/betaone_engine.h
 POSITION_BYTES = 80  # BO_PGN_POSITION_BYTES
 MAX_READER_THREADS = 16  # host threads a pretraining run may use
+_CLOSE_LOCK = threading.Lock()
 
 
 def pgn_paths(args: Sequence[str]) -> List[str]:
@@ -75,9 +76,10 @@ class ParsedGames:
         return self._exp
 
     def close(self):
-        if self.h:
-            self.lib.bo_pgn_destroy(self.h)
-            self.h = None
+        with _CLOSE_LOCK:  # (the destroy call releases the GIL: two threads must not both find the handle set)
+            h, self.h = self.h, None
+        if h:
+            self.lib.bo_pgn_destroy(h)
 
     def __del__(self):
         try:
@@ -145,14 +147,17 @@ class _Reader:
             try:
                 for p in files:
                     for blk in read_blocks(lib, p, block_tokens, max_games, stats=stats):
+                        handed = False
                         while not self.stop:
                             try:
                                 self.q.put(blk, timeout=0.2)
+                                handed = True  # the block now belongs to whoever takes it from the queue (the consumer, or close()'s drain)
                                 break
                             except queue.Full:
                                 pass
-                        if self.stop:
+                        if not handed:
                             blk.close()
+                        if self.stop:
                             return
             except BaseException as e:  # noqa: BLE001  (re-raised by the consumer)
                 self.err = e

@@ -241,7 +241,13 @@ def write_pgn(fh, games: Sequence, tags=None, device="cuda:0", lib=None, book_pl
     for i, (g, r) in enumerate(zip(games, rendered)):
         gid, positions, moves, terminal = _fields(g)
         t: Dict[str, object] = dict((tags[i] if per_game else tags) or {})
-        result, termination = result_of(gid, positions, terminal, r)
+        given = g.get("result") if isinstance(g, dict) else None  # (an annotated input game keeps its own result token: analyse.py)
+        if given is not None:  # (a foreign game's 1-0 may be a resignation or a flag: only a game handed over as terminal 1 must end in mate)
+            if terminal == 1 and not r.mated():
+                raise ValueError(f"write_pgn: game {gid} ply {len(r.san)}: terminal 1, but the final position is not checkmate")
+            result, termination = str(given), ("unterminated" if given == "*" else "normal")
+        else:
+            result, termination = result_of(gid, positions, terminal, r)
         head = {k: t.pop(k, "?") for k in SEVEN_TAGS}
         if head["Date"] == "?":
             head["Date"] = date
@@ -257,7 +263,7 @@ def write_pgn(fh, games: Sequence, tags=None, device="cuda:0", lib=None, book_pl
         if rv is not None or terminal == 3:
             if sims is None:
                 sims = _default_sims()
-            com = [eval_text(v, sims) for v in rv[:len(moves)]] if rv is not None else None
+            com = [eval_text(v, sims) if v is not None else "" for v in rv[:len(moves)]] if rv is not None else None  # (None: no comment)
             if com is not None and book_plies and book_plies[i]:
                 com = ["book"] * min(book_plies[i], len(com)) + com[book_plies[i]:]
             fin = None

@@ -27,9 +27,10 @@ extern "C" {
 /* Bumped whenever an output size, a struct, or the layout a caller has to produce changes (2: bo_debug_profile (betaone_lab.h) returns
  * [G][BO_PROF_SLOTS = 16] counters, the BO_TOWER_WINOGRAD packed-weight K order for 128 filters is winograd_k_order's;
  * 3: fast-mode arenas are allocated in 128-byte granules of 8 records, bo_fast_stats counts granules; 7: resignation and root values,
- * additions only).  A caller checks
+ * additions only; 8: analysis of games that are on the device -- bo_games_reset_dev, bo_search_begin_dev, bo_analysis_result,
+ * bo_pgn_after, bo_pgn_spans, status bit BO_ST_BAD_RANGE -- additions only).  A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 7
+#define BO_ABI_VERSION 8
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -48,7 +49,8 @@ enum {
 /* per-game status bits reported by bo_engine_status() */
 enum {
     BO_ST_NODE_OVERFLOW = 1, BO_ST_DEPTH_OVERFLOW = 2, BO_ST_NAN_SCORE = 4, BO_ST_PLY_OVERFLOW = 8,
-    BO_ST_ILLEGAL_ACTION = 16, BO_ST_UL_OVERFLOW = 32, BO_ST_TRK_OVERFLOW = 64
+    BO_ST_ILLEGAL_ACTION = 16, BO_ST_UL_OVERFLOW = 32, BO_ST_TRK_OVERFLOW = 64,
+    BO_ST_BAD_RANGE = 128   /* (ABI 8) bo_games_reset_dev: the slot's positions are not inside the array */
 };
 
 enum { BO_POLICY_NONE = 0, BO_POLICY_LOGITS = 1, BO_POLICY_PROBS = 2 };
@@ -593,6 +595,57 @@ int bo_pgn_movetext(int32_t n_plies, const void *san, const uint8_t *state, int3
  * be NULL or empty) is written as one more "{...}" after the last move (e.g. "White resigns").  Same layout rules. */
 int bo_pgn_movetext_text(int32_t n_plies, const void *san, const uint8_t *state, int32_t root_turn, int32_t root_fullmove, const char *text,
                          const int32_t *text_off, const char *final_comment, const char *result, char *out, int64_t cap, int64_t *len_out);
+
+/* ---- (ABI 8, additions) analysis of games that are already on the device: csrc/bo_analyse.h, betaone_amd/analyse.py ----------------
+ * "Here is a file of games, what does the net think of them": one search per position of every game bo_pgn_replay left in HBM.  The
+ * reference has no counterpart (uci.py searches one position a GUI hands it); bo_games_reset sets a slot up from a FEN and UCI move
+ * strings -- text parsing on the host, a serial make_move loop on one lane and a synchronise -- which is the wrong tool for tens of
+ * thousands of roots that are device memory already.  Reference-semantics engines only (BO_E_CONFIG in fast mode).
+ *
+ * bo_games_reset_dev: bo_games_reset (self-play context) for n slots from positions in the ring's format (BO_PGN_POSITION_BYTES each,
+ * what bo_pgn_replay writes): slot slots_dev[i] becomes the game whose ply 0 is entry first_dev[i], at ply ply_dev[i] -- positions
+ * first .. first + ply are copied (64 per pass), the tracker holds each once (the live tracker bo_pgn_sample encodes with), the moves
+ * are recovered from consecutive positions, counters and status are reset, the root is prepared.  ASYNCHRONOUS, and every pointer is
+ * device memory read when the kernel runs: a batch can be set up behind the previous batch's bo_analysis_result with no host wait.
+ * What the host cannot check the kernel does: a range that leaves [0, capacity) gives BO_ST_BAD_RANGE, ply + 1 > max_plies
+ * BO_ST_PLY_OVERFLOW (BO_ST_TRK_OVERFLOW) in the slot's status; such a slot holds an empty game, terminal code -1, and is not searched;
+ * a slot number outside the engine is ignored.  Nothing outside [0, capacity) is read.
+ * bo_search_begin_dev: bo_search_begin decided on the device -- slot g searches when want_dev[g] != 0 and its root is not terminal
+ * (mcts.py:160-162).  No Dirichlet noise: engines with dirichlet_alpha <= 0 only (BO_E_CONFIG otherwise).  Then bo_step as usual.
+ * bo_analysis_result: the result kernel of bo_search_result, then one bo_analysis record per slot into out[G] (device memory, or pinned
+ * device-mapped host memory; each word is stored once).  played_dev [G] (may be NULL): the move the game played from the slot's root
+ * (from | to << 6 | promo << 12, -1 none).  Needs bo_engine_root_values(e, 1) (BO_E_STATE otherwise).  Asynchronous.
+ *   terminal: the root's is_game_over(claim_draw=True) code (0, 1 side to move is mated, 2 draw -- a game that played on past a
+ *     claimable draw has such roots; -1 refused slot); n_legal; phase: 0 idle (the root was not searched), 1 the search is still
+ *     running (step once more), 2 finished -- the fields below are filled only then; status: the slot's BO_ST_* bits; ply; sims_done;
+ *     watch: the word(s) named to bo_engine_watch as the result kernel saw them (non-zero: the evaluations are invalid).
+ *   total_visits, best_move: bo_search_result's.  root_value: the root's q_value (side to move).  played_*: whether played_dev[g] is a
+ *     child of the root, its visit count and q_value as the tree holds it (the child's own side's view); 0 when it is no child.
+ *   pv: the principal variation, at most BO_PV_CAP moves: from the root, at each node the child with the most visits, the first
+ *     maximum in child order (at the root in legal-move order, so pv[0] == best_move); it ends at a node without children or whose
+ *     best child has no visit.  total_visits == 0 gives pv_len 0.
+ * bo_pgn_after: for n entries idx_dev[i] (device int64) of a ring: move_out_dev[i] = the move act_dev names at that position (-1: not
+ * decodable, or the entry is outside [0, capacity)), pos_out_dev[i] (BO_PGN_POSITION_BYTES each) = the position after it; either
+ * output may be NULL.  The position after a game's last move is not in the ring.  Asynchronous.
+ * bo_pgn_spans: host.  begin / end [games]: the bytes [begin, end) of each parsed game in the text given to bo_pgn_parse (tag section
+ * and movetext, from its first tag or word: '%' lines and ';' comments in front of it are outside), so that a writer can keep the
+ * game's tags.  The offsets count from the `text` of that one call: a caller that parses a file in chunks adds its own offset. */
+#define BO_PV_CAP 16
+typedef struct bo_analysis {
+    int32_t terminal, n_legal, total_visits, best_move;
+    float root_value;
+    int32_t played_is_child, played_visits;
+    float played_q;
+    int32_t pv_len, pv[BO_PV_CAP];
+    int32_t phase, status, ply, sims_done, watch, reserved[2];
+} bo_analysis;
+int bo_games_reset_dev(bo_engine *e, int n, const int32_t *slots_dev, const void *pos_dev, int64_t capacity, const int64_t *first_dev,
+                       const int32_t *ply_dev, void *stream);
+int bo_search_begin_dev(bo_engine *e, const int32_t *want_dev, float *nn_in_dev, void *stream);
+int bo_analysis_result(bo_engine *e, const int32_t *played_dev, bo_analysis *out, void *stream);
+int bo_pgn_after(const void *pos_dev, const int32_t *act_dev, int64_t capacity, int32_t n, const int64_t *idx_dev, void *pos_out_dev,
+                 int32_t *move_out_dev, void *stream);
+int bo_pgn_spans(const bo_pgn *p, int64_t *begin, int64_t *end);
 
 #ifdef __cplusplus
 }
