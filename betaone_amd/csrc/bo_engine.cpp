@@ -1219,9 +1219,10 @@ struct bo_replay_s {
     int64_t cap = 0, head = 0, n_records = 0;
     DPos *pos = nullptr;
     int *rep = nullptr, *pi_n = nullptr, *pi_idx = nullptr, *s_slot = nullptr, *s_k = nullptr;
-    float *pi_val = nullptr, *z = nullptr;
+    float *pi_val = nullptr, *z = nullptr, *q = nullptr;   // q: the root value beside z (z itself for a record without one)
+    int64_t n_valued = 0;                                 // resident records that carry a root value
     int s_cap = 0;
-    struct Game { int64_t start; int32_t n_rec; int32_t game_id; };
+    struct Game { int64_t start; int32_t n_rec; int32_t game_id; bool valued; };
     std::deque<Game> games;
     std::vector<int64_t> prefix;   // prefix[i] = records of games[0..i) (rebuilt after an add)
     std::vector<int> h_slot, h_k;
@@ -1239,8 +1240,9 @@ extern "C" int bo_replay_create(int64_t capacity_positions, int pi_width, int de
     if (!rc) rc = rt_malloc((void **)&r->pi_idx, n * (size_t)pi_width * 4);
     if (!rc) rc = rt_malloc((void **)&r->pi_val, n * (size_t)pi_width * 4);
     if (!rc) rc = rt_malloc((void **)&r->z, n * 4);
+    if (!rc) rc = rt_malloc((void **)&r->q, n * 4);
     if (rc) {
-        rt_free(r->pos); rt_free(r->rep); rt_free(r->pi_n); rt_free(r->pi_idx); rt_free(r->pi_val); rt_free(r->z);
+        rt_free(r->pos); rt_free(r->rep); rt_free(r->pi_n); rt_free(r->pi_idx); rt_free(r->pi_val); rt_free(r->z); rt_free(r->q);
         delete r;
         return fail(BO_E_HIP, std::string("bo_replay_create: ") + rt_errstr(rc));
     }
@@ -1250,7 +1252,7 @@ extern "C" int bo_replay_create(int64_t capacity_positions, int pi_width, int de
 
 extern "C" void bo_replay_destroy(bo_replay *r) {
     if (!r) return;
-    rt_free(r->pos); rt_free(r->rep); rt_free(r->pi_n); rt_free(r->pi_idx); rt_free(r->pi_val); rt_free(r->z); rt_free(r->s_slot); rt_free(r->s_k);
+    rt_free(r->pos); rt_free(r->rep); rt_free(r->pi_n); rt_free(r->pi_idx); rt_free(r->pi_val); rt_free(r->z); rt_free(r->q); rt_free(r->s_slot); rt_free(r->s_k);
     delete r;
 }
 
@@ -1258,17 +1260,24 @@ extern "C" void bo_replay_destroy(bo_replay *r) {
 // final position), pi of record i = entries pi_ptr[i] .. pi_ptr[i + 1] of (pi_idx, pi_val), z[i] as the reference stores it
 // (self_play.py:202: the outcome from the point of view of the side to move, sign of zero included).  Evicts the oldest games that
 // are in the way; *evicted_records (may be NULL) = how many records that cost.  Synchronises `stream` (host staging is freed).
-extern "C" int bo_replay_add_game(bo_replay *r, int32_t game_id, const bo_position *positions, int32_t n_records, const int32_t *pi_ptr,
-                                  const int32_t *pi_idx, const float *pi_val, const float *z, int64_t *evicted_records, void *stream) {
-    if (!r || !positions || n_records < 0 || (n_records && (!pi_ptr || !pi_idx || !pi_val || !z))) return fail(BO_E_ARG, "bo_replay_add_game: bad arguments");
+// root_value[i] (NULL: the game has none): the root's q_value after the search at ply i, from the side to move's point of view like
+// z[i]; without it the slot's q is z[i] and the game's records do not count as carrying a value.
+static int replay_add_game(const char *who, bo_replay *r, int32_t game_id, const bo_position *positions, int32_t n_records, const int32_t *pi_ptr,
+                           const int32_t *pi_idx, const float *pi_val, const float *z, const float *root_value, int64_t *evicted_records,
+                           void *stream) {
+    if (!r || !positions || n_records < 0 || (n_records && (!pi_ptr || !pi_idx || !pi_val || !z))) return fail(BO_E_ARG, std::string(who) + ": bad arguments");
     if (evicted_records) *evicted_records = 0;
     if (n_records == 0) return BO_OK;  // (a start position that was already over: no examples, self_play.py:101)
     const int64_t need = (int64_t)n_records + 1;
-    if (need > r->cap) return fail(BO_E_ARG, "bo_replay_add_game: the game is longer than the buffer");
+    if (need > r->cap) return fail(BO_E_ARG, std::string(who) + ": the game is longer than the buffer");
     for (int i = 0; i < n_records; i++)
-        if (pi_ptr[i + 1] - pi_ptr[i] > r->W || pi_ptr[i + 1] < pi_ptr[i]) return fail(BO_E_ARG, "bo_replay_add_game: a pi has more entries than the buffer's pi_width");
+        if (pi_ptr[i + 1] - pi_ptr[i] > r->W || pi_ptr[i + 1] < pi_ptr[i]) return fail(BO_E_ARG, std::string(who) + ": a pi has more entries than the buffer's pi_width");
     int64_t lost = 0;
-    auto evict_front = [&]() { lost += r->games.front().n_rec; r->n_records -= r->games.front().n_rec; r->games.pop_front(); };
+    auto evict_front = [&]() {
+        const auto &g = r->games.front();
+        lost += g.n_rec; r->n_records -= g.n_rec; r->n_valued -= g.valued ? g.n_rec : 0;
+        r->games.pop_front();
+    };
     if (r->head + need > r->cap) {  // does not fit behind the newest game: the games still living in that tail go, the ring comes round
         while (!r->games.empty() && r->games.front().start >= r->head) evict_front();
         r->head = 0;
@@ -1278,11 +1287,12 @@ extern "C" int bo_replay_add_game(bo_replay *r, int32_t game_id, const bo_positi
     std::vector<DPos> hp(n);
     for (size_t i = 0; i < n; i++) hp[i] = from_abi(positions[i]);
     std::vector<int> hn(n, 0), hi(n * (size_t)r->W, 0);
-    std::vector<float> hv(n * (size_t)r->W, 0.0f), hz(n, 0.0f);
+    std::vector<float> hv(n * (size_t)r->W, 0.0f), hz(n, 0.0f), hq(n, 0.0f);
     for (int i = 0; i < n_records; i++) {
         hn[i] = pi_ptr[i + 1] - pi_ptr[i];
         for (int e = 0; e < hn[i]; e++) { hi[(size_t)i * r->W + e] = pi_idx[pi_ptr[i] + e]; hv[(size_t)i * r->W + e] = pi_val[pi_ptr[i] + e]; }
         hz[i] = z[i];
+        hq[i] = root_value ? root_value[i] : z[i];
     }
     const size_t o = (size_t)r->head;
     int rc = rt_h2d(r->pos + o, hp.data(), n * sizeof(DPos), stream);
@@ -1290,21 +1300,41 @@ extern "C" int bo_replay_add_game(bo_replay *r, int32_t game_id, const bo_positi
     if (!rc) rc = rt_h2d(r->pi_idx + o * r->W, hi.data(), n * (size_t)r->W * 4, stream);
     if (!rc) rc = rt_h2d(r->pi_val + o * r->W, hv.data(), n * (size_t)r->W * 4, stream);
     if (!rc) rc = rt_h2d(r->z + o, hz.data(), n * 4, stream);
+    if (!rc) rc = rt_h2d(r->q + o, hq.data(), n * 4, stream);
     if (!rc) rc = RT_LAUNCH(bo_k_replay_counts, (int)need, stream, (const DPos *)(r->pos + o), (int)need, r->rep + o);
     const int rc2 = rt_sync(stream);
-    if (rc || rc2) return fail(BO_E_HIP, std::string("bo_replay_add_game: ") + rt_errstr(rc ? rc : rc2));
-    r->games.push_back({r->head, n_records, game_id});
+    if (rc || rc2) return fail(BO_E_HIP, std::string(who) + ": " + rt_errstr(rc ? rc : rc2));
+    r->games.push_back({r->head, n_records, game_id, root_value != nullptr});
     r->head += need;
     r->n_records += n_records;
+    r->n_valued += root_value ? n_records : 0;
     r->prefix.clear();
     if (evicted_records) *evicted_records = lost;
     return BO_OK;
+}
+
+extern "C" int bo_replay_add_game(bo_replay *r, int32_t game_id, const bo_position *positions, int32_t n_records, const int32_t *pi_ptr,
+                                  const int32_t *pi_idx, const float *pi_val, const float *z, int64_t *evicted_records, void *stream) {
+    return replay_add_game("bo_replay_add_game", r, game_id, positions, n_records, pi_ptr, pi_idx, pi_val, z, nullptr, evicted_records, stream);
+}
+
+extern "C" int bo_replay_add_game_values(bo_replay *r, int32_t game_id, const bo_position *positions, int32_t n_records, const int32_t *pi_ptr,
+                                         const int32_t *pi_idx, const float *pi_val, const float *z, const float *root_value,
+                                         int64_t *evicted_records, void *stream) {
+    return replay_add_game("bo_replay_add_game_values", r, game_id, positions, n_records, pi_ptr, pi_idx, pi_val, z, root_value, evicted_records,
+                           stream);
 }
 
 extern "C" int bo_replay_size(bo_replay *r, int64_t *n_records, int64_t *n_games) {
     if (!r) return fail(BO_E_ARG, "null handle");
     if (n_records) *n_records = r->n_records;
     if (n_games) *n_games = (int64_t)r->games.size();
+    return BO_OK;
+}
+
+extern "C" int bo_replay_values(bo_replay *r, int64_t *n_records_with_value) {
+    if (!r || !n_records_with_value) return fail(BO_E_ARG, "bo_replay_values: bad arguments");
+    *n_records_with_value = r->n_valued;
     return BO_OK;
 }
 
@@ -1360,6 +1390,20 @@ extern "C" int bo_replay_sample_sparse(bo_replay *r, int32_t n, const int64_t *r
     RT(RT_LAUNCH(bo_k_replay_encode_sparse, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
                  (const float *)r->pi_val, (const float *)r->z, r->W, (const int *)r->s_slot, (const int *)r->s_k, states_dev, (int *)pi_idx_dev,
                  pi_val_dev, z_dev));
+    RT(rt_sync(stream));
+    return BO_OK;
+}
+
+// bo_replay_sample_sparse with the records' root values: q [n] beside z [n], from the same launch.
+extern "C" int bo_replay_sample_sparse_q(bo_replay *r, int32_t n, const int64_t *record_index, float *states_dev, int32_t *pi_idx_dev,
+                                         float *pi_val_dev, float *z_dev, float *q_dev, void *stream) {
+    if (!r || n < 1 || !record_index || !states_dev || !pi_idx_dev || !pi_val_dev || !z_dev || !q_dev)
+        return fail(BO_E_ARG, "bo_replay_sample_sparse_q: bad arguments");
+    const int rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_sparse_q");
+    if (rc) return rc;
+    RT(RT_LAUNCH(bo_k_replay_encode_sparse_q, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
+                 (const float *)r->pi_val, (const float *)r->z, (const float *)r->q, r->W, (const int *)r->s_slot, (const int *)r->s_k, states_dev,
+                 (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev));
     RT(rt_sync(stream));
     return BO_OK;
 }
@@ -1652,6 +1696,48 @@ extern "C" int bo_train_loss_backward(int32_t n, int32_t W, const void *logits_d
     });
     if (!ok) return fail(BO_E_CONFIG, "bo_train_loss_backward: unsupported dtype");
     if (rc) return fail(BO_E_HIP, std::string("bo_train_loss_backward: ") + rt_errstr(rc));
+    return BO_OK;
+}
+
+// The same with the value target t = (1 - a) z + a q (bo_train.h): q [n] and the mix a (one float32) on the device; row_stats [n,6].
+extern "C" int bo_train_loss_forward_mix(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev,
+                                         int32_t value_dtype, const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev,
+                                         const float *q_dev, const float *mix_dev, float *row_stats_dev, float *loss5_dev, void *stream) {
+    int rc = train_loss_args("bo_train_loss_forward_mix", n, W, logits_dev, value_dev, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev);
+    if (rc) return rc;
+    if (!q_dev || !mix_dev || !loss5_dev) return fail(BO_E_ARG, "bo_train_loss_forward_mix: bad arguments");
+    bool ok = false;
+    train_dtype(logits_dtype, [&](auto *tl) {
+        ok = train_dtype(value_dtype, [&](auto *tv) {
+            BO_TRAIN_TYPES(tl, tv);
+            rc = RT_LAUNCH((bo_k_loss_fwd_mix<TL, TV>), n, stream, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
+                           pi_val_dev, z_dev, q_dev, mix_dev, row_stats_dev);
+        });
+    });
+    if (!ok) return fail(BO_E_CONFIG, "bo_train_loss_forward_mix: unsupported dtype");
+    if (!rc) rc = RT_LAUNCH(bo_k_loss_reduce_mix, 1, stream, (int)n, (const float *)row_stats_dev, mix_dev, loss5_dev);
+    if (rc) return fail(BO_E_HIP, std::string("bo_train_loss_forward_mix: ") + rt_errstr(rc));
+    return BO_OK;
+}
+
+extern "C" int bo_train_loss_backward_mix(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev,
+                                          int32_t value_dtype, const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev,
+                                          const float *q_dev, const float *mix_dev, const float *row_stats_dev, const float *grad_out_dev,
+                                          void *dlogits_dev, void *dvalue_dev, void *stream) {
+    int rc = train_loss_args("bo_train_loss_backward_mix", n, W, logits_dev, value_dev, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev);
+    if (rc) return rc;
+    if (!q_dev || !mix_dev || !grad_out_dev || !dlogits_dev || !dvalue_dev) return fail(BO_E_ARG, "bo_train_loss_backward_mix: bad arguments");
+    bool ok = false;
+    train_dtype(logits_dtype, [&](auto *tl) {
+        ok = train_dtype(value_dtype, [&](auto *tv) {
+            BO_TRAIN_TYPES(tl, tv);
+            rc = RT_LAUNCH((bo_k_loss_bwd_mix<TL, TV>), n, stream, (int)n, (int)W, (const TL *)logits_dev, (const TV *)value_dev,
+                           (const int *)pi_idx_dev, pi_val_dev, z_dev, q_dev, mix_dev, row_stats_dev, grad_out_dev, (TL *)dlogits_dev,
+                           (TV *)dvalue_dev);
+        });
+    });
+    if (!ok) return fail(BO_E_CONFIG, "bo_train_loss_backward_mix: unsupported dtype");
+    if (rc) return fail(BO_E_HIP, std::string("bo_train_loss_backward_mix: ") + rt_errstr(rc));
     return BO_OK;
 }
 

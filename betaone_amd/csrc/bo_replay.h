@@ -13,6 +13,9 @@
 //                        scalar planes, dense pi row (zero fill + scatter), z
 //   bo_k_replay_encode_sparse  the same planes and z, pi as the record keeps it ([W] indices and values): for the sparse-target
 //                        loss of bo_train.h, which never needs the dense row
+//   bo_k_replay_encode_sparse_q  the same launch with the record's root value q beside z (bo_train.h: the value target as a mix of the
+//                        two).  A slot keeps one float32 q next to its z: the search's root value at that ply from the side to
+//                        move's point of view, like z -- or z itself where the game was recorded without root values.
 #pragma once
 #include "bo_tree.h"
 
@@ -60,9 +63,10 @@ BO_KERNEL void bo_k_replay_encode(const DPos *pos, const int *rep, const int *pi
 }
 
 // the same sample with its pi as stored: out_idx / out_val [n, W], the record's entries first, then (-1, 0) in the unused slots
-BO_KERNEL void bo_k_replay_encode_sparse(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val,
-                                         const float *z, int W, const int *s_slot, const int *s_k, float *states, int *out_idx,
-                                         float *out_val, float *zs) {
+template <bool WITH_Q>
+BO_DEV void replay_encode_sparse(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val, const float *z,
+                                 const float *q, int W, const int *s_slot, const int *s_k, float *states, int *out_idx, float *out_val,
+                                 float *zs, float *qs) {
     const int b = bo_block(), s = bo_lane();
     const int slot = s_slot[b];
     replay_planes(states, b, pos, rep, slot, s_k[b]);
@@ -72,5 +76,18 @@ BO_KERNEL void bo_k_replay_encode_sparse(const DPos *pos, const int *rep, const 
         out_idx[(size_t)b * W + e] = used ? pi_idx[(size_t)slot * W + e] : -1;
         out_val[(size_t)b * W + e] = used ? pi_val[(size_t)slot * W + e] : 0.0f;
     }
-    if (s == 0) zs[b] = z[slot];
+    if (s == 0) {
+        zs[b] = z[slot];
+        if (WITH_Q) qs[b] = q[slot];
+    }
+}
+BO_KERNEL void bo_k_replay_encode_sparse(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val,
+                                         const float *z, int W, const int *s_slot, const int *s_k, float *states, int *out_idx,
+                                         float *out_val, float *zs) {
+    replay_encode_sparse<false>(pos, rep, pi_n, pi_idx, pi_val, z, nullptr, W, s_slot, s_k, states, out_idx, out_val, zs, nullptr);
+}
+BO_KERNEL void bo_k_replay_encode_sparse_q(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val,
+                                           const float *z, const float *q, int W, const int *s_slot, const int *s_k, float *states,
+                                           int *out_idx, float *out_val, float *zs, float *qs) {
+    replay_encode_sparse<true>(pos, rep, pi_n, pi_idx, pi_val, z, q, W, s_slot, s_k, states, out_idx, out_val, zs, qs);
 }

@@ -26,11 +26,22 @@
 // -inf has max -inf, x - max NaN, and a NaN gradient throughout).  A row with no valid entries adds 0 to the policy loss and gets
 // a zero policy gradient.  Entries whose index is not an action (-1 or anything else outside 0..4671) are skipped, values
 // included; an action twice in a row is not defined.
+//
+// The value head on a mix of the game's outcome and the search's root value (bo_k_loss_fwd_mix / _reduce_mix / _bwd_mix):
+//   t_b = (1 - a) z_b + a q_b,   value_mix = (1/B) sum_b (v_b - t_b)^2,   dvalue[b] = 2/B (v_b - t_b) g_v
+// q_b is the record's root value (bo_replay.h; q = z where the record has none), a one float32 ON THE DEVICE, read by the kernels as
+// grad_out is: a schedule changes it under a captured step.  z and q are both from the side to move's point of view: no sign flips.
+// a == 0 SELECTS t = z (no 0 * q: q may be NaN, and z = -0.0 has to stay -0.0), so the policy term, the value term and both
+// gradients are then the bits of the kernels above; a outside [0, 1] or NaN is not clamped: every entry of loss5 and dvalue are NaN.
+// The same wave-per-row layout and the same operations in the same order on the policy side.  Per row
+// [max, log sum exp, policy term, (v - t)^2, (v - z)^2, (v - q)^2]; loss5 = [policy + value_mix, policy, value_mix, value_vs_z,
+// value_vs_q], the last two diagnostics with no gradient (grad_out stays [3]).
 #pragma once
 #include "bo_wave.h"
 
 #define BO_LOSS_PER_LANE (BO_NUM_ACTIONS / 64)   // 73
 #define BO_LOSS_STATS 4                          // row_stats floats per row
+#define BO_LOSS_STATS_MIX 6                      // ... of the mix entry points
 
 #if defined(BO_WAVE_EMU)
 #define BO_LOSS_KERNEL static
@@ -130,4 +141,117 @@ BO_LOSS_KERNEL void bo_k_loss_bwd(int n, int W, const TL *logits, const TV *valu
         bo_st_f(dr + a, sm * sgb - t * gb);
     }
     if (s == 0) bo_st_f(dvalue + b, (2.0f / (float)n) * (bo_ld_f(value + b) - z[b]) * gv);
+}
+
+// ---- the value target as a mix of z and the root value q (header comment) -----------------------------------------------------------
+// The policy side of the kernels above as two functions, for the mix kernels.  The kernels above keep their own text: their
+// instances are compiled as they always were (VGPR counts are part of what profiles/ records), and a mix of 0 is checked against
+// them bit for bit (tests/value_mix_cases.py).
+//
+// A row's logits once through the wave: st[0..2] = max, log sum exp(x - max), the policy term (written by lane 0).
+template <typename TL>
+BO_DEV void bo_loss_row_policy(int W, const TL *xr, const int *ix, const float *vx, float *st) {
+    const int s = bo_lane();
+    float x[BO_LOSS_PER_LANE];
+    float m = -__builtin_inff();
+    bool nan = false, nonfinite = false;
+    for (int j = 0; j < BO_LOSS_PER_LANE; j++) {
+        x[j] = bo_ld_f(xr + s + 64 * j);
+        nan |= x[j] != x[j];
+        nonfinite |= !(x[j] - x[j] == 0.0f);
+        m = x[j] > m ? x[j] : m;
+    }
+    float mx = bo_wave_max_f(m);
+    if (bo_ballot(nan)) mx = __builtin_nanf("");  // (PyTorch's max propagates NaN; the butterfly compare would drop it)
+    float se = 0.0f;
+    for (int j = 0; j < BO_LOSS_PER_LANE; j++) se += expf(x[j] - mx);
+    const float logsum = logf(bo_wave_sum_f(se));
+    float acc = 0.0f;
+    for (int e = s; e < W; e += 64) {
+        const int i = ix[e];
+        if (bo_loss_valid(i)) acc += vx[e] * ((bo_ld_f(xr + i) - mx) - logsum);
+    }
+    acc = bo_wave_sum_f(acc);
+    const bool bad = bo_ballot(nonfinite) != 0;
+    if (s == 0) {
+        st[0] = mx;
+        st[1] = logsum;
+        st[2] = bad ? __builtin_nanf("") : -acc;
+    }
+}
+
+// dlogits of one row from its stored statistics; gp = the gradient that reaches the policy term
+template <typename TL>
+BO_DEV void bo_loss_row_dlogits(int n, int W, const TL *xr, TL *dr, const int *ix, const float *vx, float gp, float mx, float logsum) {
+    const int s = bo_lane();
+    const float gb = gp / (float)n;
+    float S = 0.0f;
+    for (int e = 0; e < W; e++) S += bo_loss_valid(ix[e]) ? vx[e] : 0.0f;  // (pi is normalised in float32: S need not be 1)
+    const float sgb = S * gb;
+    for (int j = 0; j < BO_LOSS_PER_LANE; j++) {
+        const int a = s + 64 * j;
+        float t = 0.0f;
+        for (int e = 0; e < W; e++) t = ix[e] == a ? vx[e] : t;  // one writer per address: the lane of the action looks it up
+        const float sm = expf((bo_ld_f(xr + a) - mx) - logsum);
+        bo_st_f(dr + a, sm * sgb - t * gb);
+    }
+}
+
+BO_DEV bool bo_mix_ok(float a) { return a >= 0.0f && a <= 1.0f; }  // (false for NaN)
+BO_DEV float bo_mix_target(float a, float z, float q) {
+    if (a == 0.0f) return z;                        // a select, not 0 * q
+    if (!bo_mix_ok(a)) return __builtin_nanf("");
+    return (1.0f - a) * z + a * q;
+}
+
+template <typename TL, typename TV>
+BO_LOSS_KERNEL void bo_k_loss_fwd_mix(int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z,
+                                      const float *q, const float *mix, float *row_stats) {
+    const int b = bo_block();
+    float *st = row_stats + (size_t)b * BO_LOSS_STATS_MIX;
+    bo_loss_row_policy(W, logits + (size_t)b * BO_NUM_ACTIONS, pi_idx + (size_t)b * W, pi_val + (size_t)b * W, st);
+    if (bo_lane() == 0) {
+        const float v = bo_ld_f(value + b);
+        const float d = v - bo_mix_target(mix[0], z[b], q[b]), dz = v - z[b], dq = v - q[b];
+        st[3] = d * d;
+        st[4] = dz * dz;
+        st[5] = dq * dq;
+    }
+}
+
+// bo_k_loss_reduce's order over five columns (columns 2 and 3 are summed exactly as there)
+BO_LOSS_KERNEL void bo_k_loss_reduce_mix(int n, const float *row_stats, const float *mix, float *loss5) {
+    const int s = bo_lane();
+    float p = 0.0f, v = 0.0f, vz = 0.0f, vq = 0.0f;
+    for (int b = s; b < n; b += 64) {
+        const float *st = row_stats + (size_t)b * BO_LOSS_STATS_MIX;
+        p += st[2];
+        v += st[3];
+        vz += st[4];
+        vq += st[5];
+    }
+    p = bo_wave_sum_f(p);
+    v = bo_wave_sum_f(v);
+    vz = bo_wave_sum_f(vz);
+    vq = bo_wave_sum_f(vq);
+    if (s == 0) {
+        const float pl = p / (float)n, vl = v / (float)n;
+        const bool ok = bo_mix_ok(mix[0]);
+        const float nan = __builtin_nanf("");
+        loss5[0] = ok ? pl + vl : nan;
+        loss5[1] = ok ? pl : nan;
+        loss5[2] = vl;                               // (NaN already: every row's target is)
+        loss5[3] = ok ? vz / (float)n : nan;
+        loss5[4] = ok ? vq / (float)n : nan;
+    }
+}
+
+template <typename TL, typename TV>
+BO_LOSS_KERNEL void bo_k_loss_bwd_mix(int n, int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z,
+                                      const float *q, const float *mix, const float *row_stats, const float *grad3, TL *dlogits, TV *dvalue) {
+    const int b = bo_block();
+    const float gp = grad3[0] + grad3[1], gv = grad3[0] + grad3[2];  // (grad3 is the gradient of loss5[0:3]: the diagnostics have none)
+    bo_loss_row_dlogits(n, W, logits + (size_t)b * BO_NUM_ACTIONS, dlogits + (size_t)b * BO_NUM_ACTIONS, pi_idx + (size_t)b * W,
+                        pi_val + (size_t)b * W, gp, row_stats[(size_t)b * BO_LOSS_STATS_MIX], row_stats[(size_t)b * BO_LOSS_STATS_MIX + 1]);
+    if (bo_lane() == 0) bo_st_f(dvalue + b, (2.0f / (float)n) * (bo_ld_f(value + b) - bo_mix_target(mix[0], z[b], q[b])) * gv);
 }

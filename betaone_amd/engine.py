@@ -133,6 +133,10 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_replay_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "bo_replay_sample": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bo_replay_sample_sparse": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)] + [C.c_void_p] * 5),
+    "bo_replay_add_game_values": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(BoPosition), C.c_int32, _I32P, _I32P, _F32P, _F32P, _F32P,
+                                            C.POINTER(C.c_int64), C.c_void_p]),
+    "bo_replay_values": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "bo_replay_sample_sparse_q": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)] + [C.c_void_p] * 6),
     "bo_replay_destroy": (None, [C.c_void_p]),
     "bo_nn_b1_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "bo_nn_b1_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -171,6 +175,8 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_match_select": (C.c_int, [C.c_void_p] * 4),
     "bo_train_loss_forward": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6),
     "bo_train_loss_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8),
+    "bo_train_loss_forward_mix": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8),
+    "bo_train_loss_backward_mix": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 10),
     "bo_pgn_parse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]),
     "bo_pgn_size": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int64)] * 3),
     "bo_pgn_export": (C.c_int, [C.c_void_p, _I32P, _I32P, C.c_void_p, C.c_void_p, _I32P, _F32P]),
@@ -215,7 +221,7 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 8   # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 9   # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
 
 

@@ -312,8 +312,16 @@ class GpuReplayBuffer:
         self._check(self.lib.bo_replay_size(self.h, C.byref(n), C.byref(g)))
         return int(g.value)
 
+    @property
+    def n_with_values(self) -> int:
+        """Resident records that carry a root value (games added with root_values: BOG2 records, FinishedGame.root_values)."""
+        n = C.c_int64()
+        self._check(self.lib.bo_replay_values(self.h, C.byref(n)))
+        return int(n.value)
+
     def add(self, games: Sequence) -> int:
-        """Add finished games (FinishedGame objects, packed bytes, or unpack_games dicts); returns the records evicted to make room."""
+        """Add finished games (FinishedGame objects, packed bytes, or unpack_games dicts); returns the records evicted to make room.
+        A game's root_values (one per ply, side to move) are kept beside z for batch_sparse_q; a game without them keeps q = z."""
         lost = 0
         for g in games:
             if isinstance(g, (bytes, bytearray)):
@@ -331,9 +339,15 @@ class GpuReplayBuffer:
             out = np.float32(g["outcome"])
             z = np.array([out if g["positions"][i].turn == 1 else -out for i in range(n)], dtype=np.float32)  # self_play.py:202
             ev = C.c_int64(0)
-            self._check(self.lib.bo_replay_add_game(self.h, int(g["game_id"]), g["positions"], n, ptr.ctypes.data_as(E._I32P),
-                                                    np.ascontiguousarray(idx).ctypes.data_as(E._I32P), np.ascontiguousarray(val).ctypes.data_as(E._F32P),
-                                                    z.ctypes.data_as(E._F32P), C.byref(ev), self._stream()))
+            rv = g.get("root_values")
+            if rv is not None:
+                rv = np.ascontiguousarray(rv, dtype=np.float32)
+                if rv.shape != (n,):
+                    raise ValueError(f"GpuReplayBuffer.add: game {g['game_id']}: {rv.size} root values for {n} plies")
+            self._check(self.lib.bo_replay_add_game_values(self.h, int(g["game_id"]), g["positions"], n, ptr.ctypes.data_as(E._I32P),
+                                                           np.ascontiguousarray(idx).ctypes.data_as(E._I32P),
+                                                           np.ascontiguousarray(val).ctypes.data_as(E._F32P), z.ctypes.data_as(E._F32P),
+                                                           rv.ctypes.data_as(E._F32P) if rv is not None else None, C.byref(ev), self._stream()))
             lost += int(ev.value)
         self.n_evicted += lost
         return lost
@@ -360,22 +374,38 @@ class GpuReplayBuffer:
                                                      val.data_ptr(), zs.data_ptr(), self._stream()))
         return states, idx, val, zs
 
+    def batch_sparse_q(self, record_index) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """batch_sparse plus the records' root values q [n,1] (the search's value of the position for the side to move, as z is the
+        game's; q == z for a record without one) for train.sparse_policy_value_loss_mix.  One launch writes all five."""
+        q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
+        n, W = int(q.size), self.pi_width
+        kw = dict(dtype=torch.float32, device=self.device)
+        states, zs, qs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw), torch.empty((n, 1), **kw)
+        idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
+        self._check(self.lib.bo_replay_sample_sparse_q(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), states.data_ptr(), idx.data_ptr(),
+                                                       val.data_ptr(), zs.data_ptr(), qs.data_ptr(), self._stream()))
+        return states, idx, val, zs, qs
+
     def sample(self, batch_size: int, rng: Optional[np.random.Generator] = None):
         rng = rng if rng is not None else np.random.default_rng()
         return self.batch(rng.integers(0, len(self), size=int(batch_size)))
 
-    def loader(self, batch_size: int, steps: Optional[int] = None, seed: Optional[int] = None, shuffle: bool = True, sparse: bool = False):
+    def loader(self, batch_size: int, steps: Optional[int] = None, seed: Optional[int] = None, shuffle: bool = True, sparse: bool = False,
+               with_q: bool = False):
         """An iterable with DataLoader's contract for train_network (train.py:252: `for states, t_policies, t_values in dataloader`):
         one epoch over the resident records in a random order (shuffle=True, the reference's DataLoader(shuffle=True)), or `steps` batches
         drawn with replacement.  Batches are made on the buffer's device; the loop's `.to(config.DEVICE)` finds them there.
-        sparse=True: the same batches as batch_sparse's (states, pi_idx, pi_val, values)."""
-        return _ReplayLoader(self, int(batch_size), steps, seed, shuffle, sparse)
+        sparse=True: the same batches as batch_sparse's (states, pi_idx, pi_val, values); with_q=True (sparse only): batch_sparse_q's
+        five-tuples, the same records in the same order."""
+        if with_q and not sparse:
+            raise ValueError("loader: with_q needs sparse=True (the dense sampler has no root values)")
+        return _ReplayLoader(self, int(batch_size), steps, seed, shuffle, sparse, with_q)
 
 
 class _ReplayLoader:
-    def __init__(self, buf: GpuReplayBuffer, batch_size: int, steps, seed, shuffle, sparse=False):
+    def __init__(self, buf: GpuReplayBuffer, batch_size: int, steps, seed, shuffle, sparse=False, with_q=False):
         self.buf, self.batch_size, self.steps, self.seed, self.shuffle = buf, batch_size, steps, seed, shuffle
-        self.make = buf.batch_sparse if sparse else buf.batch
+        self.make = buf.batch_sparse_q if with_q else buf.batch_sparse if sparse else buf.batch
 
     def __len__(self) -> int:
         return self.steps if self.steps is not None else (len(self.buf) + self.batch_size - 1) // self.batch_size

@@ -7,8 +7,10 @@ the loss is a pair of HIP kernels that read that sparse target (csrc/bo_train.h)
 backward passes are PyTorch's (MIOpen); only the loss and its gradient are hand-written.
 
     loss, p_loss, v_loss = sparse_policy_value_loss(logits, value, pi_idx, pi_val, z)     # train.calculate_loss, sparse target
+    loss, p_loss, v_mix, v_z, v_q = sparse_policy_value_loss_mix(logits, value, pi_idx, pi_val, z, q, mix)   # value target (1-mix) z + mix q
 
     python -m betaone_amd.train --iteration 3 --data-dir data --save-dir checkpoints --candidate cand.pth
+    python -m betaone_amd.train --value-mix 0.5 ...     # records of selfplay_main --record-values, or of a run with resignation
     python -m betaone_amd.match checkpoints/best_model.pth cand.pth --promote checkpoints/best_model.pth
 """
 from __future__ import annotations
@@ -31,6 +33,7 @@ from . import records as R
 
 DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # BO_DTYPE_* of include/betaone_engine.h
 ROW_STATS = 4
+ROW_STATS_MIX = 6
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -93,6 +96,62 @@ def sparse_policy_value_loss(logits, value, pi_idx, pi_val, z):
     return loss3[0], loss3[1], loss3[2]
 
 
+class _SparseLossMix(torch.autograd.Function):
+    """loss5 of bo_train_loss_forward_mix; the backward is bo_train_loss_backward_mix with the gradient of loss5[0:3] (the two
+    diagnostics carry none).  q and mix are read on the device by both."""
+
+    @staticmethod
+    def forward(ctx, logits, value, pi_idx, pi_val, z, q, mix):
+        lib = E.load_hip_library()
+        n, W = pi_idx.shape
+        if (logits.dim() != 2 or logits.shape != (n, E.NUM_ACTIONS) or value.numel() != n or pi_val.shape != (n, W) or z.numel() != n
+                or q.numel() != n or mix.numel() != 1):
+            raise ValueError(f"sparse loss: shapes logits {tuple(logits.shape)} value {tuple(value.shape)} pi_idx {tuple(pi_idx.shape)} "
+                             f"pi_val {tuple(pi_val.shape)} z {tuple(z.shape)} q {tuple(q.shape)} mix {tuple(mix.shape)}")
+        if logits.dtype not in DTYPE_CODES or value.dtype not in DTYPE_CODES:
+            raise TypeError(f"sparse loss: logits {logits.dtype} / value {value.dtype}: float32, float16 or bfloat16")
+        if pi_idx.dtype != torch.int32 or any(t.dtype != torch.float32 for t in (pi_val, z, q, mix)):
+            raise TypeError("sparse loss: pi_idx int32, pi_val, z, q and mix float32")
+        dev = logits.device
+        if any(t.device != dev for t in (value, pi_idx, pi_val, z, q, mix)):
+            raise ValueError("sparse loss: all inputs on one device")
+        logits, value = logits.contiguous(), value.contiguous()
+        pi_idx, pi_val, z, q = pi_idx.contiguous(), pi_val.contiguous(), z.contiguous(), q.contiguous()
+        row_stats = torch.empty((n, ROW_STATS_MIX), dtype=torch.float32, device=dev)
+        loss5 = torch.empty(5, dtype=torch.float32, device=dev)
+        _check(lib, lib.bo_train_loss_forward_mix(n, W, logits.data_ptr(), DTYPE_CODES[logits.dtype], value.data_ptr(), DTYPE_CODES[value.dtype],
+                                                  pi_idx.data_ptr(), pi_val.data_ptr(), z.data_ptr(), q.data_ptr(), mix.data_ptr(),
+                                                  row_stats.data_ptr(), loss5.data_ptr(), _stream(logits)))
+        ctx.save_for_backward(logits, value, pi_idx, pi_val, z, q, mix, row_stats)
+        ctx.value_shape = value.shape
+        return loss5
+
+    @staticmethod
+    def backward(ctx, g5):
+        lib = E.load_hip_library()
+        logits, value, pi_idx, pi_val, z, q, mix, row_stats = ctx.saved_tensors
+        n, W = pi_idx.shape
+        g3 = g5[:3].to(torch.float32).contiguous()
+        dlogits, dvalue = torch.empty_like(logits), torch.empty_like(value)
+        _check(lib, lib.bo_train_loss_backward_mix(n, W, logits.data_ptr(), DTYPE_CODES[logits.dtype], value.data_ptr(), DTYPE_CODES[value.dtype],
+                                                   pi_idx.data_ptr(), pi_val.data_ptr(), z.data_ptr(), q.data_ptr(), mix.data_ptr(),
+                                                   row_stats.data_ptr(), g3.data_ptr(), dlogits.data_ptr(), dvalue.data_ptr(), _stream(logits)))
+        return dlogits, dvalue.view(ctx.value_shape), None, None, None, None, None
+
+
+def sparse_policy_value_loss_mix(logits, value, pi_idx, pi_val, z, q, mix):
+    """(total, policy, value_mix, value_vs_z, value_vs_q): sparse_policy_value_loss with the value head regressed on
+    t = (1 - mix) z + mix q, q [B,1] (or [B]) the records' root values (GpuReplayBuffer.batch_sparse_q; both z and q are from the side
+    to move's point of view).  value_mix = mean (value - t)^2 and total = policy + value_mix; value_vs_z and value_vs_q are the means
+    against z and q alone, detached diagnostics.  mix: a Python float, or a one-element float32 tensor on the logits' device that the
+    kernels read when they run (change it in place under a captured step).  mix == 0 is sparse_policy_value_loss bit for bit; a mix
+    outside [0, 1] is not clamped, every loss is NaN."""
+    if not isinstance(mix, torch.Tensor):
+        mix = torch.tensor([float(mix)], dtype=torch.float32, device=logits.device)
+    loss5 = _SparseLossMix.apply(logits, value, pi_idx, pi_val, z.reshape(-1), q.reshape(-1), mix.reshape(-1))
+    return loss5[0], loss5[1], loss5[2], loss5[3].detach(), loss5[4].detach()
+
+
 def dense_policy_value_loss(logits, value, target_policy, target_value):
     """The reference's calculate_loss on a dense target (train.py:222-249): the A/B baseline of --dense-loss and the tests' yardstick."""
     value_loss = F.mse_loss(value, target_value)
@@ -101,13 +160,23 @@ def dense_policy_value_loss(logits, value, target_policy, target_value):
 
 
 def train_steps(model, optimizer, scheduler, scaler, loader, *, sparse: bool = True, amp: bool = True, grad_clip: Optional[float] = None,
-                log_every: int = 0, log=None) -> Dict:
+                log_every: int = 0, log=None, value_mix=0.0) -> Dict:
     """One pass of train_network's loop (train.py:271-295) over `loader`'s batches: zero_grad, forward (under torch.autocast when amp),
     scaler.scale(loss).backward(), unscale_, clip_grad_norm_(max_norm=GRAD_CLIP_MAX), scaler.step, scaler.update, scheduler.step.
     sparse: batches are (states, pi_idx, pi_val, z) and the loss is sparse_policy_value_loss; otherwise (states, pi, z) and
     dense_policy_value_loss.  The running losses stay on the device: the host reads them every `log_every` steps (0: never) and at the
     end.  Returns {"steps", "samples", "loss": [total, policy, value] means, "losses": [steps][3] per step, "clipped": steps whose
-    gradient norm exceeded grad_clip}."""
+    gradient norm exceeded grad_clip}.
+    value_mix: a float other than 0, or a one-element float32 device tensor WHATEVER it holds (its value is the device's business: a
+    schedule may change it between steps) -> batches are batch_sparse_q's five-tuples (loader(..., with_q=True)) and the loss is
+    sparse_policy_value_loss_mix; "loss"[2] / "losses"[:, 2] are then value_mix and the result gains "value_vs_z" / "value_vs_q" (means)
+    and "diagnostics" [steps][2].  At 0 nothing changes: four-tuples and sparse_policy_value_loss."""
+    mixed = isinstance(value_mix, torch.Tensor) or float(value_mix) != 0.0
+    if mixed and not sparse:
+        raise ValueError("train_steps: value_mix needs the sparse loss")
+    if mixed and not isinstance(value_mix, torch.Tensor):  # one upload, not one per step
+        value_mix = torch.tensor([float(value_mix)], dtype=torch.float32, device=next(model.parameters()).device)
+    diag: List[torch.Tensor] = []
     if grad_clip is None:
         from . import dropin
 
@@ -123,9 +192,15 @@ def train_steps(model, optimizer, scheduler, scaler, loader, *, sparse: bool = T
         states = batch[0]
         dev = states.device
         optimizer.zero_grad()
+        if mixed and len(batch) < 5:
+            raise ValueError(f"train_steps: value_mix is set (a tensor counts whatever it holds) but the loader yields {len(batch)}-tuples: "
+                             f"it needs batch_sparse_q's (states, pi_idx, pi_val, z, q) -- loader(..., sparse=True, with_q=True)")
         with torch.autocast(dev.type, enabled=amp):
             logits, value = model(states)
-            if sparse:
+            if mixed:
+                loss, p_loss, v_loss, v_z, v_q = sparse_policy_value_loss_mix(logits, value, batch[1], batch[2], batch[3], batch[4], value_mix)
+                diag.append(torch.stack([v_z, v_q]))
+            elif sparse:
                 loss, p_loss, v_loss = sparse_policy_value_loss(logits, value, batch[1], batch[2], batch[3])
             else:
                 loss, p_loss, v_loss = dense_policy_value_loss(logits, value, batch[1], batch[2])
@@ -145,8 +220,12 @@ def train_steps(model, optimizer, scheduler, scaler, loader, *, sparse: bool = T
         return {"steps": 0, "samples": 0, "loss": [0.0, 0.0, 0.0], "losses": [], "clipped": 0}
     losses = torch.stack(per_step)
     host = losses.cpu()
-    return {"steps": len(per_step), "samples": samples, "loss": host.double().mean(0).tolist(), "losses": host.tolist(),
-            "clipped": int(torch.stack(clipped).sum().item())}
+    out = {"steps": len(per_step), "samples": samples, "loss": host.double().mean(0).tolist(), "losses": host.tolist(),
+           "clipped": int(torch.stack(clipped).sum().item())}
+    if mixed:
+        d = torch.stack(diag).cpu()
+        out.update(value_vs_z=float(d[:, 0].double().mean()), value_vs_q=float(d[:, 1].double().mean()), diagnostics=d.tolist())
+    return out
 
 
 # ---- the command line: one training iteration of main.py's loop ---------------------------------------------------------------
@@ -214,10 +293,17 @@ def main(argv=None) -> int:
     ap.add_argument("--candidate", default=None, help="write the new weights here and leave best_model.pth alone")
     ap.add_argument("--out", default=None, help="JSON with per-epoch losses, learning rate, steps/s and samples/s")
     ap.add_argument("--dense-loss", action="store_true", help="the reference's calculate_loss on dense batches (A/B comparisons)")
+    ap.add_argument("--value-mix", type=float, default=0.0, metavar="A",
+                    help="regress the value head on (1 - A) z + A q, q the records' root values (selfplay_main --record-values or a resign "
+                         "threshold); 0 = the game's outcome alone, as the reference trains")
     ap.add_argument("--no-amp", action="store_true", help="float32 forward (the reference trains under torch.autocast)")
     ap.add_argument("--log-every", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
+    if a.value_mix != 0.0 and a.dense_loss:
+        ap.error("--value-mix needs the sparse loss: not with --dense-loss")
+    if not 0.0 <= a.value_mix <= 1.0:
+        ap.error(f"--value-mix {a.value_mix}: a mix in [0, 1]")
     log = lambda s: print(f"[train] {s}", flush=True)  # noqa: E731
 
     dev = E.runtime_device(a.device)
@@ -256,21 +342,33 @@ def main(argv=None) -> int:
         return 1
     buf = load_buffer(files, dev)
     log(f"iteration {iteration}: {len(buf)} records of {buf.n_games} games from iterations {sorted(files)} (pi_width {buf.pi_width})")
+    with_values = buf.n_with_values
+    if a.value_mix > 0.0 and with_values == 0:
+        n_rec = len(buf)
+        buf.close()
+        raise SystemExit(f"train: --value-mix {a.value_mix}: none of the {n_rec} records carries a root value: "
+                         f"run selfplay_main with --record-values or a resign threshold")
+    if a.value_mix > 0.0:
+        log(f"value target (1 - {a.value_mix}) z + {a.value_mix} q: {with_values} of {len(buf)} records carry a root value (the rest train on z)")
 
     amp = not a.no_amp
     scaler = torch.GradScaler(dev.type, enabled=amp)
     epochs = []
     for ep in range(a.epochs):
-        loader = buf.loader(a.batch, steps=a.steps_per_epoch, seed=a.seed * 1000003 + iteration * 1009 + ep, sparse=not a.dense_loss)
+        loader = buf.loader(a.batch, steps=a.steps_per_epoch, seed=a.seed * 1000003 + iteration * 1009 + ep, sparse=not a.dense_loss,
+                            with_q=a.value_mix > 0.0)
         lr = optimizer.param_groups[0]["lr"]
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
-        r = train_steps(model, optimizer, scheduler, scaler, loader, sparse=not a.dense_loss, amp=amp, log_every=a.log_every, log=log)
+        r = train_steps(model, optimizer, scheduler, scaler, loader, sparse=not a.dense_loss, amp=amp, log_every=a.log_every, log=log,
+                        value_mix=a.value_mix)
         dt = time.perf_counter() - t0  # (train_steps ends reading the losses: the device is done)
         epochs.append({"epoch": ep, "steps": r["steps"], "samples": r["samples"], "loss": r["loss"][0], "policy_loss": r["loss"][1],
                        "value_loss": r["loss"][2], "lr": lr, "clipped": r["clipped"], "seconds": dt,
-                       "steps_per_s": r["steps"] / dt if dt > 0 else None, "samples_per_s": r["samples"] / dt if dt > 0 else None})
+                       "steps_per_s": r["steps"] / dt if dt > 0 else None, "samples_per_s": r["samples"] / dt if dt > 0 else None,
+                       # (at mix 0 the value loss IS the loss against z, and nothing is compared with q)
+                       "value_vs_z": r.get("value_vs_z", r["loss"][2]), "value_vs_q": r.get("value_vs_q"), "records_with_values": with_values})
         log(f"epoch {ep + 1}/{a.epochs}: loss {r['loss'][0]:.4f} policy {r['loss'][1]:.4f} value {r['loss'][2]:.4f} "
             f"({r['steps']} steps, {r['samples'] / dt if dt > 0 else 0:.0f} samples/s)")
     buf.close()
@@ -285,7 +383,7 @@ def main(argv=None) -> int:
     log(f"checkpoint {ck_path}; weights {weights}")
     if a.out:
         summary = {"iteration": iteration, "records": sum(e["samples"] for e in epochs[:1]), "loss": "dense" if a.dense_loss else "sparse",
-                   "amp": amp, "batch": a.batch, "epochs": epochs, "checkpoint": ck_path, "weights": weights}
+                   "amp": amp, "batch": a.batch, "value_mix": a.value_mix, "epochs": epochs, "checkpoint": ck_path, "weights": weights}
         with open(a.out, "w") as f:
             json.dump(summary, f, indent=1)
     return 0

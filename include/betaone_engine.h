@@ -28,9 +28,11 @@ extern "C" {
  * [G][BO_PROF_SLOTS = 16] counters, the BO_TOWER_WINOGRAD packed-weight K order for 128 filters is winograd_k_order's;
  * 3: fast-mode arenas are allocated in 128-byte granules of 8 records, bo_fast_stats counts granules; 7: resignation and root values,
  * additions only; 8: analysis of games that are on the device -- bo_games_reset_dev, bo_search_begin_dev, bo_analysis_result,
- * bo_pgn_after, bo_pgn_spans, status bit BO_ST_BAD_RANGE -- additions only).  A caller checks
+ * bo_pgn_after, bo_pgn_spans, status bit BO_ST_BAD_RANGE -- additions only; 9: the value target as a mix of the game's outcome and
+ * the search's root value -- bo_replay_add_game_values, bo_replay_values, bo_replay_sample_sparse_q, bo_train_loss_forward_mix,
+ * bo_train_loss_backward_mix -- additions only).  A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 8
+#define BO_ABI_VERSION 9
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -442,6 +444,18 @@ int bo_replay_sample(bo_replay *rb, int32_t n, const int64_t *record_index, floa
  * buffer was created with.  Same checks as bo_replay_sample. */
 int bo_replay_sample_sparse(bo_replay *rb, int32_t n, const int64_t *record_index, float *states_dev, int32_t *pi_idx_dev, float *pi_val_dev,
                             float *z_dev, void *stream);
+/* (ABI 9, additions) Root values in the buffer.  A slot keeps one float32 q beside its z: root_value[i], the root's q_value after the
+ * search at ply i from the side to move's point of view (what a BOG2 record carries) -- the same point of view as z[i], no sign flip.
+ * root_value may be NULL: the call is then bo_replay_add_game, the slots keep q = z and the game's records do not count as carrying a
+ * value.  bo_replay_values: how many resident records carry one (eviction takes a game's count with it).
+ * bo_replay_sample_sparse_q: bo_replay_sample_sparse plus q [n] float32; states, pi_idx, pi_val and z are bit-identical to that call's
+ * for the same indices, q comes from the same launch.  Same checks. */
+int bo_replay_add_game_values(bo_replay *rb, int32_t game_id, const bo_position *positions, int32_t n_records, const int32_t *pi_ptr,
+                              const int32_t *pi_idx, const float *pi_val, const float *z, const float *root_value,
+                              int64_t *evicted_records, void *stream);
+int bo_replay_values(bo_replay *rb, int64_t *n_records_with_value);
+int bo_replay_sample_sparse_q(bo_replay *rb, int32_t n, const int64_t *record_index, float *states_dev, int32_t *pi_idx_dev,
+                              float *pi_val_dev, float *z_dev, float *q_dev, void *stream);
 void bo_replay_destroy(bo_replay *rb);
 
 /* ---- (ABI 4) the residual tower of ONE board (a few boards) as ONE launch spread over the chip: csrc/bo_tower_b1.h ----------------
@@ -520,6 +534,20 @@ int bo_train_loss_forward(int32_t n, int32_t W, const void *logits_dev, int32_t 
 int bo_train_loss_backward(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
                            const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, const float *row_stats_dev,
                            const float *grad_out_dev, void *dlogits_dev, void *dvalue_dev, void *stream);
+/* (ABI 9, additions) The value head regressed on t[b] = (1 - a) z[b] + a q[b]: q [n] float32 (bo_replay_sample_sparse_q), and the mix a
+ * as ONE float32 on the device (mix_dev), read by the kernels like grad_out -- a schedule changes it under a captured step.
+ * row_stats [n,6] float32: max, log sum exp, the policy term, (v - t)^2, (v - z)^2, (v - q)^2.
+ * loss5 float32 [5] = [policy + value_mix, policy, value_mix, value_vs_z, value_vs_q]: value_mix the mean of (v - t)^2, the last two the
+ * means against z and q alone -- diagnostics without a gradient: grad_out stays [3], the gradient of loss5[0..2].
+ * a == 0 selects t = z: loss5[0..2], dlogits and dvalue are then bit for bit those of the two calls above, whatever q holds (NaN
+ * included).  a outside [0, 1] or NaN is not clamped: all of loss5 and dvalue are NaN.  Otherwise as the two calls above. */
+int bo_train_loss_forward_mix(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
+                              const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, const float *q_dev,
+                              const float *mix_dev, float *row_stats_dev, float *loss5_dev, void *stream);
+int bo_train_loss_backward_mix(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
+                               const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, const float *q_dev,
+                               const float *mix_dev, const float *row_stats_dev, const float *grad_out_dev, void *dlogits_dev,
+                               void *dvalue_dev, void *stream);
 
 /* ---- (ABI 6, additions) PGN pretraining: csrc/bo_pgn.h --------------------------------------------------------------------------
  * Replaces the reference's PGNDataset (train.py:81-160: python-chess reads the games, parses SAN and encodes 120 planes per position in
