@@ -13,6 +13,7 @@
 #include "bo_pgn.h"
 #include "bo_san.h"
 #include "bo_analyse.h"
+#include "bo_perft.h"
 #include "bo_nn_fused.h"
 #include "bo_conv.h"
 #include "bo_tower.h"
@@ -2735,4 +2736,188 @@ extern "C" int bo_nn_conv3x3_small(const float *x_dev, const float *wpacked_dev,
 #undef BO_SMALL_CASE
     return fail(BO_E_CONFIG, "bo_nn_conv3x3_small: supported (c_in, c_out): (128 | C, C) for C in {64, 128, 256}");
 #endif
+}
+
+// ---- perft on the device (bo_perft.h) --------------------------------------------------------------------------------------------
+// Level l of the walk is a frontier (positions and tags) in HBM; level 0 holds the roots.  Every level but the last one generated also
+// keeps its move counts and their scan, because a level whose children do not fit the next buffer is expanded chunk by chunk.
+namespace {
+struct PerftLevel {
+    DPos *pos = nullptr;
+    int32_t *tag = nullptr, *cnt = nullptr;
+    uint64_t *off = nullptr;
+    int64_t have = 0, have_scan = 0;
+};
+struct PerftRun {
+    void *stream = nullptr;
+    int depth = 0;
+    int64_t cap = 0, splits = 0;
+    uint32_t flags = 0;
+    std::vector<PerftLevel> lv;
+    int32_t *tsum = nullptr, *root_moves = nullptr, *root_n = nullptr;
+    uint64_t *tbase = nullptr, *nodes = nullptr, *sums = nullptr, *stats = nullptr;
+    int64_t have_tiles = 0, *d_word = nullptr, *h_word = nullptr;
+    ~PerftRun() {
+        (void)rt_sync(stream);  // nothing of ours is in flight when its memory goes
+        for (PerftLevel &L : lv) { rt_free(L.pos); rt_free(L.tag); rt_free(L.cnt); rt_free(L.off); }
+        rt_free(tsum); rt_free(tbase); rt_free(root_moves); rt_free(root_n); rt_free(nodes); rt_free(sums); rt_free(stats); rt_free(d_word);
+        if (h_word) rt_host_free(h_word);
+    }
+    // grow-only, doubling up to `limit` entries (the old contents are dead: a buffer is refilled before it is read)
+    static int64_t grown(int64_t have, int64_t need, int64_t limit) { return std::max(need, std::min(limit, 2 * have)); }
+    int room(int l, int64_t n) {
+        PerftLevel &L = lv[l];
+        if (L.have >= n) return 0;
+        const int64_t m = grown(L.have, n, cap);
+        rt_free(L.pos); rt_free(L.tag);
+        L.pos = nullptr; L.tag = nullptr; L.have = 0;
+        int rc = rt_malloc((void **)&L.pos, (size_t)m * sizeof(DPos));
+        if (!rc) rc = rt_malloc((void **)&L.tag, (size_t)m * 4);
+        if (!rc) L.have = m;
+        return rc;
+    }
+    int room_scan(int l, int64_t n) {
+        PerftLevel &L = lv[l];
+        if (L.have_scan >= n) return 0;
+        const int64_t m = grown(L.have_scan, n, std::max(cap, n));
+        rt_free(L.cnt); rt_free(L.off);
+        L.cnt = nullptr; L.off = nullptr; L.have_scan = 0;
+        int rc = rt_malloc((void **)&L.cnt, (size_t)m * 4);
+        if (!rc) rc = rt_malloc((void **)&L.off, (size_t)(m + 1) * 8);
+        if (!rc) L.have_scan = m;
+        const int64_t nt = (m + BO_PERFT_TILE - 1) / BO_PERFT_TILE;
+        if (!rc && have_tiles < nt) {
+            rt_free(tsum); rt_free(tbase);
+            tsum = nullptr; tbase = nullptr; have_tiles = 0;
+            rc = rt_malloc((void **)&tsum, (size_t)nt * 4);
+            if (!rc) rc = rt_malloc((void **)&tbase, (size_t)nt * 8);
+            if (!rc) have_tiles = nt;
+        }
+        return rc;
+    }
+};
+
+// the subtree below entries [0, n) of level l
+int perft_level(PerftRun &R, int l, int64_t n) {
+    PerftLevel &L = R.lv[l];
+    const uint32_t mode = ((R.flags & BO_PERFT_ORDER) ? PF_ORDER : 0u) | (l == 0 ? PF_ROOT_LEVEL : 0u);
+    if (l == R.depth - 1) {
+        if (R.flags & BO_PERFT_STATS)
+            RT(RT_LAUNCH(bo_k_perft_count_stats, n, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (int64_t)0, R.nodes, R.sums, R.stats, mode));
+        else
+            RT(RT_LAUNCH(bo_k_perft_count, n, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (int64_t)0, (int32_t *)nullptr, R.nodes, R.sums,
+                         mode | PF_LEAF));
+        return BO_OK;
+    }
+    RT(R.room_scan(l, n));
+    const int nt = (int)((n + BO_PERFT_TILE - 1) / BO_PERFT_TILE);
+    RT(RT_LAUNCH(bo_k_perft_count, n, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (int64_t)0, L.cnt, R.nodes, R.sums, mode));
+    RT(RT_LAUNCH(bo_k_perft_tile_sums, nt, R.stream, (const int32_t *)L.cnt, n, R.tsum));
+    RT(RT_LAUNCH(bo_k_perft_tile_scan, 1, R.stream, (const int32_t *)R.tsum, nt, R.tbase, L.off, n));
+    RT(RT_LAUNCH(bo_k_perft_offsets, nt, R.stream, (const int32_t *)L.cnt, n, (const uint64_t *)R.tbase, L.off));
+    RT(rt_d2h(R.h_word, L.off + n, 8, R.stream));  // the one word the host reads between levels
+    RT(rt_sync(R.stream));
+    int64_t left = R.h_word[0], a = 0;
+    while (a < n && left > 0) {
+        int64_t e = n, c = left;
+        if (left > R.cap) {  // the rest of the level does not fit: the longest run of entries from a that does
+            RT(RT_LAUNCH(bo_k_perft_split, 1, R.stream, (const uint64_t *)L.off, a, n, R.cap, R.d_word));
+            RT(rt_d2h(R.h_word, R.d_word, 16, R.stream));
+            RT(rt_sync(R.stream));
+            e = R.h_word[0];
+            c = R.h_word[1];
+            if (e <= a || e > n || c < 1 || c > R.cap) return fail(BO_E_STATE, "bo_perft: the level split is inconsistent");
+            if (c < left) R.splits++;
+        }
+        RT(R.room(l + 1, c));
+        RT(RT_LAUNCH(bo_k_perft_expand, e - a, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (const uint64_t *)L.off, a, R.lv[l + 1].pos,
+                     R.lv[l + 1].tag, R.lv[l + 1].have, mode));
+        const int rc = perft_level(R, l + 1, c);
+        if (rc) return rc;
+        left -= c;
+        a = e;
+    }
+    return BO_OK;
+}
+}  // namespace
+
+extern "C" int bo_perft(int device, int32_t n_roots, const char *const *fens, int32_t depth, int64_t capacity, uint32_t flags,
+                        bo_perft_result *results, int32_t *divide_moves, uint64_t *divide_nodes, int64_t *n_splits, void *stream) {
+    if (n_splits) *n_splits = 0;
+    if (n_roots < 0 || n_roots > (1 << 20) || depth < 0 || depth > 64 || (flags & ~7u) || (n_roots && !results))
+        return fail(BO_E_ARG, "bo_perft: bad arguments (n_roots <= 2^20, 0 <= depth <= 64)");
+    const bool divide = (flags & BO_PERFT_DIVIDE) != 0;
+    if (divide && n_roots && (!divide_moves || !divide_nodes)) return fail(BO_E_ARG, "bo_perft: BO_PERFT_DIVIDE needs divide_moves and divide_nodes");
+    if (capacity < BO_MAX_MOVES || capacity > ((int64_t)1 << 26))
+        return fail(BO_E_CONFIG, "bo_perft: capacity must be 256 (the children of one position) .. 2^26 positions per level");
+    if (n_roots == 0) return BO_OK;
+    std::vector<DPos> roots((size_t)n_roots);
+    for (int i = 0; i < n_roots; i++) {
+        if (!pgn_fen_root(fens && fens[i] ? fens[i] : "", &roots[i])) return fail(BO_E_FEN, "bo_perft: bad FEN (root " + std::to_string(i) + ")");
+    }
+    const size_t N = (size_t)n_roots;
+    memset(results, 0, N * sizeof(bo_perft_result));
+    if (divide) {
+        for (size_t i = 0; i < N * BO_MAX_MOVES; i++) { divide_moves[i] = -1; divide_nodes[i] = 0; }
+    }
+    if (depth == 0) {
+        for (size_t i = 0; i < N; i++) results[i].nodes = 1;
+        return BO_OK;
+    }
+    RT(rt_set_device(device));
+    PerftRun R;
+    R.stream = stream; R.depth = depth; R.cap = capacity; R.flags = flags;
+    R.lv.resize((size_t)depth);
+    {   // level 0: the roots (outside `capacity`: the caller chose their number)
+        PerftLevel &L = R.lv[0];
+        RT(rt_malloc((void **)&L.pos, N * sizeof(DPos)));
+        RT(rt_malloc((void **)&L.tag, N * 4));
+        L.have = n_roots;
+    }
+    RT(rt_malloc((void **)&R.root_moves, N * BO_MAX_MOVES * 4));
+    RT(rt_malloc((void **)&R.root_n, N * 4));
+    RT(rt_malloc((void **)&R.nodes, N * BO_MAX_MOVES * 8));
+    RT(rt_malloc((void **)&R.sums, N * 8));
+    RT(rt_malloc((void **)&R.stats, N * PF_NSTATS * 8));
+    RT(rt_malloc((void **)&R.d_word, 16));
+    RT(rt_host_alloc((void **)&R.h_word, 16));
+    std::vector<int32_t> tags(N);
+    for (size_t i = 0; i < N; i++) tags[i] = (int32_t)(i * BO_MAX_MOVES);
+    RT(rt_h2d(R.lv[0].pos, roots.data(), N * sizeof(DPos), stream));
+    RT(rt_h2d(R.lv[0].tag, tags.data(), N * 4, stream));
+    RT(rt_memset(R.nodes, 0, N * BO_MAX_MOVES * 8, stream));
+    RT(rt_memset(R.sums, 0, N * 8, stream));
+    RT(rt_memset(R.stats, 0, N * PF_NSTATS * 8, stream));
+    RT(RT_LAUNCH(bo_k_perft_roots, n_roots, stream, R.lv[0].pos, R.root_moves, R.root_n));
+    RT(rt_sync(stream));  // (roots and tags are host vectors of this frame)
+    const int rc = perft_level(R, 0, n_roots);
+    if (rc) return rc;
+    std::vector<uint64_t> nodes(N * BO_MAX_MOVES), sums(N), stats(N * PF_NSTATS);
+    std::vector<int32_t> rmoves(N * BO_MAX_MOVES), rn(N);
+    RT(rt_d2h(nodes.data(), R.nodes, nodes.size() * 8, stream));
+    RT(rt_d2h(sums.data(), R.sums, sums.size() * 8, stream));
+    RT(rt_d2h(stats.data(), R.stats, stats.size() * 8, stream));
+    RT(rt_d2h(rmoves.data(), R.root_moves, rmoves.size() * 4, stream));
+    RT(rt_d2h(rn.data(), R.root_n, rn.size() * 4, stream));
+    RT(rt_sync(stream));
+    for (size_t r = 0; r < N; r++) {
+        bo_perft_result &o = results[r];
+        o.n_moves = rn[r];
+        for (int i = 0; i < BO_MAX_MOVES; i++) o.nodes += nodes[r * BO_MAX_MOVES + i];
+        if (flags & BO_PERFT_ORDER) o.checksum = sums[r];
+        if (flags & BO_PERFT_STATS) {
+            const uint64_t *s = &stats[r * PF_NSTATS];
+            o.stats.captures = s[PF_CAPTURES]; o.stats.en_passant = s[PF_EP]; o.stats.castles = s[PF_CASTLES];
+            o.stats.promotions = s[PF_PROMOTIONS]; o.stats.checks = s[PF_CHECKS]; o.stats.checkmates = s[PF_CHECKMATES];
+            o.stats.stalemates = s[PF_STALEMATES];
+        }
+        if (divide) {
+            for (int i = 0; i < BO_MAX_MOVES; i++) {
+                divide_moves[r * BO_MAX_MOVES + i] = rmoves[r * BO_MAX_MOVES + i];
+                divide_nodes[r * BO_MAX_MOVES + i] = nodes[r * BO_MAX_MOVES + i];
+            }
+        }
+    }
+    if (n_splits) *n_splits = R.splits;
+    return BO_OK;
 }

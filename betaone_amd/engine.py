@@ -192,6 +192,8 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_pgn_spans": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "bo_pgn_movetext": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int64,
                                   C.POINTER(C.c_int64)]),
+    "bo_perft": (C.c_int, [C.c_int, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.POINTER(C.c_int64), C.c_void_p]),
 }
 # include/betaone_lab.h: introspection for the parity tests and in-kernel timing for bench.py / scripts/ (same library, not the boundary)
 _LAB_SYMBOLS = {
@@ -221,7 +223,7 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 9   # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 10  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
 
 

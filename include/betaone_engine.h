@@ -30,9 +30,9 @@ extern "C" {
  * additions only; 8: analysis of games that are on the device -- bo_games_reset_dev, bo_search_begin_dev, bo_analysis_result,
  * bo_pgn_after, bo_pgn_spans, status bit BO_ST_BAD_RANGE -- additions only; 9: the value target as a mix of the game's outcome and
  * the search's root value -- bo_replay_add_game_values, bo_replay_values, bo_replay_sample_sparse_q, bo_train_loss_forward_mix,
- * bo_train_loss_backward_mix -- additions only).  A caller checks
+ * bo_train_loss_backward_mix -- additions only; 10: perft on the device -- bo_perft, bo_perft_result -- additions only).  A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 9
+#define BO_ABI_VERSION 10
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -674,6 +674,44 @@ int bo_analysis_result(bo_engine *e, const int32_t *played_dev, bo_analysis *out
 int bo_pgn_after(const void *pos_dev, const int32_t *act_dev, int64_t capacity, int32_t n, const int64_t *idx_dev, void *pos_out_dev,
                  int32_t *move_out_dev, void *stream);
 int bo_pgn_spans(const bo_pgn *p, int64_t *begin, int64_t *end);
+
+/* ---- (ABI 10, additions) perft on the device: csrc/bo_perft.h, betaone_amd/perft.py ------------------------------------------------
+ * perft(depth) = the number of move sequences of length `depth` from a root, as python-chess's Board perft counts them: draw rules are
+ * ignored, only a position without legal moves ends a line.  The tree is walked level by level on a frontier in device memory, one
+ * wavefront per position, with the move generator and make_move of the searches (csrc/bo_chess.h).  Engine-less; SYNCHRONISES `stream`
+ * (the level sizes are read back) and allocates and frees its own device memory.
+ *
+ * fens [n_roots]: FEN strings, NULL = the start position (fens itself may be NULL: all start positions); a root needs one king per
+ * side (BO_E_FEN otherwise, as for an unparsable FEN).  The roots' en-passant key is resolved as bo_games_reset resolves it.
+ * depth >= 0.  capacity: positions per level buffer, 256 <= capacity <= 2^26 (BO_E_CONFIG otherwise); there is one buffer per level
+ * below the root, allocated as far as it is used.  When the children of a level do not fit, the level is split into chunks of
+ * consecutive entries whose children do fit and each chunk is taken to the bottom before the next starts: *n_splits (may be NULL)
+ * counts the extra chunks.  The results do not depend on capacity.  n_roots <= 2^20; n_roots == 0 does nothing.
+ * flags: BO_PERFT_DIVIDE fills divide_moves / divide_nodes ([n_roots][BO_MAX_LEGAL], both needed then, else ignored): the root's moves
+ * in generated order (from | to << 6 | promo << 12; -1 beyond n_moves) and the node count below each (depth 0: all zero);
+ * BO_PERFT_STATS fills results[r].stats (slower: every leaf is made and its own moves generated instead of counting the last level
+ * in bulk); BO_PERFT_ORDER fills results[r].checksum.  Fields that were not asked for are zero.
+ * A root without legal moves has 0 nodes for depth >= 1; depth 0 gives 1 node, zero stats and checksum 0. */
+enum { BO_PERFT_DIVIDE = 1, BO_PERFT_STATS = 2, BO_PERFT_ORDER = 4 };
+typedef struct bo_perft_stats {   /* over the leaves (the positions at `depth`), the published perft breakdown */
+    uint64_t captures;            /* the last move took a piece, en passant included */
+    uint64_t en_passant;          /* the last move was an en-passant capture */
+    uint64_t castles;             /* ... a castling move */
+    uint64_t promotions;          /* ... a promotion */
+    uint64_t checks;              /* the leaf's side to move is in check (checkmates included) */
+    uint64_t checkmates;          /* in check and no legal move */
+    uint64_t stalemates;          /* not in check and no legal move */
+} bo_perft_stats;
+typedef struct bo_perft_result {
+    uint64_t nodes;               /* perft(depth) of this root */
+    uint64_t checksum;            /* BO_PERFT_ORDER: sum mod 2^64, over every node at depth 0 .. depth - 1, of the FNV-1a hash of its move
+                                   * list in generated order: h = 0xcbf29ce484222325, per move word m: h = (h ^ m) * 0x100000001b3 */
+    bo_perft_stats stats;         /* BO_PERFT_STATS */
+    int32_t n_moves;              /* legal moves of the root (depth 0: not generated, 0) */
+    int32_t reserved;
+} bo_perft_result;
+int bo_perft(int device, int32_t n_roots, const char *const *fens, int32_t depth, int64_t capacity, uint32_t flags, bo_perft_result *results,
+             int32_t *divide_moves, uint64_t *divide_nodes, int64_t *n_splits, void *stream);
 
 #ifdef __cplusplus
 }
