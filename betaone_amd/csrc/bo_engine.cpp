@@ -14,6 +14,7 @@
 #include "bo_san.h"
 #include "bo_analyse.h"
 #include "bo_perft.h"
+#include "bo_tb.h"
 #include "bo_nn_fused.h"
 #include "bo_conv.h"
 #include "bo_tower.h"
@@ -2919,5 +2920,284 @@ extern "C" int bo_perft(int device, int32_t n_roots, const char *const *fens, in
         }
     }
     if (n_splits) *n_splits = R.splits;
+    return BO_OK;
+}
+
+// ---- endgame tablebases on the device (bo_tb.h) ------------------------------------------------------------------------------------
+struct bo_tb {
+    int device = 0;
+    std::string name;               // "KQK": each side's pieces in the order Q R B N P
+    TbTable self{};                 // (codes: device memory)
+    int64_t n = 0;                  // entries
+    std::vector<bo_tb *> subs;      // the sub-tables the passes read (a subset of what bo_tb_create was given)
+    TbTable *d_tabs = nullptr;      // [1 + subs]: this table, then its sub-tables
+    uint64_t *d_counter = nullptr;  // [2]
+    uint64_t *h_counter = nullptr;  // pinned [2]
+    bool complete = false;
+    int passes = 0;
+    bo_tb_info info{};              // of the complete table
+};
+namespace {
+const char TB_ORDER[] = "QRBNP";
+int tb_piece_type(char c) { return c == 'P' ? 1 : c == 'N' ? 2 : c == 'B' ? 3 : c == 'R' ? 4 : c == 'Q' ? 5 : 0; }
+// "KQKR" -> the two sides' pieces, each sorted Q R B N P.  false: not a material name
+bool tb_parse(const char *m, std::string side[2]) {
+    if (!m || m[0] != 'K') return false;
+    int k = 0;
+    for (const char *c = m + 1; *c; c++) {
+        if (*c == 'K') { if (++k > 1) return false; }
+        else if (!tb_piece_type(*c)) return false;
+        else side[k].push_back(*c);
+    }
+    if (k != 1) return false;
+    for (int i = 0; i < 2; i++) std::sort(side[i].begin(), side[i].end(), [](char a, char b) { return strchr(TB_ORDER, a) < strchr(TB_ORDER, b); });
+    return true;
+}
+uint32_t tb_sig_host(const std::string &strong, const std::string &weak) {
+    uint32_t s = 0;
+    for (char c : strong) s += 1u << (3 * (tb_piece_type(c) - 1));
+    for (char c : weak) s += 1u << (16 + 3 * (tb_piece_type(c) - 1));
+    return s;
+}
+// the name with the stronger side first: more men, then the better first piece in the order Q R B N P
+std::string tb_canonical(std::string a, std::string b) {
+    auto key = [](const std::string &x) {
+        std::string k;
+        for (char c : x) k.push_back((char)('0' + (strchr(TB_ORDER, c) - TB_ORDER)));
+        return k;
+    };
+    const bool swap = b.size() > a.size() || (b.size() == a.size() && key(b) < key(a));
+    return swap ? "K" + b + "K" + a : "K" + a + "K" + b;
+}
+bool tb_draw_material(const std::string &a, const std::string &b) {
+    const std::string all = a + b;
+    return all.empty() || (all.size() == 1 && (all[0] == 'B' || all[0] == 'N'));
+}
+// the materials one move away from (a, b): a capture, a promotion, a capture with promotion
+void tb_children(const std::string &a, const std::string &b, std::vector<std::pair<std::string, std::string>> *out) {
+    auto sorted = [](std::string x) {
+        std::sort(x.begin(), x.end(), [](char p, char q) { return strchr(TB_ORDER, p) < strchr(TB_ORDER, q); });
+        return x;
+    };
+    for (int side = 0; side < 2; side++) {
+        const std::string &own = side ? b : a, &opp = side ? a : b;
+        std::vector<std::string> opps{opp};  // the opponent's men after this side's move: as they are, or one taken
+        for (size_t i = 0; i < opp.size(); i++) { std::string o = opp; o.erase(i, 1); opps.push_back(o); }
+        std::vector<std::string> owns{own};
+        if (own.find('P') != std::string::npos) {
+            for (const char *q = "QRBN"; *q; q++) { std::string o = own; o[o.find('P')] = *q; owns.push_back(sorted(o)); }
+        }
+        for (const std::string &o : owns)
+            for (const std::string &p : opps) {
+                if (o == own && p == opp) continue;
+                out->push_back(side ? std::make_pair(p, o) : std::make_pair(o, p));
+            }
+    }
+}
+void tb_stats_host(bo_tb *tb, const uint16_t *codes) {
+    bo_tb_info &I = tb->info;
+    memset(&I, 0, sizeof(I));
+    I.n_entries = tb->n;
+    I.n_men = tb->self.n_men;
+    I.passes = tb->passes;
+    I.complete = tb->complete ? 1 : 0;
+    snprintf(I.material, sizeof(I.material), "%s", tb->name.c_str());
+    uint64_t h = BO_PERFT_FNV_BASIS;
+    for (int s = 0; s < 2; s++) {
+        bo_tb_side_stats &S = I.side[s];
+        S.max_win_ply = S.max_loss_ply = -1;
+        for (int64_t i = s * (tb->n / 2); i < (s + 1) * (tb->n / 2); i++) {
+            const uint16_t c = codes[i];
+            h = (h ^ (uint64_t)(c & 0xFF)) * BO_PERFT_FNV_PRIME;
+            h = (h ^ (uint64_t)(c >> 8)) * BO_PERFT_FNV_PRIME;
+            if (!c) continue;
+            S.legal++;
+            if (c == 1) { S.draws++; continue; }
+            const int k = c - 2;
+            if (k & 1) { S.wins++; S.max_win_ply = std::max(S.max_win_ply, k); }
+            else { S.losses++; S.max_loss_ply = std::max(S.max_loss_ply, k); }
+        }
+    }
+    I.fnv1a = h;
+}
+int tb_refresh_stats(bo_tb *tb, void *stream) {
+    std::vector<uint16_t> host((size_t)tb->n);
+    RT(rt_d2h(host.data(), tb->self.codes, (size_t)tb->n * 2, stream));
+    RT(rt_sync(stream));
+    tb_stats_host(tb, host.data());
+    return BO_OK;
+}
+}  // namespace
+
+extern "C" void bo_tb_destroy(bo_tb *tb) {
+    if (!tb) return;
+    (void)rt_set_device(tb->device);
+    rt_free(tb->self.codes);
+    rt_free(tb->d_tabs);
+    rt_free(tb->d_counter);
+    if (tb->h_counter) rt_host_free(tb->h_counter);
+    delete tb;
+}
+
+extern "C" int bo_tb_create(int device, const char *material, bo_tb *const *sub_tables, int32_t n_sub, bo_tb **out) {
+    if (!out || n_sub < 0 || (n_sub && !sub_tables)) return fail(BO_E_ARG, "bo_tb_create: bad arguments");
+    *out = nullptr;
+    std::string side[2];
+    if (!tb_parse(material, side)) return fail(BO_E_ARG, "bo_tb_create: a material is K, the strong side's pieces, K, the weak side's pieces (QRBNP)");
+    const int men = 2 + (int)side[0].size() + (int)side[1].size();
+    if (men > TB_MAX_MEN) return fail(BO_E_ARG, "bo_tb_create: " + std::string(material) + " has " + std::to_string(men) + " men; tables have 2 to 4");
+    if (side[0].find('P') != std::string::npos && side[1].find('P') != std::string::npos)
+        return fail(BO_E_CONFIG, "bo_tb_create: " + std::string(material) + " has pawns on both sides: en passant is not handled (a follow-up)");
+    for (int i = 0; i < n_sub; i++) {
+        if (!sub_tables[i]) return fail(BO_E_ARG, "bo_tb_create: null sub-table");
+        if (sub_tables[i]->device != device) return fail(BO_E_ARG, "bo_tb_create: a sub-table lives on another device");
+    }
+    if (tb_canonical(side[0], side[1]) != "K" + side[0] + "K" + side[1])
+        return fail(BO_E_ARG, "bo_tb_create: the strong side comes first: write " + tb_canonical(side[0], side[1]));
+    bo_tb *tb = new bo_tb();
+    tb->device = device;
+    tb->name = "K" + side[0] + "K" + side[1];
+    TbTable &T = tb->self;
+    T.n_men = men;
+    T.sig = tb_sig_host(side[0], side[1]);
+    int s = 0;
+    T.pt[s] = 6; T.strong[s++] = 1;
+    for (char c : side[0]) { T.pt[s] = (uint8_t)tb_piece_type(c); T.strong[s++] = 1; }
+    T.pt[s] = 6; T.strong[s++] = 0;
+    for (char c : side[1]) { T.pt[s] = (uint8_t)tb_piece_type(c); T.strong[s++] = 0; }
+    tb->n = (int64_t)2 << (6 * men);
+    // the sub-tables the material needs
+    std::vector<std::pair<std::string, std::string>> kids;
+    tb_children(side[0], side[1], &kids);
+    for (const auto &k : kids) {
+        if (tb_draw_material(k.first, k.second)) continue;
+        const uint32_t sig = tb_sig_host(k.first, k.second), sig_m = tb_sig_host(k.second, k.first);
+        if (sig == T.sig || sig_m == T.sig) continue;
+        bo_tb *found = nullptr;
+        for (int i = 0; i < n_sub && !found; i++)
+            if (sub_tables[i]->self.sig == sig || sub_tables[i]->self.sig == sig_m) found = sub_tables[i];
+        const std::string want = tb_canonical(k.first, k.second);
+        if (!found) {
+            const std::string msg = "bo_tb_create: " + tb->name + " needs the sub-table " + want + ", which was not given";
+            delete tb;
+            return fail(BO_E_STATE, msg);
+        }
+        if (!found->complete) { delete tb; return fail(BO_E_STATE, "bo_tb_create: the sub-table " + want + " is not complete (build or upload it first)"); }
+        if (std::find(tb->subs.begin(), tb->subs.end(), found) == tb->subs.end()) tb->subs.push_back(found);
+    }
+    std::vector<TbTable> tabs{T};
+    int rc = rt_set_device(device);
+    if (!rc) rc = rt_malloc((void **)&T.codes, (size_t)tb->n * 2);
+    tabs[0].codes = T.codes;
+    for (bo_tb *sub : tb->subs) tabs.push_back(sub->self);
+    if (!rc) rc = rt_malloc((void **)&tb->d_tabs, tabs.size() * sizeof(TbTable));
+    if (!rc) rc = rt_malloc((void **)&tb->d_counter, 16);
+    if (!rc) rc = rt_host_alloc((void **)&tb->h_counter, 16);
+    if (!rc) rc = rt_h2d(tb->d_tabs, tabs.data(), tabs.size() * sizeof(TbTable), nullptr);
+    if (!rc) rc = rt_memset(T.codes, 0, (size_t)tb->n * 2, nullptr);
+    if (!rc) rc = rt_sync(nullptr);  // (tabs is a vector of this frame)
+    if (rc) { bo_tb_destroy(tb); return fail(BO_E_HIP, std::string("bo_tb_create: ") + rt_errstr(rc)); }
+    *out = tb;
+    return BO_OK;
+}
+
+extern "C" int bo_tb_build(bo_tb *tb, int32_t max_passes, int32_t *passes, void *stream) {
+    if (passes) *passes = 0;
+    if (!tb) return fail(BO_E_ARG, "bo_tb_build: null table");
+    RT(rt_set_device(tb->device));
+    int max_sub = -1;  // the largest value in any sub-table
+    for (bo_tb *s : tb->subs)
+        for (int k = 0; k < 2; k++) max_sub = std::max(max_sub, std::max(s->info.side[k].max_win_ply, s->info.side[k].max_loss_ply));
+    const int grid = (int)(tb->n / TB_RUN), n_tabs = 1 + (int)tb->subs.size();
+    tb->complete = false;
+    tb->passes = 0;
+    RT(RT_LAUNCH(bo_k_tb_init, grid, stream, (const TbTable *)tb->d_tabs));
+    bool done = false;
+    for (int i = 1; !done && (max_passes < 0 || i <= max_passes); i++) {
+        if (i > 0x7ff0) return fail(BO_E_STATE, "bo_tb_build: the passes do not end");
+        RT(rt_memset(tb->d_counter, 0, 16, stream));
+        RT(RT_LAUNCH(bo_k_tb_pass, grid, stream, (const TbTable *)tb->d_tabs, n_tabs, i, tb->d_counter));
+        RT(rt_d2h(tb->h_counter, tb->d_counter, 16, stream));  // the one counter the host reads between passes
+        RT(rt_sync(stream));
+        tb->passes = i;
+        if (tb->h_counter[1]) return fail(BO_E_STATE, "bo_tb_build: " + tb->name + ": a child position has no code (a sub-table is wrong)");
+        done = tb->h_counter[0] == 0 && i - 1 > max_sub;
+    }
+    tb->complete = done;
+    if (passes) *passes = tb->passes;
+    return tb_refresh_stats(tb, stream);
+}
+
+extern "C" int bo_tb_verify(bo_tb *tb, uint64_t *mismatches, void *stream) {
+    if (!tb || !mismatches) return fail(BO_E_ARG, "bo_tb_verify: bad arguments");
+    RT(rt_set_device(tb->device));
+    RT(rt_memset(tb->d_counter, 0, 16, stream));
+    RT(RT_LAUNCH(bo_k_tb_verify, (int)(tb->n / TB_RUN), stream, (const TbTable *)tb->d_tabs, 1 + (int)tb->subs.size(), tb->d_counter));
+    RT(rt_d2h(tb->h_counter, tb->d_counter, 16, stream));
+    RT(rt_sync(stream));
+    *mismatches = tb->h_counter[0];
+    return BO_OK;
+}
+
+extern "C" int bo_tb_stats(bo_tb *tb, bo_tb_info *out) {
+    if (!tb || !out) return fail(BO_E_ARG, "bo_tb_stats: bad arguments");
+    if (!tb->info.n_entries) {  // neither built nor uploaded yet
+        RT(rt_set_device(tb->device));
+        const int rc = tb_refresh_stats(tb, nullptr);
+        if (rc) return rc;
+    }
+    *out = tb->info;
+    return BO_OK;
+}
+
+extern "C" int bo_tb_download(bo_tb *tb, uint16_t *codes, int64_t n_entries) {
+    if (!tb || !codes) return fail(BO_E_ARG, "bo_tb_download: bad arguments");
+    if (n_entries != tb->n) return fail(BO_E_ARG, "bo_tb_download: " + tb->name + " has " + std::to_string(tb->n) + " entries");
+    RT(rt_set_device(tb->device));
+    RT(rt_d2h(codes, tb->self.codes, (size_t)tb->n * 2, nullptr));
+    RT(rt_sync(nullptr));
+    return BO_OK;
+}
+
+extern "C" int bo_tb_upload(bo_tb *tb, const uint16_t *codes, int64_t n_entries, int32_t passes) {
+    if (!tb || !codes) return fail(BO_E_ARG, "bo_tb_upload: bad arguments");
+    if (n_entries != tb->n) return fail(BO_E_ARG, "bo_tb_upload: " + tb->name + " has " + std::to_string(tb->n) + " entries");
+    RT(rt_set_device(tb->device));
+    RT(rt_h2d(tb->self.codes, codes, (size_t)tb->n * 2, nullptr));
+    RT(rt_sync(nullptr));
+    tb->complete = true;
+    tb->passes = passes;
+    tb_stats_host(tb, codes);
+    return BO_OK;
+}
+
+extern "C" int bo_tb_probe(bo_tb *const *tbs, int32_t n_tb, const bo_position *positions, int32_t n, uint16_t *codes, int32_t *status, void *stream) {
+    if (n_tb < 0 || n_tb > TB_MAX_TABLES || (n_tb && !tbs) || n < 0 || (n && (!positions || !codes || !status)))
+        return fail(BO_E_ARG, "bo_tb_probe: bad arguments (at most 64 tables)");
+    std::vector<TbTable> tabs;
+    for (int i = 0; i < n_tb; i++) {
+        if (!tbs[i]) return fail(BO_E_ARG, "bo_tb_probe: null table");
+        if (tbs[i]->device != tbs[0]->device) return fail(BO_E_ARG, "bo_tb_probe: the tables live on different devices");
+        if (!tbs[i]->complete) return fail(BO_E_STATE, "bo_tb_probe: the table " + tbs[i]->name + " is not complete");
+        tabs.push_back(tbs[i]->self);
+    }
+    if (n == 0) return BO_OK;
+    if (n_tb) RT(rt_set_device(tbs[0]->device));
+    TbTable *d_tabs = nullptr;
+    bo_position *d_pos = nullptr;
+    uint16_t *d_codes = nullptr;
+    int32_t *d_status = nullptr;
+    int rc = rt_malloc((void **)&d_tabs, std::max<size_t>(1, tabs.size()) * sizeof(TbTable));
+    if (!rc) rc = rt_malloc((void **)&d_pos, (size_t)n * sizeof(bo_position));
+    if (!rc) rc = rt_malloc((void **)&d_codes, (size_t)n * 2);
+    if (!rc) rc = rt_malloc((void **)&d_status, (size_t)n * 4);
+    if (!rc && n_tb) rc = rt_h2d(d_tabs, tabs.data(), tabs.size() * sizeof(TbTable), stream);
+    if (!rc) rc = rt_h2d(d_pos, positions, (size_t)n * sizeof(bo_position), stream);
+    if (!rc) rc = RT_LAUNCH(bo_k_tb_probe, (n + 63) / 64, stream, (const TbTable *)d_tabs, n_tb, (const bo_position *)d_pos, n, d_codes, d_status);
+    if (!rc) rc = rt_d2h(codes, d_codes, (size_t)n * 2, stream);
+    if (!rc) rc = rt_d2h(status, d_status, (size_t)n * 4, stream);
+    const int rc2 = rt_sync(stream);
+    rt_free(d_tabs); rt_free(d_pos); rt_free(d_codes); rt_free(d_status);
+    if (rc || rc2) return fail(BO_E_HIP, std::string("bo_tb_probe: ") + rt_errstr(rc ? rc : rc2));
     return BO_OK;
 }

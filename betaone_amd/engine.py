@@ -194,6 +194,14 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
                                   C.POINTER(C.c_int64)]),
     "bo_perft": (C.c_int, [C.c_int, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                            C.POINTER(C.c_int64), C.c_void_p]),
+    "bo_tb_create": (C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]),
+    "bo_tb_build": (C.c_int, [C.c_void_p, C.c_int32, _I32P, C.c_void_p]),
+    "bo_tb_verify": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "bo_tb_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bo_tb_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "bo_tb_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "bo_tb_probe": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bo_tb_destroy": (None, [C.c_void_p]),
 }
 # include/betaone_lab.h: introspection for the parity tests and in-kernel timing for bench.py / scripts/ (same library, not the boundary)
 _LAB_SYMBOLS = {
@@ -223,7 +231,7 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 10  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 11  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
 
 

@@ -30,9 +30,11 @@ extern "C" {
  * additions only; 8: analysis of games that are on the device -- bo_games_reset_dev, bo_search_begin_dev, bo_analysis_result,
  * bo_pgn_after, bo_pgn_spans, status bit BO_ST_BAD_RANGE -- additions only; 9: the value target as a mix of the game's outcome and
  * the search's root value -- bo_replay_add_game_values, bo_replay_values, bo_replay_sample_sparse_q, bo_train_loss_forward_mix,
- * bo_train_loss_backward_mix -- additions only; 10: perft on the device -- bo_perft, bo_perft_result -- additions only).  A caller checks
+ * bo_train_loss_backward_mix -- additions only; 10: perft on the device -- bo_perft, bo_perft_result -- additions only; 11: endgame
+ * tablebases on the device -- bo_tb_create, bo_tb_build, bo_tb_verify, bo_tb_stats, bo_tb_download, bo_tb_upload, bo_tb_probe,
+ * bo_tb_destroy -- additions only).  A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 10
+#define BO_ABI_VERSION 11
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -712,6 +714,56 @@ typedef struct bo_perft_result {
 } bo_perft_result;
 int bo_perft(int device, int32_t n_roots, const char *const *fens, int32_t depth, int64_t capacity, uint32_t flags, bo_perft_result *results,
              int32_t *divide_moves, uint64_t *divide_nodes, int64_t *n_splits, void *stream);
+
+/* ---- (ABI 11, additions) endgame tablebases on the device: csrc/bo_tb.h, betaone_amd/tablebase.py ----------------------------------
+ * Distance to mate in plies, 50-move rule ignored, no castling rights, 2 to 4 men, pawns on one side only (so no en passant).
+ * material: the strong side first, "KQK", "KPK", "KBNK", "KQKR" ...; each side's pieces are kept in the order Q R B N P.  The strong
+ * side is white in the table's frame; the colour-swapped material is served by the mirror (ranks flipped, colours and the side to move
+ * swapped).  5 or more men, a malformed name, the weaker side first ("KKQ", "KPKR": the message names "KQK", "KRKP"): BO_E_ARG; pawns on both sides ("KPKP"): BO_E_CONFIG (a follow-up: it needs en passant).
+ * Index: idx = ((stm * 64 + sq[0]) * 64 + sq[1]) ... over the piece list K, strong pieces, k, weak pieces; stm 0 = the strong side
+ * moves; 2 * 64^men entries.  Payload: one uint16 per entry -- 0 not a position, 1 draw, 2 + k mate in k plies (k even: the side to
+ * move is mated in k, k = 0 checkmate; k odd: the side to move mates in k).
+ * bo_tb_create: sub_tables [n] are the complete tables a capture or a promotion of `material` leads to (KK, KBK and KNK need none:
+ * insufficient material, a draw); one that is needed and not given, or not complete: BO_E_STATE with its name in bo_last_error().
+ * The table keeps the pointers: destroy it before its sub-tables.
+ * bo_tb_build: the classification of every index, then passes 1, 2, ... (pass i assigns exactly the entries whose value is i), until a
+ * pass assigns nothing and i - 1 exceeds the largest value in any sub-table.  max_passes < 0: to the end; otherwise at most that many
+ * passes (0: the classification only) and the table stays incomplete when they do not reach the end.  *passes (may be NULL) = passes
+ * run.  SYNCHRONISES `stream` (one counter is read after each pass).  Two builds give the same bytes.
+ * bo_tb_verify: every entry recomputed from its children's codes (and every index's legality); *mismatches must be 0.
+ * bo_tb_stats: per side to move (0 strong, 1 weak) over the payload; complete tables only fill `complete` = 1.
+ * bo_tb_download / bo_tb_upload: the payload as a host array of n_entries uint16 (BO_E_ARG when n_entries is not the table's); an
+ * uploaded table counts as complete.
+ * bo_tb_probe: positions [n] (HOST memory) against the set tbs [n_tb <= 64, complete tables on one device]: codes [n] (uint16) and
+ * status [n] (BO_TB_*) to host memory; SYNCHRONISES `stream`.  Clocks and the e.p. square are ignored. */
+enum {
+    BO_TB_COVERED = 0,         /* codes[i] is the position's code (insufficient material: 1, no table needed) */
+    BO_TB_NO_TABLE = 1,        /* its material's table is not in the set */
+    BO_TB_TOO_MANY_MEN = 2,    /* more than 4 men */
+    BO_TB_CASTLING = 3,        /* castling rights */
+    BO_TB_PAWNS_BOTH = 4,      /* pawns of both colours */
+    BO_TB_NOT_A_POSITION = 5   /* the table holds code 0 for it (the side not to move is in check, ...) or a king is missing */
+};
+typedef struct bo_tb bo_tb;
+typedef struct bo_tb_side_stats {
+    uint64_t legal, wins, draws, losses;   /* entries with this side to move: code != 0, odd k, code 1, even k */
+    int32_t max_win_ply, max_loss_ply;     /* the largest k of a win / of a loss, -1 when there is none */
+} bo_tb_side_stats;
+typedef struct bo_tb_info {
+    int64_t n_entries;
+    int32_t n_men, passes, complete, reserved;
+    uint64_t fnv1a;                        /* FNV-1a (64 bit) over the payload's little-endian bytes */
+    bo_tb_side_stats side[2];              /* 0: the strong side to move, 1: the weak side */
+    char material[16];                     /* the name as the table keeps it */
+} bo_tb_info;
+int bo_tb_create(int device, const char *material, bo_tb *const *sub_tables, int32_t n_sub, bo_tb **out);
+int bo_tb_build(bo_tb *tb, int32_t max_passes, int32_t *passes, void *stream);
+int bo_tb_verify(bo_tb *tb, uint64_t *mismatches, void *stream);
+int bo_tb_stats(bo_tb *tb, bo_tb_info *out);
+int bo_tb_download(bo_tb *tb, uint16_t *codes, int64_t n_entries);
+int bo_tb_upload(bo_tb *tb, const uint16_t *codes, int64_t n_entries, int32_t passes);
+int bo_tb_probe(bo_tb *const *tbs, int32_t n_tb, const bo_position *positions, int32_t n, uint16_t *codes, int32_t *status, void *stream);
+void bo_tb_destroy(bo_tb *tb);
 
 #ifdef __cplusplus
 }
