@@ -10,6 +10,7 @@
 #include "bo_select_wide.h"
 #include "bo_replay.h"
 #include "bo_train.h"
+#include "bo_metrics.h"
 #include "bo_pgn.h"
 #include "bo_san.h"
 #include "bo_analyse.h"
@@ -1740,6 +1741,27 @@ extern "C" int bo_train_loss_backward_mix(int32_t n, int32_t W, const void *logi
     });
     if (!ok) return fail(BO_E_CONFIG, "bo_train_loss_backward_mix: unsupported dtype");
     if (rc) return fail(BO_E_HIP, std::string("bo_train_loss_backward_mix: ") + rt_errstr(rc));
+    return BO_OK;
+}
+
+// Held-out validation metrics (bo_metrics.h): a record per row, then the rows of every bucket added into accum.
+extern "C" int bo_train_metrics(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
+                                const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, const float *q_dev,
+                                const int32_t *bucket_dev, int32_t n_buckets, float *rows_dev, double *accum_dev, void *stream) {
+    int rc = train_loss_args("bo_train_metrics", n, W, logits_dev, value_dev, pi_idx_dev, pi_val_dev, z_dev, rows_dev);
+    if (rc) return rc;
+    if (n_buckets < 1 || !accum_dev) return fail(BO_E_ARG, "bo_train_metrics: bad arguments");
+    bool ok = false;
+    train_dtype(logits_dtype, [&](auto *tl) {
+        ok = train_dtype(value_dtype, [&](auto *tv) {
+            BO_TRAIN_TYPES(tl, tv);
+            rc = RT_LAUNCH((bo_k_metrics_rows<TL, TV>), n, stream, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
+                           pi_val_dev, z_dev, q_dev, rows_dev);
+        });
+    });
+    if (!ok) return fail(BO_E_CONFIG, "bo_train_metrics: unsupported dtype");
+    if (!rc) rc = RT_LAUNCH(bo_k_metrics_reduce, n_buckets, stream, (int)n, (const float *)rows_dev, (const int *)bucket_dev, accum_dev);
+    if (rc) return fail(BO_E_HIP, std::string("bo_train_metrics: ") + rt_errstr(rc));
     return BO_OK;
 }
 

@@ -101,3 +101,23 @@ BO_DEV float bo_wave_sum_f(float v) {
     for (int m = 1; m < 64; m <<= 1) v = v + bo_shfl_xor_f(v, m);
     return v;
 }
+// wave-wide argmax, the same butterfly: the largest v and, among equal ones, the lowest i (all lanes get both; the order on
+// (v, i) pairs is total, so every lane ends with the same pair).  A NaN never wins and is never replaced: no NaN among the v.
+BO_DEV void bo_wave_argmax_f(float &v, int &i) {
+    for (int m = 1; m < 64; m <<= 1) {
+        const float ov = bo_shfl_xor_f(v, m);
+        const int oi = bo_shfl_xor(i, m);
+        const bool take = (ov > v) | ((ov == v) & (oi < i));
+        v = take ? ov : v;
+        i = take ? oi : i;
+    }
+}
+// wave-wide float64 sum, the same butterfly (a double travels as its two halves)
+BO_DEV double bo_wave_sum_d(double v) {
+    for (int m = 1; m < 64; m <<= 1) {
+        const uint64_t u = __builtin_bit_cast(uint64_t, v);
+        const uint32_t lo = (uint32_t)bo_shfl_xor((int)(uint32_t)u, m), hi = (uint32_t)bo_shfl_xor((int)(uint32_t)(u >> 32), m);
+        v = v + __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+    }
+    return v;
+}

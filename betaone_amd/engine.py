@@ -177,6 +177,8 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_train_loss_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8),
     "bo_train_loss_forward_mix": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8),
     "bo_train_loss_backward_mix": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 10),
+    "bo_train_metrics": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+                         + [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bo_pgn_parse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]),
     "bo_pgn_size": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int64)] * 3),
     "bo_pgn_export": (C.c_int, [C.c_void_p, _I32P, _I32P, C.c_void_p, C.c_void_p, _I32P, _F32P]),
@@ -231,8 +233,16 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 11  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 12  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
+# BO_METRIC_ROW_* / BO_METRIC_* of include/betaone_engine.h by name (bo_train_metrics; tests/test_validate_emu.py compares with the header)
+METRIC_ROW = {name: k for k, name in enumerate((
+    "BAD", "HAS_POLICY", "DECISIVE", "RANK", "TOP1", "TOP3", "TOP5", "ARGMAX_IN_SUPPORT", "CE", "TARGET_ENTROPY", "NET_ENTROPY", "P_TOP",
+    "P_SUPPORT", "SE_Z", "SE_Q", "ABS_V", "SIGN_OK", "Z", "V"))}
+METRIC = {name: k for k, name in enumerate((
+    "N_ROWS", "N_BAD", "N_POLICY_ROWS", "N_DECISIVE", "SUM_RANK", "SUM_TOP1", "SUM_TOP3", "SUM_TOP5", "SUM_ARGMAX_IN_SUPPORT", "SUM_CE",
+    "SUM_TARGET_ENTROPY", "SUM_NET_ENTROPY", "SUM_P_TOP", "SUM_P_SUPPORT", "SUM_SE_Z", "SUM_SE_Q", "SUM_ABS_V", "SUM_SIGN_OK", "SUM_Z", "SUM_V"))}
+METRIC_ROW_COLS, METRIC_COLS = len(METRIC_ROW), len(METRIC)
 
 
 def load_hip_library() -> C.CDLL:

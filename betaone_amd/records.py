@@ -391,35 +391,46 @@ class GpuReplayBuffer:
         return self.batch(rng.integers(0, len(self), size=int(batch_size)))
 
     def loader(self, batch_size: int, steps: Optional[int] = None, seed: Optional[int] = None, shuffle: bool = True, sparse: bool = False,
-               with_q: bool = False):
+               with_q: bool = False, index=None):
         """An iterable with DataLoader's contract for train_network (train.py:252: `for states, t_policies, t_values in dataloader`):
         one epoch over the resident records in a random order (shuffle=True, the reference's DataLoader(shuffle=True)), or `steps` batches
         drawn with replacement.  Batches are made on the buffer's device; the loop's `.to(config.DEVICE)` finds them there.
         sparse=True: the same batches as batch_sparse's (states, pi_idx, pi_val, values); with_q=True (sparse only): batch_sparse_q's
-        five-tuples, the same records in the same order."""
+        five-tuples, the same records in the same order.
+        index: draw only from these record indices (validate.holdout_games keeps held-out games out of training with it): an epoch is
+        one pass over them, `steps` batches are drawn from them with replacement.  None: every resident record, the draws as ever."""
         if with_q and not sparse:
             raise ValueError("loader: with_q needs sparse=True (the dense sampler has no root values)")
-        return _ReplayLoader(self, int(batch_size), steps, seed, shuffle, sparse, with_q)
+        if index is not None:
+            index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+            if index.size == 0 or int(index.min()) < 0 or int(index.max()) >= len(self):
+                raise ValueError(f"loader: index needs at least one record, all inside [0, {len(self)})")
+        return _ReplayLoader(self, int(batch_size), steps, seed, shuffle, sparse, with_q, index)
 
 
 class _ReplayLoader:
-    def __init__(self, buf: GpuReplayBuffer, batch_size: int, steps, seed, shuffle, sparse=False, with_q=False):
+    def __init__(self, buf: GpuReplayBuffer, batch_size: int, steps, seed, shuffle, sparse=False, with_q=False, index=None):
         self.buf, self.batch_size, self.steps, self.seed, self.shuffle = buf, batch_size, steps, seed, shuffle
         self.make = buf.batch_sparse_q if with_q else buf.batch_sparse if sparse else buf.batch
+        self.index = index
+
+    def _n(self) -> int:
+        return len(self.buf) if self.index is None else int(self.index.size)
 
     def __len__(self) -> int:
-        return self.steps if self.steps is not None else (len(self.buf) + self.batch_size - 1) // self.batch_size
+        return self.steps if self.steps is not None else (self._n() + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
         rng = np.random.default_rng(self.seed)
-        n = len(self.buf)
+        n = self._n()
+        pick = (lambda k: k) if self.index is None else (lambda k: self.index[k])
         if self.steps is not None:
             for _ in range(self.steps):
-                yield self.make(rng.integers(0, n, size=self.batch_size))
+                yield self.make(pick(rng.integers(0, n, size=self.batch_size)))
             return
         order = rng.permutation(n) if self.shuffle else np.arange(n)
         for i in range(0, n, self.batch_size):
-            yield self.make(order[i:i + self.batch_size])
+            yield self.make(pick(order[i:i + self.batch_size]))
 
 
 def all_gather_bytes(payload: bytes, device: Optional[torch.device] = None, group=None) -> List[bytes]:

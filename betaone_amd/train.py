@@ -11,6 +11,7 @@ backward passes are PyTorch's (MIOpen); only the loss and its gradient are hand-
 
     python -m betaone_amd.train --iteration 3 --data-dir data --save-dir checkpoints --candidate cand.pth
     python -m betaone_amd.train --value-mix 0.5 ...     # records of selfplay_main --record-values, or of a run with resignation
+    python -m betaone_amd.train --holdout-fraction 0.05 ...   # 5 % of the games never train; validated after every epoch (validate.py)
     python -m betaone_amd.match checkpoints/best_model.pth cand.pth --promote checkpoints/best_model.pth
 """
 from __future__ import annotations
@@ -244,9 +245,24 @@ def iteration_files(data_dir: str, iteration: int, past: int = 5):
     return found, pickles_only
 
 
-def load_buffer(files: Dict[int, List[str]], device) -> R.GpuReplayBuffer:
-    games = [g for it in sorted(files) for f in files[it] for g in R.load_games(f)]
-    games = [g for g in games if int(g["n_plies"]) > 0]
+def load_window_games(files: Dict[int, List[str]]) -> List[dict]:
+    """The games of the window that have plies, oldest iteration first, each with its "iteration" (validate.holdout_games keys the
+    split on it and the game's id)."""
+    games = []
+    for it in sorted(files):
+        for f in files[it]:
+            for g in R.load_games(f):
+                if int(g["n_plies"]) > 0:
+                    g["iteration"] = it
+                    games.append(g)
+    return games
+
+
+def load_buffer(files: Dict[int, List[str]], device, games: Optional[List[dict]] = None) -> R.GpuReplayBuffer:
+    """A replay buffer sized for all the games of the window (nothing is evicted: record k of the buffer is record k of the games in
+    load_window_games' order)."""
+    if games is None:
+        games = load_window_games(files)
     if not games:
         raise SystemExit("train: the compact files of the window hold no plies")
     width = max(2, max(len(ix) for g in games for ix, _ in g["pis"]))
@@ -296,6 +312,10 @@ def main(argv=None) -> int:
     ap.add_argument("--value-mix", type=float, default=0.0, metavar="A",
                     help="regress the value head on (1 - A) z + A q, q the records' root values (selfplay_main --record-values or a resign "
                          "threshold); 0 = the game's outcome alone, as the reference trains")
+    ap.add_argument("--holdout-fraction", type=float, default=0.0, metavar="F",
+                    help="keep this share of the games (whole games, chosen by a hash of iteration, game id and --holdout-seed) out of "
+                         "training and evaluate them after every epoch (betaone_amd.validate); 0 = train on everything")
+    ap.add_argument("--holdout-seed", type=int, default=0)
     ap.add_argument("--no-amp", action="store_true", help="float32 forward (the reference trains under torch.autocast)")
     ap.add_argument("--log-every", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
@@ -304,6 +324,8 @@ def main(argv=None) -> int:
         ap.error("--value-mix needs the sparse loss: not with --dense-loss")
     if not 0.0 <= a.value_mix <= 1.0:
         ap.error(f"--value-mix {a.value_mix}: a mix in [0, 1]")
+    if not 0.0 <= a.holdout_fraction < 1.0:
+        ap.error(f"--holdout-fraction {a.holdout_fraction}: a share in [0, 1)")
     log = lambda s: print(f"[train] {s}", flush=True)  # noqa: E731
 
     dev = E.runtime_device(a.device)
@@ -340,7 +362,21 @@ def main(argv=None) -> int:
     if not files:
         log(f"no compact records for iterations {max(0, iteration - a.past)}..{iteration} under {a.data_dir}")
         return 1
-    buf = load_buffer(files, dev)
+    train_index = held_index = None
+    games = None
+    if a.holdout_fraction > 0.0:
+        from . import validate as V
+
+        games = load_window_games(files)
+        train_index, held_index = V.holdout_games(games, a.holdout_fraction, a.holdout_seed)
+        if held_index.size == 0 or train_index.size == 0:
+            raise SystemExit(f"train: --holdout-fraction {a.holdout_fraction} (seed {a.holdout_seed}) holds out "
+                             f"{V.held_out_game_count(games, a.holdout_fraction, a.holdout_seed)} of the {len(games)} games: "
+                             f"{'nothing to validate on' if held_index.size == 0 else 'nothing left to train on'}")
+    buf = load_buffer(files, dev, games=games)
+    if held_index is not None:
+        log(f"held out: {held_index.size} records of {V.held_out_game_count(games, a.holdout_fraction, a.holdout_seed)} games "
+            f"(fraction {a.holdout_fraction}, seed {a.holdout_seed}); {train_index.size} records train")
     log(f"iteration {iteration}: {len(buf)} records of {buf.n_games} games from iterations {sorted(files)} (pi_width {buf.pi_width})")
     with_values = buf.n_with_values
     if a.value_mix > 0.0 and with_values == 0:
@@ -356,7 +392,7 @@ def main(argv=None) -> int:
     epochs = []
     for ep in range(a.epochs):
         loader = buf.loader(a.batch, steps=a.steps_per_epoch, seed=a.seed * 1000003 + iteration * 1009 + ep, sparse=not a.dense_loss,
-                            with_q=a.value_mix > 0.0)
+                            with_q=a.value_mix > 0.0, index=train_index)
         lr = optimizer.param_groups[0]["lr"]
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
@@ -369,8 +405,15 @@ def main(argv=None) -> int:
                        "steps_per_s": r["steps"] / dt if dt > 0 else None, "samples_per_s": r["samples"] / dt if dt > 0 else None,
                        # (at mix 0 the value loss IS the loss against z, and nothing is compared with q)
                        "value_vs_z": r.get("value_vs_z", r["loss"][2]), "value_vs_q": r.get("value_vs_q"), "records_with_values": with_values})
+        val = ""
+        if held_index is not None:  # (after the clock: the epoch's steps/s stay those of training)
+            rep = V.evaluate(model, buf, held_index, batch=a.batch, amp=amp, with_q=with_values > 0)
+            epochs[-1]["validation"] = rep["overall"]
+            o = rep["overall"]
+            fmt = lambda x: "-" if x is None else f"{x:.4f}"  # noqa: E731
+            val = f"; val policy {fmt(o['policy_ce'])} top1 {fmt(o['policy_top1'])} value {fmt(o['value_mse_z'])}"
         log(f"epoch {ep + 1}/{a.epochs}: loss {r['loss'][0]:.4f} policy {r['loss'][1]:.4f} value {r['loss'][2]:.4f} "
-            f"({r['steps']} steps, {r['samples'] / dt if dt > 0 else 0:.0f} samples/s)")
+            f"({r['steps']} steps, {r['samples'] / dt if dt > 0 else 0:.0f} samples/s){val}")
     buf.close()
 
     os.makedirs(a.save_dir, exist_ok=True)
@@ -384,6 +427,8 @@ def main(argv=None) -> int:
     if a.out:
         summary = {"iteration": iteration, "records": sum(e["samples"] for e in epochs[:1]), "loss": "dense" if a.dense_loss else "sparse",
                    "amp": amp, "batch": a.batch, "value_mix": a.value_mix, "epochs": epochs, "checkpoint": ck_path, "weights": weights}
+        if held_index is not None:
+            summary.update(holdout_fraction=a.holdout_fraction, holdout_seed=a.holdout_seed, held_out_records=int(held_index.size))
         with open(a.out, "w") as f:
             json.dump(summary, f, indent=1)
     return 0

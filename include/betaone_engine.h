@@ -32,9 +32,10 @@ extern "C" {
  * the search's root value -- bo_replay_add_game_values, bo_replay_values, bo_replay_sample_sparse_q, bo_train_loss_forward_mix,
  * bo_train_loss_backward_mix -- additions only; 10: perft on the device -- bo_perft, bo_perft_result -- additions only; 11: endgame
  * tablebases on the device -- bo_tb_create, bo_tb_build, bo_tb_verify, bo_tb_stats, bo_tb_download, bo_tb_upload, bo_tb_probe,
- * bo_tb_destroy -- additions only).  A caller checks
+ * bo_tb_destroy -- additions only; 12: held-out validation metrics on the device -- bo_train_metrics and the BO_METRIC_* columns --
+ * additions only).  A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 11
+#define BO_ABI_VERSION 12
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -550,6 +551,43 @@ int bo_train_loss_backward_mix(int32_t n, int32_t W, const void *logits_dev, int
                                const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, const float *q_dev,
                                const float *mix_dev, const float *row_stats_dev, const float *grad_out_dev, void *dlogits_dev,
                                void *dvalue_dev, void *stream);
+
+/* ---- (ABI 12, additions) held-out validation metrics: csrc/bo_metrics.h ---------------------------------------------------------------
+ * What a net's logits [n,4672] and value [n] say about records it was not trained on, with the inputs of bo_train_loss_forward (the
+ * same dtypes, float32 arithmetic) plus q [n] float32 (NULL: no root values, se_q is 0) and bucket [n] int32 (NULL: every row is
+ * bucket 0; a row whose id is outside [0, n_buckets) is counted nowhere).
+ * rows [n][BO_METRIC_ROW_COLS] float32 (device, written): one record per row, columns BO_METRIC_ROW_*.  With the row's valid entries e
+ * (0 <= pi_idx < 4672), p = softmax(logits row) and i* the valid entry with the largest pi_val (ties: the lowest action):
+ *   BAD                a logit is NaN, +inf or -inf, or the value is NaN: every other column of the record is then 0
+ *   HAS_POLICY         the row has a valid entry (and is not bad); without one the policy columns RANK .. P_SUPPORT are 0
+ *   DECISIVE           z != 0
+ *   RANK               actions a with logit[a] > logit[i*], or equal and a < i* (stored values compared: exact in every dtype)
+ *   TOP1, TOP3, TOP5   RANK < 1, 3, 5
+ *   ARGMAX_IN_SUPPORT  the net's argmax (the lowest action among equal maxima) is a valid entry of the row
+ *   CE                 -sum_e pi_val[e] log p[pi_idx[e]]: the bits of bo_train_loss_forward's row_stats[b][2] on the same inputs
+ *   TARGET_ENTROPY     -sum_e pi_val[e] log pi_val[e] over pi_val[e] > 0;   NET_ENTROPY  -sum_a p[a] log p[a]
+ *   P_TOP, P_SUPPORT   p[i*], sum_e p[pi_idx[e]]
+ *   SE_Z, SE_Q, ABS_V  (v - z)^2, (v - q)^2, |v|;   SIGN_OK  z != 0 and v z > 0;   Z, V  the outcome and the value themselves
+ * accum [n_buckets][BO_METRIC_COLS] float64 (device, ADDED TO -- zero it before a pass): column N_ROWS counts the bucket's rows that are
+ * not bad, every later column c is the sum of row column c - 1 over the bucket's rows, in a fixed order (bit-reproducible).  The
+ * counts are sums of small integers in float64: exact, whatever the split into batches.  Nothing is read back: a validation pass needs
+ * no host synchronisation before its end.  Asynchronous on `stream`; capturable. */
+enum {
+    BO_METRIC_ROW_BAD = 0, BO_METRIC_ROW_HAS_POLICY, BO_METRIC_ROW_DECISIVE, BO_METRIC_ROW_RANK, BO_METRIC_ROW_TOP1, BO_METRIC_ROW_TOP3,
+    BO_METRIC_ROW_TOP5, BO_METRIC_ROW_ARGMAX_IN_SUPPORT, BO_METRIC_ROW_CE, BO_METRIC_ROW_TARGET_ENTROPY, BO_METRIC_ROW_NET_ENTROPY,
+    BO_METRIC_ROW_P_TOP, BO_METRIC_ROW_P_SUPPORT, BO_METRIC_ROW_SE_Z, BO_METRIC_ROW_SE_Q, BO_METRIC_ROW_ABS_V, BO_METRIC_ROW_SIGN_OK,
+    BO_METRIC_ROW_Z, BO_METRIC_ROW_V, BO_METRIC_ROW_COLS
+};
+enum {
+    BO_METRIC_N_ROWS = 0, BO_METRIC_N_BAD, BO_METRIC_N_POLICY_ROWS, BO_METRIC_N_DECISIVE, BO_METRIC_SUM_RANK, BO_METRIC_SUM_TOP1,
+    BO_METRIC_SUM_TOP3, BO_METRIC_SUM_TOP5, BO_METRIC_SUM_ARGMAX_IN_SUPPORT, BO_METRIC_SUM_CE, BO_METRIC_SUM_TARGET_ENTROPY,
+    BO_METRIC_SUM_NET_ENTROPY, BO_METRIC_SUM_P_TOP, BO_METRIC_SUM_P_SUPPORT, BO_METRIC_SUM_SE_Z, BO_METRIC_SUM_SE_Q, BO_METRIC_SUM_ABS_V,
+    BO_METRIC_SUM_SIGN_OK, BO_METRIC_SUM_Z, BO_METRIC_SUM_V, BO_METRIC_COLS
+};
+int bo_train_metrics(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
+                     const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, const float *q_dev /* may be NULL */,
+                     const int32_t *bucket_dev /* may be NULL */, int32_t n_buckets, float *rows_dev /* [n][BO_METRIC_ROW_COLS] */,
+                     double *accum_dev /* [n_buckets][BO_METRIC_COLS], added to */, void *stream);
 
 /* ---- (ABI 6, additions) PGN pretraining: csrc/bo_pgn.h --------------------------------------------------------------------------
  * Replaces the reference's PGNDataset (train.py:81-160: python-chess reads the games, parses SAN and encodes 120 planes per position in
