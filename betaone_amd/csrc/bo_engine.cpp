@@ -650,6 +650,15 @@ extern "C" int bo_search_stop(bo_engine *e, const int32_t *stop_mask, int32_t *s
     return BO_OK;
 }
 
+extern "C" int bo_search_close(bo_engine *e, void *stream) {
+    if (!e) return fail(BO_E_ARG, "null engine");
+    if (e->fast) return fail(BO_E_CONFIG, "bo_search_close: reference-semantics engines only");
+    if (e->d.c.root_q) return fail(BO_E_STATE, "bo_search_close: root values are on (a closed search's q values lack the last evaluation)");
+    e->prefetch_valid = false;  // (as a step: a prefetched result block is older than the closed searches)
+    RT(RT_LAUNCH(bo_k_search_close, e->d.c.G, stream, e->d));
+    return BO_OK;
+}
+
 // the result kernel and the copy of its block, enqueued (no wait)
 static int ship(bo_engine *e, int *dst_a, const int *src_a, size_t n_a, int *dst_b, const int *src_b, size_t n_b, void *stream) {
     const size_t n = n_a > n_b ? n_a : n_b;
@@ -1766,6 +1775,16 @@ extern "C" int bo_train_metrics(int32_t n, int32_t W, const void *logits_dev, in
 }
 
 // ---- introspection -----------------------------------------------------------------------------------------
+extern "C" int bo_debug_search_state(bo_engine *e, int32_t *out, void *stream) {
+    if (!e || !out) return fail(BO_E_ARG, "bad arguments");
+    if (e->fast) return fail(BO_E_CONFIG, "bo_debug_search_state: reference-semantics engines only");
+    const size_t G = (size_t)e->d.c.G;
+    const int *src[5] = {e->d.phase, e->d.sims_done, e->d.rows, e->d.req_node, e->d.n_nodes};
+    for (int k = 0; k < 5; k++) RT(rt_d2h(out + k * G, src[k], G * 4, stream));
+    RT(rt_sync(stream));
+    return BO_OK;
+}
+
 extern "C" int bo_debug_tree(bo_engine *e, int slot, bo_node *out, int32_t cap, int32_t *n_nodes, void *stream) {
     if (!e || slot < 0 || slot >= e->d.c.G || !n_nodes) return fail(BO_E_ARG, "bad arguments");
     const EngCfg &c = e->d.c;

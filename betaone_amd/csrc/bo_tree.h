@@ -1197,6 +1197,39 @@ BO_KERNEL void bo_k_stop(Eng e, const int *mask) {
     }
 }
 
+// Close searches that wait for their LAST leaf evaluation, without that evaluation.  A game with phase RUN, a leaf requested
+// (req_node > 0), no pending rows and S - sims_done <= B would, once the row arrived, go through step_body like this: apply_leaf
+// (writes the ul_* cache and eval_slot only), select_leaf (the tree is as the previous descent left it: the same leaf), the run
+// (leaf, cnt = S - sims_done) and the flush -- the leaf's children are created with 0 visits, and backup_run adds 1 to n_visits of
+// the leaf and of every ancestor up to the root cnt times -- then PH_DONE.  pi, the best move and the played move read the visit
+// counts of the root's children only (result_body): those cnt increments along the parent links are applied here, the evaluation's
+// own products (the leaf's expansion, the q values on the path) are not.  The tree is rebuilt by the next search (root_prepare).
+// Every other game -- done, idle, mid-burst after a terminal yield (req_node < 0), waiting for its root's row, more than one batch
+// to go -- is left exactly as it is.
+BO_KERNEL void bo_k_search_close(Eng e) {
+    const int g = bo_block(), lane = bo_lane();
+    if (e.phase[g] != PH_RUN) return;
+    const size_t no = NOFF(e, g);
+    const int req = e.req_node[g], n_nodes = e.n_nodes[g];
+    const int cnt = e.c.S - e.sims_done[g];
+    if (req <= 0 || req >= n_nodes || e.rows[g] != 0 || e.n_runs[g] != 0 || e.n_ul[g] != 0 || cnt < 1 || cnt > e.c.B) return;
+    // the expansion the flush would have made: it is skipped, but a tree too small for it is reported all the same
+    int c = e.widen_lut[cnt];
+    const int nl = e.req_nlegal[g];
+    if (c <= 0 || c > nl) c = nl;
+    if (c > e.c.CH_MAX) c = e.c.CH_MAX;
+    const int flags = n_nodes + c > e.c.NCAP ? ST_NODE_OVERFLOW : 0;
+    int d = 0;
+    for (int x = req; x >= 0 && x < n_nodes && d < BO_PATH_CAP; x = e.parent[no + x], d++)  // backup_run's walk (wave-uniform)
+        if (lane == 0) e.n_visits[no + x] += cnt;
+    bo_sync();
+    if (lane == 0) {
+        e.sims_done[g] = e.c.S; e.rows[g] = 0; e.n_runs[g] = 0; e.n_ul[g] = 0;
+        e.req_node[g] = -1; e.phase[g] = PH_DONE;
+        if (flags) e.status[g] |= flags;
+    }
+}
+
 // Two small blocks of words between device memory and PINNED, device-mapped host memory, by the compute queue itself: the turn of a
 // ply (result block out, sampled actions and go flags in, root info out) then has no copy commands between its kernels -- each
 // hipMemcpyAsync was ~10-50 us of runtime work plus a blit kernel of its own on the path the device idles through.  Either pair may be

@@ -101,6 +101,7 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_step_heads": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p]),
     "bo_search_poll": (C.c_int, [C.c_void_p, _I32P, _I32P, _I32P, C.c_void_p]),
     "bo_search_stop": (C.c_int, [C.c_void_p, _I32P, _I32P, C.c_void_p]),
+    "bo_search_close": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bo_search_result": (C.c_int, [C.c_void_p, _I32P, _I32P, _F32P, _I32P, _I32P, _I32P, C.c_void_p]),
     "bo_play": (C.c_int, [C.c_void_p, _I32P, C.c_void_p]),
     "bo_game_export": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BoPosition), _I32P, C.c_int32, _I32P, C.c_void_p]),
@@ -208,6 +209,7 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
 # include/betaone_lab.h: introspection for the parity tests and in-kernel timing for bench.py / scripts/ (same library, not the boundary)
 _LAB_SYMBOLS = {
     "bo_debug_tree": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BoNode), C.c_int32, _I32P, C.c_void_p]),
+    "bo_debug_search_state": (C.c_int, [C.c_void_p, _I32P, C.c_void_p]),
     "bo_debug_fast": (C.c_int, [C.c_void_p, C.c_int, _I32P, C.c_int32, _I32P, C.c_void_p]),
     "bo_event_pair_overhead": (C.c_int, [_F64P, C.c_int32, C.c_void_p]),
     "bo_nn_b1_profile": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.c_int]),
@@ -233,7 +235,7 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 12  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 13  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
 # BO_METRIC_ROW_* / BO_METRIC_* of include/betaone_engine.h by name (bo_train_metrics; tests/test_validate_emu.py compares with the header)
 METRIC_ROW = {name: k for k, name in enumerate((
@@ -462,6 +464,11 @@ class Engine:
         self._check(self.lib.bo_search_stop(self.h, _p(m) if m is not None else None, _p(done), stream))
         return done
 
+    def search_close(self, stream: int = 0) -> None:
+        """Finish every search that waits for its LAST leaf evaluation without it (bo_search_close): the remaining visits are counted
+        along the requested leaf's path, the leaf is not expanded, no q moves; every other search is left as it is.  Nothing waits."""
+        self._check(self.lib.bo_search_close(self.h, stream))
+
     def result(self, stream: int = 0) -> Dict[str, np.ndarray]:
         G = self.G
         out = dict(n=np.zeros(G, np.int32), idx=np.zeros((G, RES_CAP), np.int32), val=np.zeros((G, RES_CAP), np.float32),
@@ -613,6 +620,12 @@ class Engine:
         self._check(self.lib.bo_debug_tree(self.h, slot, arr, n.value, C.byref(n), stream))
         return [dict(parent=a.parent, n=a.n_visits, q=np.float32(a.q_value), prior=np.float32(a.prior), move=a.move,
                      n_children=a.n_children, first_child=a.first_child, terminal=a.terminal) for a in arr[:n.value]]
+
+    def debug_search_state(self, stream: int = 0) -> Dict[str, np.ndarray]:
+        """Per slot, between two steps: phase, sims_done, pending rows, req_node (-1: no evaluation requested), n_nodes."""
+        out = np.zeros((5, self.G), np.int32)
+        self._check(self.lib.bo_debug_search_state(self.h, _p(out), stream))
+        return dict(zip(("phase", "sims_done", "rows", "req_node", "n_nodes"), out))
 
     def status(self, stream: int = 0) -> Dict[str, np.ndarray]:
         names = ["status", "evals", "flushes", "term_sims", "levels", "children_scanned"]

@@ -163,6 +163,10 @@ class Rollout:
         self.resign_t = np.float32(resign_threshold) if self.resign else None
         self.resign_k, self.resign_f = int(resign_plies), float(resign_check_fraction)
         self.values = self.resign or bool(record_values)
+        # close_allowed: a search's expected iterations may end with the close kernel in place of the last evaluation (_eval_and_step_n).
+        # Reference search only, and only while nobody reads root values (resignation, record_values, analysis): the closed tree lacks
+        # the last leaf's expansion and q update.  BETAONE_CLOSE_LAST_EVAL=0 keeps the evaluation (A/B runs).
+        self.close_allowed = (not fast) and not self.values and os.environ.get("BETAONE_CLOSE_LAST_EVAL", "1") != "0"
         self.device = E.runtime_device(device)
         # `stream`: every launch of this Rollout goes to that HIP stream (CohortRollout: one stream per cohort of games, so that
         # one cohort's tower runs while another's tree step / head kernels / host turn are in progress); None = torch's current one
@@ -200,6 +204,10 @@ class Rollout:
         self.expected_evals = math.ceil(self.S / self.L) if self.fast else 1 + math.ceil(self.S / self.B)
         self.games: List[Optional[GameState]] = [None] * self.G
         self.use_graph = bool(use_graph) and self.device.type == "cuda"
+        # close_last_eval: on where the iterations run as captured graphs -- the product path.  The eager loop (use_graph=False) is the
+        # path on which a caller watches every evaluation (seam recordings replayed through the oracle, which evaluates every leaf as
+        # the reference does): it keeps the last evaluation unless this is set by hand.
+        self.close_last_eval = self.close_allowed and self.use_graph
         self._graph = None
         self._graphs_n = {}         # n -> (graph of n back-to-back evaluate->step iterations, its output tensors)
         self._logits = self._value = None
@@ -359,34 +367,47 @@ class Rollout:
 
     MAX_GRAPH_ITERATIONS = 12
 
-    def _eval_and_step_n(self, n: int):
+    def _eval_and_step_n(self, n: int, close: Optional[bool] = None):
         """n x (net forward -> tree step).  With graphs: ONE launch of a graph that holds the n iterations back to back (between
-        two graph launches the device idles ~8 us -- profiles/r02_trace_percentiles.md -- between two nodes of one graph < 1 us)."""
+        two graph launches the device idles ~8 us -- profiles/r02_trace_percentiles.md -- between two nodes of one graph < 1 us).
+        With close_last_eval and n >= 2 the last of the n iterations is the close kernel instead (Engine.search_close): a search's
+        last evaluation only adds the remaining visits along the leaf's path as far as pi, the move and the records can tell, so
+        those visits are counted without it -- n - 1 evaluations; a game the close finds in any other state is left running and
+        finished by the single iterations behind the poll / the turn's redo."""
+        if close is None:
+            close = self.close_last_eval
+        close = bool(close) and n >= 2
+        iters = n - 1 if close else n
         if n <= 1 or not self.use_graph:
-            for _ in range(n):
+            for _ in range(iters):
                 self._eval_and_step()
+            if close:
+                self.eng.search_close(self._stream())
             return
         if n > self.MAX_GRAPH_ITERATIONS:  # (fast mode with few leaves per step: hundreds of evaluations per search)
             while n > 0:
                 k = min(n, self.MAX_GRAPH_ITERATIONS)
-                self._eval_and_step_n(k)
+                self._eval_and_step_n(k, close and k == n)  # (only the last chunk ends with the close)
                 n -= k
             return
-        g = self._graphs_n.get(n)
+        key = (n, True) if close else n
+        g = self._graphs_n.get(key)
         if g is None:
             if self._graph is None:
                 self._capture()  # warms the allocator / MIOpen up as well
             cg, keep = torch.cuda.CUDAGraph(), []
             with torch.cuda.graph(cg, capture_error_mode=CAPTURE_MODE):
-                for _ in range(n):
+                for _ in range(iters):
                     self._stamp(1)
                     logits, value = self._forward()
                     self._stamp(2)
                     self._step_after(logits, value)
                     self._stamp(3)
                     keep.append((logits, value))
-            g = self._graphs_n[n] = (cg, keep)
-        self.n_forward += n
+                if close:
+                    self.eng.search_close(self._stream())
+            g = self._graphs_n[key] = (cg, keep)
+        self.n_forward += iters
         g[0].replay()
 
     # ---- game slots ---------------------------------------------------------------------------------

@@ -33,9 +33,10 @@ extern "C" {
  * bo_train_loss_backward_mix -- additions only; 10: perft on the device -- bo_perft, bo_perft_result -- additions only; 11: endgame
  * tablebases on the device -- bo_tb_create, bo_tb_build, bo_tb_verify, bo_tb_stats, bo_tb_download, bo_tb_upload, bo_tb_probe,
  * bo_tb_destroy -- additions only; 12: held-out validation metrics on the device -- bo_train_metrics and the BO_METRIC_* columns --
- * additions only).  A caller checks
+ * additions only; 13: a search that waits for its last leaf evaluation is finished without it -- bo_search_close -- addition only).
+ * A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 12
+#define BO_ABI_VERSION 13
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -153,6 +154,17 @@ int bo_search_poll(bo_engine *e, int32_t *n_running, int32_t *n_requested, int32
  * marked finished -- bo_search_result then returns what the reference returns for NUM_SIMULATIONS = sims_done[g]
  * (optional out, [G] int32: simulations completed per game).  Reference-semantics engines only.  Synchronises. */
 int bo_search_stop(bo_engine *e, const int32_t *stop_mask, int32_t *sims_done, void *stream);
+
+/* (ABI 13) Finish, WITHOUT its evaluation, every running search that waits for its last leaf evaluation: a leaf is requested, no rows
+ * are pending and NUM_SIMULATIONS - sims_done <= MCTS_BATCH_SIZE.  The step behind that evaluation would re-select the leaf for the
+ * remaining simulations, expand it and back its value up (mcts.py:247-257, 291-295): every node from the leaf up to the root gains that
+ * many visits.  Here the visits are added and the search is marked finished; the leaf is not expanded and no q_value moves.
+ * bo_search_result, both turns and the records -- which read the visit counts of the root's children (mcts.py:259-280) -- give what
+ * they give behind the evaluated step; root values and the tree below the root do not (BO_E_STATE with bo_engine_root_values on).
+ * Every other search -- finished, idle, waiting for its root's evaluation, in the middle of a run of terminal simulations, or with more
+ * than one batch to go -- is left untouched: the caller goes on with bo_step as before.  Reference-semantics engines only.
+ * Asynchronous on `stream`; capturable. */
+int bo_search_close(bo_engine *e, void *stream);
 
 /* Result of the finished searches (mcts.py:259-280): sparse pi (res_n[g] entries of
  * (action index, probability) at [g*BO_RES_CAP ..]), best move as action index (-1: no legal

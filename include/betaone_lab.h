@@ -26,6 +26,9 @@ typedef struct {
     int32_t terminal;  /* -1 never visited as leaf, 0 no, 1 mate, 2 draw */
 } bo_node;
 int bo_debug_tree(bo_engine *e, int slot, bo_node *out, int32_t cap, int32_t *n_nodes, void *stream);
+/* The search state of every slot between two steps, out [5][G] int32: phase (0 idle, 1 running, 2 done), sims_done, pending rows, the
+ * node whose evaluation is requested (-1: none), nodes in the tree.  Reference-semantics engines.  Synchronises. */
+int bo_debug_search_state(bo_engine *e, int32_t *out, void *stream);
 
 /* FAST mode, per game [G]: record granules requested by PUCT descents so far (x BO_FAST_GRANULE_BYTES = bytes the select
  * path moved), path nodes updated by the backup (x 16 B; with 12 B x children_scanned + 8 B x levels of bo_engine_status
