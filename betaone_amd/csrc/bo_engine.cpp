@@ -104,6 +104,7 @@ struct bo_engine {
     float resign_t = 0.0f;
     int resign_k = 1;
     float *d_root_value = nullptr;                       // bo_search_root_value's staging [G]
+    TbTable *d_tb_tabs = nullptr;                        // bo_engine_tablebases: room for TB_MAX_TABLES descriptors (Eng.tb_tabs points here)
     std::vector<int> turn_want;
     bool turn_outstanding = false, ev_turn_made = false;
     rt_event ev_turn{};
@@ -308,6 +309,9 @@ extern "C" int bo_engine_create(const bo_config *cfg, int device, bo_engine **ou
     rc |= e->alloc(&d.prof, G * BO_PROF_SLOTS);
     rc |= e->alloc(&d.resign_cnt, 2 * G); rc |= e->alloc(&e->d_root_value, G);
     if (!rc) rt_memset(d.resign_cnt, 0, 2 * G * 4, nullptr);
+    rc |= e->alloc(&e->d_tb_tabs, (size_t)TB_MAX_TABLES); rc |= e->alloc(&d.tb_stat, 3 * G);
+    if (!rc) rt_memset(d.tb_stat, 0, 3 * G * 4, nullptr);
+    d.tb_tabs = e->d_tb_tabs; d.tb_n = 0; d.tb_flags = 0;
     d.played_now = nullptr;
     if (fast) {
         FastW &f = e->f;
@@ -598,7 +602,9 @@ static int step_launch(bo_engine *e, const float *policy_dev, const float *value
 #endif
         RT(RT_LAUNCH(bo_k_fw_leaf, rows, stream, e->d, e->f, nn_in_dev));
     } else {
-        RT(RT_LAUNCH(bo_k_step, e->d.c.G, stream, e->d, policy_dev, value_dev, policy_kind, nn_in_dev, vt));
+        // (the probing instantiation only where the search probes: without it the default kernel runs, the one there was before the tables)
+        if (e->d.tb_n > 0 && (e->d.tb_flags & TBF_SEARCH)) RT(RT_LAUNCH(bo_k_step_tb, e->d.c.G, stream, e->d, policy_dev, value_dev, policy_kind, nn_in_dev, vt));
+        else RT(RT_LAUNCH(bo_k_step, e->d.c.G, stream, e->d, policy_dev, value_dev, policy_kind, nn_in_dev, vt));
     }
     return BO_OK;
 }
@@ -3240,5 +3246,42 @@ extern "C" int bo_tb_probe(bo_tb *const *tbs, int32_t n_tb, const bo_position *p
     const int rc2 = rt_sync(stream);
     rt_free(d_tabs); rt_free(d_pos); rt_free(d_codes); rt_free(d_status);
     if (rc || rc2) return fail(BO_E_HIP, std::string("bo_tb_probe: ") + rt_errstr(rc ? rc : rc2));
+    return BO_OK;
+}
+
+// ---- tablebases in the search (bo_tree.h: step_body<true>, root_prepare) -------------------------------------------------------------
+extern "C" int bo_engine_tablebases(bo_engine *e, bo_tb *const *tbs, int32_t n_tb, int32_t flags) {
+    if (!e || n_tb < 0 || (n_tb && !tbs)) return fail(BO_E_ARG, "bo_engine_tablebases: bad arguments");
+    if (n_tb > TB_MAX_TABLES) return fail(BO_E_ARG, "bo_engine_tablebases: at most " + std::to_string(TB_MAX_TABLES) + " tables");
+    if (flags & ~(TBF_SEARCH | TBF_ADJUDICATE)) return fail(BO_E_ARG, "bo_engine_tablebases: unknown flag bits (1 probe in the search, 2 adjudicate at the root)");
+    if (e->fast) return fail(BO_E_CONFIG, "bo_engine_tablebases: reference-semantics engines only");
+    std::vector<TbTable> tabs;
+    for (int i = 0; i < n_tb; i++) {
+        if (!tbs[i]) return fail(BO_E_ARG, "bo_engine_tablebases: null table");
+        if (tbs[i]->device != e->device) return fail(BO_E_ARG, "bo_engine_tablebases: the table " + tbs[i]->name + " lives on another device than the engine");
+        if (!tbs[i]->complete) return fail(BO_E_STATE, "bo_engine_tablebases: the table " + tbs[i]->name + " is not complete");
+        tabs.push_back(tbs[i]->self);
+    }
+    RT(rt_set_device(e->device));
+    if (n_tb) {
+        RT(rt_h2d(e->d_tb_tabs, tabs.data(), tabs.size() * sizeof(TbTable), nullptr));
+        RT(rt_sync(nullptr));  // (tabs is a vector of this frame)
+    }
+    e->d.tb_n = n_tb;
+    e->d.tb_flags = n_tb ? flags : 0;
+    return BO_OK;
+}
+
+extern "C" int bo_engine_tb_stats(bo_engine *e, int32_t *tb_nodes, int32_t *tb_sims, int32_t *adjudicated, void *stream) {
+    if (!e) return fail(BO_E_ARG, "null engine");
+    const size_t G = (size_t)e->d.c.G;
+    std::vector<int> h(3 * G);
+    RT(rt_d2h(h.data(), e->d.tb_stat, 3 * G * 4, stream));
+    RT(rt_sync(stream));
+    for (size_t g = 0; g < G; g++) {
+        if (tb_nodes) tb_nodes[g] = h[3 * g];
+        if (tb_sims) tb_sims[g] = h[3 * g + 1];
+        if (adjudicated) adjudicated[g] = h[3 * g + 2];
+    }
     return BO_OK;
 }

@@ -25,6 +25,7 @@
 //     [G,120,8,8] batch and the step is capturable in a hipGraph.
 #pragma once
 #include "bo_chess.h"
+#include "bo_tb_probe.h"
 #include <math.h>
 
 #define BO_CH_CAP 32     // max children created per expansion (int(WIDEN*sqrt(BATCH)) must fit)
@@ -94,7 +95,16 @@ struct Eng {
     int *resign_cnt;                  // [G][2] resignation: consecutive own searches below the threshold, per ply parity (committed by bo_k_turn_play)
     unsigned long long *prof;         // [G][BO_PROF_SLOTS] cycles: apply, select, first-visit (movegen+draw rules), terminal backups, encode, flush, total; steps,
                                       // loop iterations, first visits.  profile = N > 1 counts only game-steps longer than N cycles
+    // endgame tablebases in the search (bo_engine_tablebases; "Tablebases in the search" below)
+    const TbTable *tb_tabs;           // [tb_n] device: the set's descriptors (the tables themselves belong to the caller)
+    int tb_n;                         // 0: off
+    int tb_flags;                     // bit 0 (TBF_SEARCH): probe a leaf at its first visit; bit 1 (TBF_ADJUDICATE): probe every new root
+    int *tb_stat;                     // [G][3] table leaves created, simulations they absorbed (both since the game's set-up), the root was adjudicated
 };
+enum { TBF_SEARCH = 1, TBF_ADJUDICATE = 2 };
+// node codes of a table leaf (e.term; bo_debug_tree reports them): the side to move at the leaf wins / loses / draws by the table.  The
+// leaf's min(k, 512) lives in its eval_slot, which a terminal node has no other use for.
+enum { TERM_TB_WIN = 3, TERM_TB_LOSS = 4, TERM_TB_DRAW = 5 };
 
 #define NOFF(e, g) ((size_t)(g) * (size_t)(e).c.nstride)
 
@@ -442,8 +452,13 @@ BO_DEV float bo_div_count(float x, float fn, float y) {
 // where the two paths part (the levels above are the same nodes: one set), and when the node at that level turns from one
 // path's child to the other's -- and the other path's deeper levels still choose what they chose -- the sets are swapped and
 // the loop goes on.  Everything a simulation does to the statistics is the same operation in the same order as before.
+// TB (the probing step kernel): a table leaf's value depends on its k, which the sibling logic below does not know, and the simulations
+// table leaves absorb are counted apart -- so a burst that starts in a table leaf stays in it (db < 0: no second path, no sibling), and
+// one that starts in a rule leaf treats table leaves as unknown children.  Ending a burst early is always allowed.
+template <bool TB>
 BO_DEV int terminal_burst(const Eng &e, int g, const int *path, int d, float v, int sims_left, float *lds, bool *staged,
                           const int *pb = nullptr, int db = 0, float vb = 0.0f, int *n_swaps = nullptr) {
+    const bool lone = TB && db < 0;
     const size_t no = NOFF(e, g);
     const int lane = bo_lane(), grp = lane >> 4, j = lane & 15;
     // common nodes of the two paths: path[0 .. c-1] == pb[0 .. c-1]; they part at level c - 1 (the children of path[c - 1])
@@ -480,6 +495,7 @@ BO_DEV int terminal_burst(const Eng &e, int g, const int *path, int d, float v, 
     const float cp = have ? e.prior[no + my_fc + j] : 0.0f;
     // at the last level any child that is ALREADY KNOWN to be a terminal leaf may take the next simulation
     int cterm = (have && last && e.n_children[no + my_fc + j] == 0) ? (int)e.term[no + my_fc + j] : -1;
+    if (TB && (lone || cterm >= TERM_TB_WIN)) cterm = -1;
     // the other path's register set: levels >= c (its own nodes); its chosen child also at level c - 1 (same node, other child)
     int b_cn = 0, b_cterm = -1;
     float b_cq = 0.0f, b_cp = 0.0f;
@@ -490,6 +506,7 @@ BO_DEV int terminal_burst(const Eng &e, int g, const int *path, int d, float v, 
         b_cq = b_have ? e.q[no + b_fc + j] : 0.0f;
         b_cp = b_have ? e.prior[no + b_fc + j] : 0.0f;
         b_cterm = (b_have && grp == db - 1 && e.n_children[no + b_fc + j] == 0) ? (int)e.term[no + b_fc + j] : -1;
+        if (TB && b_cterm >= TERM_TB_WIN) b_cterm = -1;
     }
     float v_cur = v, v_oth = vb;
     int d_oth = db;
@@ -937,6 +954,18 @@ BO_DEV void apply_leaf(const Eng &e, int g, int leaf, const float *row, int kind
 // simulation loop until the game needs a new evaluation or its search is complete, and write the
 // requested leaf's planes into NN input row g.
 // (returns the game's node count when it leaves)
+//
+// Tablebases in the search (TB = true: bo_k_step_tb, launched when TBF_SEARCH is set; the default kernel compiles none of it).  A leaf
+// that the rules leave ongoing at its first visit, with at most TB_MAX_MEN men and no castling rights, is looked up (tb_lookup: one
+// 2-byte load, wave-uniform like the leaf).  A draw, or a mate in k with halfmove + k <= 100 (it arrives before a fifty-move claim can),
+// makes it a TABLE LEAF: a terminal leaf with the value 0 or, as seen by the side that just moved like the rule mate's 1.0,
+// +m(k) when the side to move is mated (k even) and -m(k) when it mates (k odd), m(k) = 1 - min(k, 512) / 1024 (exact in binary32;
+// m(0) = 1 is the rule mate).  The root is never probed here: a covered root is searched like any other.
+BO_DEV float tb_leaf_value(int t, int kc) {
+    const float m = 1.0f - (float)kc * (1.0f / 1024.0f);
+    return t == TERM_TB_LOSS ? m : t == TERM_TB_WIN ? -m : 0.0f;
+}
+template <bool TB>
 BO_DEV int step_body(const Eng &e, int g, const float *policy, const float *value, int kind, float *nn_in, StepShared &sh, const StepTail &vt) {
     const int lane = bo_lane();
     const size_t no = NOFF(e, g);
@@ -986,12 +1015,28 @@ BO_DEV int step_body(const Eng &e, int g, const float *policy, const float *valu
         n_iter++;
         BO_PROF(1)
         int t = e.term[no + leaf];
+        int tb_k = 0;  // a table leaf's min(k, 512)
+        if (TB && t >= TERM_TB_WIN) tb_k = (int)e.eval_slot[no + leaf];
         if (t < 0) {  // first visit: legal moves + is_terminal()  (mcts.py:235, cached per node)
             n_first++;
             const DPos P = e.npos[no + leaf];
             bool chk;
             const int n = bo_movegen(P, sh.moves, &chk);
             t = terminal_eval(e, g, sh.path, depth, P, sh.moves, n, chk, sh.moves2, sh.chain);
+            if constexpr (TB) {
+                const bool gate = t == 0 && leaf != 0 && (e.tb_flags & TBF_SEARCH) && bo_popc64(P.bb[BB_WHITE] | P.bb[BB_BLACK]) <= TB_MAX_MEN &&
+                                  !(P.flags & F_CASTLE_MASK);
+                if (bo_uniform(gate ? 1 : 0)) {
+                    const uint32_t code = tb_lookup(e.tb_tabs, e.tb_n, P.bb, pos_turn(P));
+                    const int k = (int)code - 2;
+                    if (code == 1u) t = TERM_TB_DRAW;
+                    else if (code >= 2u && code != TB_NO_TABLE && P.halfmove + k <= 100) t = (k & 1) ? TERM_TB_WIN : TERM_TB_LOSS;
+                    if (t != 0) {
+                        tb_k = t == TERM_TB_DRAW ? 0 : k < 512 ? k : 512;
+                        if (lane == 0) { e.eval_slot[no + leaf] = (short)tb_k; e.tb_stat[3 * g] += 1; }
+                    }
+                }
+            }
             if (lane == 0) e.term[no + leaf] = (signed char)t;
             if (t == 0) {  // it will be evaluated now: keep its ordered legal moves for apply_leaf
                 for (int j = lane; j < n; j += 64) e.req_moves[(size_t)g * BO_MAX_MOVES + j] = sh.moves[j];
@@ -1001,7 +1046,9 @@ BO_DEV int step_body(const Eng &e, int g, const float *policy, const float *valu
             BO_PROF(2)
         }
         if (t > 0) {  // mcts.py:235-238: terminal leaves absorb the simulation, no NN row
-            const float tv = t == 1 ? 1.0f : 0.0f;
+            float tv = t == 1 ? 1.0f : 0.0f;
+            const bool tb_leaf = TB && t >= TERM_TB_WIN;
+            if (tb_leaf) tv = tb_leaf_value(t, tb_k);
             int applied = 1;
             bool small = depth <= BO_BURST_LEVELS && BO_BURST_FITS(e.c.S);
             for (int k = 0; k < depth && small; k++) small = e.n_children[no + sh.path[k]] <= 16;
@@ -1009,11 +1056,12 @@ BO_DEV int step_body(const Eng &e, int g, const float *policy, const float *valu
             const int may = e.c.S - sims < term_budget ? e.c.S - sims : term_budget;
             if (small) {
                 const bool small_b = b_depth > 0 && e.c.burst_two != 0;  // the previous burst's path rides along (terminal_burst checks that it still fits)
-                applied = terminal_burst(e, g, sh.path, depth, tv, may, sh.probs, &burst_tables_staged, sh.bpath, small_b ? b_depth : 0, b_tv, &n_swaps);
+                applied = terminal_burst<TB>(e, g, sh.path, depth, tv, may, sh.probs, &burst_tables_staged, sh.bpath, tb_leaf ? -1 : small_b ? b_depth : 0, b_tv,
+                                             &n_swaps);
                 n_burst++; n_burst_sims += applied;
                 bo_sync();
                 if (lane <= depth) sh.bpath[lane] = sh.path[lane];
-                b_depth = depth; b_tv = tv;
+                b_depth = tb_leaf ? 0 : depth; b_tv = tv;  // (a table leaf's path does not ride along with a later burst)
                 bo_sync();
             }
             else { backup_run(e, g, leaf, tv, 1, sh.path2, &flags, sh.path, depth); n_general++; }  // deep or wide path: one simulation the general way
@@ -1021,6 +1069,7 @@ BO_DEV int step_body(const Eng &e, int g, const float *policy, const float *valu
             sims += applied;
             term_budget -= applied;
             if (lane == 0) e.stat_term_sims[g] += applied;
+            if (tb_leaf && lane == 0) e.tb_stat[3 * g + 1] += applied;
             BO_PROF(3)
             if (term_budget <= 0 && sims < e.c.S) break;  // yield: req stays -1, phase stays RUN
             continue;
@@ -1069,7 +1118,14 @@ BO_KERNEL void bo_k_step(Eng e, const float *policy, const float *value, int kin
     BO_SHARED StepShared sh;
     const int g = bo_block();
     if (e.phase[g] != PH_RUN) return;
-    step_body(e, g, policy, value, kind, nn_in, sh, vt);
+    step_body<false>(e, g, policy, value, kind, nn_in, sh, vt);
+}
+// the same with the table probe at a leaf's first visit (step_body<true>): launched in its place when TBF_SEARCH is set
+BO_KERNEL void bo_k_step_tb(Eng e, const float *policy, const float *value, int kind, float *nn_in, StepTail vt) {
+    BO_SHARED StepShared sh;
+    const int g = bo_block();
+    if (e.phase[g] != PH_RUN) return;
+    step_body<true>(e, g, policy, value, kind, nn_in, sh, vt);
 }
 
 // Prepare the root of game g's next search from the top of its position stack: reset the tree,
@@ -1094,7 +1150,18 @@ BO_DEV int root_prepare(const Eng &e, int g, StepShared &sh) {  // returns the r
     const int n = bo_movegen(P, sh.moves, &chk);
     if (lane == 0) sh.path[0] = 0;
     bo_sync();
-    const int t = terminal_eval(e, g, sh.path, 0, P, sh.moves, n, chk, sh.moves2, sh.chain);
+    int t = terminal_eval(e, g, sh.path, 0, P, sh.moves, n, chk, sh.moves2, sh.chain);
+    // Adjudication (TBF_ADJUDICATE): a new root that the rules leave ongoing and the tables cover as a draw, or as lost for the side to
+    // move, ends the game -- code 2, or 3 ("the side to move resigned").  No clock condition: the rule is tablebase.rescore's, so a run
+    // that adjudicates writes the records a plain run rescored afterwards would.  A won or an uncovered root is played on.
+    int adj = 0;
+    if (bo_uniform(((e.tb_flags & TBF_ADJUDICATE) && t == 0 && bo_popc64(P.bb[BB_WHITE] | P.bb[BB_BLACK]) <= TB_MAX_MEN && !(P.flags & F_CASTLE_MASK)) ? 1 : 0)) {
+        const uint32_t code = tb_lookup(e.tb_tabs, e.tb_n, P.bb, pos_turn(P));
+        if (code == 1u) t = 2;
+        else if (code >= 2u && code != TB_NO_TABLE && !((code - 2u) & 1u)) t = 3;
+        adj = t != 0;
+    }
+    if (lane == 0) e.tb_stat[3 * g + 2] = adj;
     for (int j = lane; j < n; j += 64) {
         e.root_moves[(size_t)g * BO_MAX_MOVES + j] = sh.moves[j];
         e.req_moves[(size_t)g * BO_MAX_MOVES + j] = sh.moves[j];
@@ -1158,6 +1225,7 @@ BO_KERNEL void bo_k_setup(Eng e, SetupArgs a) {
             e.trk_n[g] = ply + 1;
         }
         e.stat_evals[g] = e.stat_flushes[g] = e.stat_term_sims[g] = e.stat_levels[g] = e.stat_children_scanned[g] = 0;
+        e.tb_stat[3 * g] = e.tb_stat[3 * g + 1] = 0;
         e.resign_cnt[2 * g] = e.resign_cnt[2 * g + 1] = 0;
     }
     bo_sync();

@@ -77,8 +77,8 @@ def _records(ro: Rollout, fin: FinishedGame) -> List[SelfPlayData]:
 
 def run_self_play_games(model, game_ids: Sequence[int], seeds: Optional[Sequence[int]] = None,
                         n_slots: Optional[int] = None, start_fens: Optional[Sequence[Optional[str]]] = None,
-                        on_game=None, dense: bool = True, reload_model=None, on_records=None, rollout_kw: Optional[dict] = None
-                        ) -> Dict[int, Optional[List[SelfPlayData]]]:
+                        on_game=None, dense: bool = True, reload_model=None, on_records=None, rollout_kw: Optional[dict] = None,
+                        stats: Optional[dict] = None) -> Dict[int, Optional[List[SelfPlayData]]]:
     """Play len(game_ids) games, n_slots at a time, on one GPU.  Game i draws its Dirichlet noise and its
     moves from numpy.random.RandomState(seeds[i]) -- the stream the reference consumes after
     np.random.seed(seeds[i]) -- so results do not depend on n_slots or on which GPU a game lands on.
@@ -88,7 +88,9 @@ def run_self_play_games(model, game_ids: Sequence[int], seeds: Optional[Sequence
     as they exist (selfplay_main pickles them there and keeps an empty list, so an iteration's tuples never pile up in memory).
     reload_model() -> None | a new PolicyValueNet: polled once per ply; a returned model replaces the evaluate stage for every
     evaluation from the next ply on (main.py:147-148 hands weights to its workers through best_model.pth: betaone_amd.selfplay_main
-    watches that file).  rollout_kw: further Rollout arguments (resign_threshold, resign_plies, resign_check_fraction, record_values)."""
+    watches that file).  rollout_kw: further Rollout arguments (resign_threshold, resign_plies, resign_check_fraction, record_values,
+    tablebases, tb_search, tb_adjudicate).  stats: a dict that receives the run's counters (searches, and with tablebases the table
+    leaves, the simulations they absorbed and the adjudicated games)."""
     ids = list(game_ids)
     seeds = list(seeds) if seeds is not None else ids
     n_slots = min(n_slots or len(ids), len(ids))
@@ -121,6 +123,9 @@ def run_self_play_games(model, game_ids: Sequence[int], seeds: Optional[Sequence
             ro.play_ply(on_finished=finished, refill=next_game)
             _settle_status(ro, results, finished, next_game)
     finally:
+        if stats is not None:
+            stats.update(searches=ro.n_sims // max(1, ro.S), forwards=ro.n_forward, tb_nodes=ro.tb_nodes, tb_sims=ro.tb_sims,
+                         adjudicated=ro.n_adjudicated, finished=ro.n_finished)
         ro.close()
     return results
 

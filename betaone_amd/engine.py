@@ -204,6 +204,8 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_tb_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "bo_tb_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     "bo_tb_probe": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bo_engine_tablebases": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32]),
+    "bo_engine_tb_stats": (C.c_int, [C.c_void_p, _I32P, _I32P, _I32P, C.c_void_p]),
     "bo_tb_destroy": (None, [C.c_void_p]),
 }
 # include/betaone_lab.h: introspection for the parity tests and in-kernel timing for bench.py / scripts/ (same library, not the boundary)
@@ -235,7 +237,7 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 13  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 14  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
 # BO_METRIC_ROW_* / BO_METRIC_* of include/betaone_engine.h by name (bo_train_metrics; tests/test_validate_emu.py compares with the header)
 METRIC_ROW = {name: k for k, name in enumerate((
@@ -631,6 +633,26 @@ class Engine:
         names = ["status", "evals", "flushes", "term_sims", "levels", "children_scanned"]
         out = {k: np.zeros(self.G, np.int32) for k in names}
         self._check(self.lib.bo_engine_status(self.h, *[_p(out[k]) for k in names], stream))
+        return out
+
+    TB_SEARCH, TB_ADJUDICATE = 1, 2  # bo_engine_tablebases' flag bits
+
+    def tablebases(self, tables: Sequence = (), flags: int = 0):
+        """bo_engine_tablebases: the searches of this engine read `tables` (tablebase.Table objects, complete, on the engine's device) from
+        now on -- TB_SEARCH: probe leaves in the search, TB_ADJUDICATE: end a game at a root the tables give as drawn or lost.  No tables:
+        off.  The engine keeps the Tables alive; call it before a step is captured into a graph.  A bad argument raises ValueError."""
+        tables = list(tables)
+        arr = (C.c_void_p * max(1, len(tables)))(*[t.h for t in tables])
+        rc = self.lib.bo_engine_tablebases(self.h, arr, len(tables), int(flags))
+        if rc != 0:
+            msg = f"bo_engine_tablebases: {self.lib.bo_last_error().decode()}"
+            raise (ValueError if rc in (-1, -3) else EngineError)(msg)
+        self._tables = tables
+
+    def tb_stats(self, stream: int = 0) -> Dict[str, np.ndarray]:
+        """Per slot: table leaves created and simulations they absorbed since the game's set-up; whether the current root was adjudicated."""
+        out = {k: np.zeros(self.G, np.int32) for k in ("tb_nodes", "tb_sims", "adjudicated")}
+        self._check(self.lib.bo_engine_tb_stats(self.h, _p(out["tb_nodes"]), _p(out["tb_sims"]), _p(out["adjudicated"]), stream))
         return out
 
     def fast_options(self, tree_reuse=None, games_per_halfwave=None, select_flags=None):

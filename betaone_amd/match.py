@@ -2,7 +2,8 @@
 betaone_amd/match.py -- head-to-head matches between two networks on the GPU, and the AlphaGo Zero promotion gate.
 
     python -m betaone_amd.match BEST.pth CANDIDATE.pth --games N --slots G --cohorts K --sims S \\
-        [--openings FILE] [--open-plies P] [--t-final T] [--out match.json] [--promote DEST --threshold 0.55] [--pgn games.pgn]
+        [--openings FILE] [--open-plies P] [--t-final T] [--out match.json] [--promote DEST --threshold 0.55] [--pgn games.pgn] \\
+        [--tablebases DIR [--tb-search] [--tb-adjudicate]]
 
 Net A (the first checkpoint) and net B (the second) share ONE evaluate stage (fused_net.PairedNet): row g of every evaluation is
 evaluated by the net of the side to move at game g's root (bo_match_select sets the per-row selector on the device, right before each
@@ -19,7 +20,9 @@ the selector is computed from the real root either way, so the results never dep
 
 Results (JSON, printed): W/D/L from B's view, score, Elo difference -400 log10(1/s - 1) with a 95 % interval (pentanomial over
 opening pairs when openings are given, per-game trinomial otherwise), likelihood of superiority, and per game the opening, colours,
-UCI moves, result and termination.  --promote DEST writes B's state_dict to DEST (through a temporary file and os.replace) only when
+UCI moves, result and termination.  --tablebases DIR: both nets see the same endgame tables -- --tb-search scores covered leaves of
+every search from them, --tb-adjudicate ends a game at a position they give as drawn (a draw) or as lost for the side to move (a loss
+for that side; termination "adjudication", a PGN tag Termination "adjudication").  --promote DEST writes B's state_dict to DEST (through a temporary file and os.replace) only when
 B's score >= --threshold: main.py's best_model.pth convention with the AlphaGo Zero gate.
 """
 from __future__ import annotations
@@ -242,12 +245,15 @@ class MatchScheduler:
 
 # ---- the match ----------------------------------------------------------------------------------------------------------------------
 def game_result(fin, net_of_white: int) -> Tuple[float, str]:
-    """(B's score, termination) of a FinishedGame: terminal 1 = the side to move in the final position is mated."""
-    if fin.terminal == 1:
+    """(B's score, termination) of a FinishedGame: terminal 1 = the side to move in the final position is mated; terminal 3 = it lost
+    without being mated (the tablebases give the position as lost: "adjudication").  A draw the tablebases called is an adjudication too."""
+    adjudicated = bool(getattr(fin, "adjudicated", False))
+    if fin.terminal in (1, 3):
         white_won = fin.positions[-1].turn != 1
         winner = net_of_white if white_won else 1 - net_of_white
-        return (1.0 if winner == 1 else 0.0), "checkmate"
-    return 0.5, ("draw" if fin.terminal == 2 else "move_limit")
+        how = "checkmate" if fin.terminal == 1 else "adjudication" if adjudicated else "resignation"
+        return (1.0 if winner == 1 else 0.0), how
+    return 0.5, ("adjudication" if adjudicated and fin.terminal == 2 else "draw" if fin.terminal == 2 else "move_limit")
 
 
 def play_match(ro, sched: MatchScheduler, step_of=None, seed_iteration: int = 0, log=None, finished: Optional[Dict] = None) -> Dict:
@@ -311,7 +317,8 @@ def write_match_pgn(fh, played: Dict, finished: Dict, a: str, b: str, device="cu
     games = played["games"]
     names = {"A": f"A ({a})", "B": f"B ({b})"}
     tags = [{"Event": "BetaOne match", "Date": date or pgn_write.today(), "Round": f"{g['opening'] + 1}.{g['game_id'] % 2 + 1}",
-             "White": names[g["white"]], "Black": names[g["black"]]} for g in games]
+             "White": names[g["white"]], "Black": names[g["black"]],
+             **({"Termination": "adjudication"} if g["termination"] == "adjudication" else {})} for g in games]
     fins = [finished[g["game_id"]] for g in games]
     return pgn_write.write_pgn(fh, fins, tags=tags, device=device, book_plies=[int(getattr(f, "first_ply", 0)) for f in fins])
 
@@ -361,7 +368,11 @@ def main(argv=None) -> int:
     ap.add_argument("--threshold", type=float, default=0.55)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--pgn", default=None, metavar="FILE", help="also write every game as PGN (SAN rendered on the GPU)")
+    from .selfplay_main import tb_arguments, tb_check_arguments, tb_rollout_kw
+
+    tb_arguments(ap)
     args = ap.parse_args(argv)
+    tb_check_arguments(ap, args)
 
     import torch
 
@@ -376,7 +387,7 @@ def main(argv=None) -> int:
     print(f"[match] A {net_shape(sd_a)} vs B {net_shape(sd_b)}: evaluate stage {pair.route}")
     ro = CohortRollout(pair, args.slots, cohorts=args.cohorts, num_simulations=args.sims, mcts_batch_size=args.mcts_batch,
                        dirichlet_alpha=0.0, temperature=(args.open_plies, 1.0, args.t_final), max_game_moves=args.max_game_moves,
-                       rng_mode="native", device=str(dev))
+                       rng_mode="native", device=str(dev), **tb_rollout_kw(args, str(dev)))
     sched = MatchScheduler(openings, args.games, args.slots, args.cohorts)
     finished: Optional[Dict] = {} if args.pgn else None
     try:
@@ -392,7 +403,7 @@ def main(argv=None) -> int:
     st["promoted"] = promote(sd_b, args.promote, st["score"], args.threshold) if args.promote else False
     out = {"a": args.a, "b": args.b, "settings": {k: getattr(args, k) for k in ("games", "slots", "cohorts", "sims", "mcts_batch", "openings",
                                                                              "open_plies", "t_final", "max_game_moves", "seed_iteration",
-                                                                             "threshold")},
+                                                                             "threshold", "tablebases", "tb_search", "tb_adjudicate")},
            "summary": st, "games": played["games"]}
     print(f"[match] B vs A: +{st['wins']} ={st['draws']} -{st['losses']}  score {st['score']:.3f}  Elo {st['elo']:+.1f} "
           f"[{st['elo_95'][0]:+.1f}, {st['elo_95'][1]:+.1f}] ({st['interval']})  LOS {st['los']:.3f}  "

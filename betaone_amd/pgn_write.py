@@ -268,7 +268,8 @@ def write_pgn(fh, games: Sequence, tags=None, device="cuda:0", lib=None, book_pl
                 com = ["book"] * min(book_plies[i], len(com)) + com[book_plies[i]:]
             fin = None
             if terminal == 3:
-                fin = ("White" if positions[len(moves)].turn == 1 else "Black") + " resigns"
+                # (a game the tablebases ended -- FinishedGame.adjudicated -- did not resign: the tables give its side to move as lost)
+                fin = ("White" if positions[len(moves)].turn == 1 else "Black") + (" is lost by the tablebases" if getattr(g, "adjudicated", False) else " resigns")
             text += movetext(r, root.turn, root.fullmove_number, result, 0, lib, comments=com, final_comment=fin) + "\n"
         else:
             text += movetext(r, root.turn, root.fullmove_number, result, book_plies[i] if book_plies else 0, lib) + "\n"

@@ -94,6 +94,7 @@ class FinishedGame:
     root_values: Optional[np.ndarray] = None  # float32 v_i per recorded ply (the root's q_value, side to move), when recorded
     resign_check: bool = False       # a check game: resignation was disabled for it (resign_check_game)
     resign: bool = False             # the run resigned games (resign_threshold was set)
+    adjudicated: bool = False        # ended by the tablebases at its last root (tb_adjudicate): terminal 2 a table draw, 3 the side to move is lost
 
     def z(self, i: int) -> float:    # self_play.py:202, for record i (ply first_ply + i)
         return self.outcome if self.positions[self.first_ply + i].turn == 1 else -self.outcome
@@ -143,7 +144,20 @@ class Rollout:
                  rng_mode: str = "python", policy_kind: str = "logits", fast: bool = False, leaves_per_step: int = 16,
                  fast_arena_granules: int = 0, stream: Optional["torch.cuda.Stream"] = None, time_tower: bool = False,
                  resign_threshold: Optional[float] = None, resign_plies: int = 1, resign_check_fraction: float = 0.1,
-                 record_values: bool = False):
+                 record_values: bool = False, tablebases=None, tb_search: bool = False, tb_adjudicate: bool = False):
+        # tablebases (a tablebase.TableSet on this device; DESIGN "Tablebases in the search"): tb_search -- the search probes covered leaves
+        # and scores them from the tables; tb_adjudicate -- a game ends at a root the tables give as drawn or as lost for the side to
+        # move (terminal 2 / 3, FinishedGame.adjudicated).  None: today's code path exactly, no call more.
+        if tablebases is None and (tb_search or tb_adjudicate):
+            raise ValueError("Rollout: tb_search / tb_adjudicate need tablebases (a tablebase.TableSet)")
+        if tablebases is not None:
+            if fast:
+                raise ValueError("Rollout: tablebases need the reference search semantics (fast=False)")
+            if tablebases.dev != E.runtime_device(device):
+                raise ValueError(f"Rollout: the tablebases live on {tablebases.dev}, the games on {E.runtime_device(device)}")
+        self.tb = tablebases
+        self.tb_flags = (E.Engine.TB_SEARCH if tb_search else 0) | (E.Engine.TB_ADJUDICATE if tb_adjudicate else 0)
+        self.tb_nodes = self.tb_sims = self.n_adjudicated = self.n_finished = 0  # over the finished games (tb_*: table leaves, their simulations)
         # resignation (DESIGN "Resignation"): a game resigns at ply i, before it plays, when v_i < resign_threshold at that ply and at its
         # side's previous resign_plies - 1 searches; check games (resign_check_game) never resign.  None: today's code path exactly.
         # record_values: keep v_i per ply (FinishedGame.root_values) with resignation off.
@@ -198,6 +212,8 @@ class Rollout:
         self.fast, self.L = bool(fast), self.eng.L
         if self.values:
             self.eng.root_values(True)  # (before any step is captured)
+        if self.tb is not None:
+            self.eng.tablebases(list(self.tb.tables.values()), self.tb_flags)  # (before any step is captured, too)
         self.nn_in = torch.zeros((self.G * self.L, E.INPUT_CHANNELS, 8, 8), dtype=torch.float32, device=self.device)
         # evaluations per search before the first poll: reference semantics = root + one per batch; fast mode = one per L
         # simulations (a root kept from the previous search needs no evaluation of its own; a fresh one costs one more round)
@@ -904,9 +920,17 @@ class Rollout:
         if self.values:
             t = max(0, len(moves) - gs.first_ply)
             rv = self._rv[g, :t].copy() if self.rng_mode == "native" else np.asarray(gs.root_values[:t], dtype=np.float32)
+        adjudicated = False
+        self.n_finished += 1
+        if self.tb is not None:  # (the slot still holds the game: its counters, and whether its last root was ended by the tables)
+            st = self.eng.tb_stats(self._stream())
+            adjudicated = bool(st["adjudicated"][g]) and terminal in (2, 3)
+            self.tb_nodes += int(st["tb_nodes"][g])
+            self.tb_sims += int(st["tb_sims"][g])
+            self.n_adjudicated += int(adjudicated)
         return FinishedGame(game_id=gs.game_id, slot=g, moves=moves, positions=positions, pis=pis, outcome=outcome,
                             terminal=terminal, first_ply=gs.first_ply, root_values=rv, resign_check=bool(self._rcheck[g]),
-                            resign=self.resign)
+                            resign=self.resign, adjudicated=adjudicated)
 
     # ---- training records ---------------------------------------------------------------------------------
     def encode_finished_in_slot(self, g: int, n_records: int, first_ply: int = 0) -> torch.Tensor:
@@ -1065,6 +1089,10 @@ class CohortRollout:
     n_plies = property(lambda self: sum(p.n_plies for p in self.parts))
     n_forward = property(lambda self: sum(p.n_forward for p in self.parts))
     host_seconds = property(lambda self: sum(p.host_seconds for p in self.parts))
+    tb_nodes = property(lambda self: sum(p.tb_nodes for p in self.parts))
+    tb_sims = property(lambda self: sum(p.tb_sims for p in self.parts))
+    n_adjudicated = property(lambda self: sum(p.n_adjudicated for p in self.parts))
+    n_finished = property(lambda self: sum(p.n_finished for p in self.parts))
     games = property(lambda self: [g for p in self.parts for g in p.games])
 
     @property

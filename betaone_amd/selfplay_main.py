@@ -96,7 +96,8 @@ def run_iteration(model, iteration: int, n_games: int, n_slots: int, rank: int =
     (self_play.py:220-231), "compact" = ~100 B/ply records appended to DATA_DIR/iter_{i}/games_rank{rank}.bog
     (betaone_amd.records, read back by records.CompactDataset with ChessDataset's item contract), "both".
     rollout_kw: resignation / root-value arguments of the Rollout (--resign-threshold, --resign-plies, --resign-check-fraction,
-    --record-values; compact records then are BOG2 with the per-ply root values).  Returns {game_id: plies}."""
+    --record-values; compact records then are BOG2 with the per-ply root values) and its tablebase arguments (--tablebases, --tb-search,
+    --tb-adjudicate; the summary line then counts table leaves, their simulations and the adjudicated games).  Returns {game_id: plies}."""
     from betaone_amd import dropin
 
     dropin.install()
@@ -111,6 +112,7 @@ def run_iteration(model, iteration: int, n_games: int, n_slots: int, rank: int =
         return {}
     t0 = time.time()
     done: Dict[int, int] = {}
+    stats: dict = {}
     path = R.compact_path(config.DATA_DIR, iteration, rank)
 
     have_compact = R.game_ids_on_disk(config.DATA_DIR, iteration) if records == "both" else set()
@@ -128,7 +130,7 @@ def run_iteration(model, iteration: int, n_games: int, n_slots: int, rank: int =
     results = self_play.run_self_play_games(model, todo, seeds=[game_seed(iteration, j) for j in todo],
                                             n_slots=min(n_slots, len(todo)), on_game=on_game, dense=records != "compact",
                                             reload_model=reload_model, on_records=on_records if records != "compact" else None,
-                                            rollout_kw=rollout_kw)
+                                            rollout_kw=rollout_kw, stats=stats)
     for j, data in results.items():
         if data is None:
             done.pop(j, None)  # aborted game (self_play.py:167): no record
@@ -136,8 +138,41 @@ def run_iteration(model, iteration: int, n_games: int, n_slots: int, rank: int =
     dt = time.time() - t0
     plies = sum(done.values())
     log(f"[rank {rank}] iteration {iteration}: {len(done)} games, {plies} plies in {dt:.1f} s "
-        f"({plies * config.NUM_SIMULATIONS / max(dt, 1e-9):.0f} nodes/s)")
+        f"({plies * config.NUM_SIMULATIONS / max(dt, 1e-9):.0f} nodes/s)" + tb_summary(rollout_kw, stats, len(done), plies))
     return done
+
+
+def tb_summary(rollout_kw: Optional[dict], stats: dict, games: int, plies: int) -> str:
+    """The tablebase part of a run's summary line ("" without --tablebases)."""
+    if not rollout_kw or rollout_kw.get("tablebases") is None:
+        return ""
+    return (f"; tablebases: {stats.get('tb_nodes', 0)} table leaves, {stats.get('tb_sims', 0)} table simulations, "
+            f"{stats.get('adjudicated', 0)} games adjudicated, {plies / max(1, games):.1f} plies per game")
+
+
+def tb_arguments(ap) -> None:
+    """--tablebases DIR [--tb-search] [--tb-adjudicate], shared by selfplay_main and match."""
+    ap.add_argument("--tablebases", default=None, metavar="DIR", help="endgame tablebases (*.botb of python -m betaone_amd.tablebase build), loaded once per rank")
+    ap.add_argument("--tb-search", action="store_true", help="score covered leaves of the search from the tables (needs --tablebases)")
+    ap.add_argument("--tb-adjudicate", action="store_true", help="end a game at a position the tables give as drawn or lost for the side to move (needs --tablebases)")
+
+
+def tb_check_arguments(ap, args) -> None:
+    if args.tablebases is None and (args.tb_search or args.tb_adjudicate):
+        ap.error("--tb-search / --tb-adjudicate need --tablebases DIR")
+    if args.tablebases is not None and not (args.tb_search or args.tb_adjudicate):
+        ap.error("--tablebases needs --tb-search, --tb-adjudicate or both")
+    if args.tablebases is not None and not os.path.isdir(args.tablebases):
+        ap.error(f"--tablebases: {args.tablebases} is not a directory")
+
+
+def tb_rollout_kw(args, device) -> dict:
+    """The Rollout arguments of --tablebases: the set is loaded here, once per process."""
+    if args.tablebases is None:
+        return {}
+    from betaone_amd import tablebase as TB
+
+    return dict(tablebases=TB.TableSet.load(args.tablebases, device), tb_search=args.tb_search, tb_adjudicate=args.tb_adjudicate)
 
 
 def launch_ranks(n: int, child_args: List[str], env: Optional[dict] = None) -> int:
@@ -173,7 +208,9 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--resign-check-fraction", type=float, default=0.1, metavar="F",
                     help="fraction of game ids that never resign, to calibrate T (python -m betaone_amd.resign; default 0.1)")
     ap.add_argument("--record-values", action="store_true", help="keep the per-ply root values in compact records with resignation off")
+    tb_arguments(ap)
     args = ap.parse_args(argv)
+    tb_check_arguments(ap, args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, ["-m", "betaone_amd.selfplay_main"] + list(sys.argv[1:] if argv is None else argv)))
     rollout_kw = {}
@@ -195,6 +232,7 @@ def main(argv: Optional[List[str]] = None):
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
         config.DEVICE = f"cuda:{local}"  # explicit: engine, NN rows and model of this rank on its own GPU
+    rollout_kw.update(tb_rollout_kw(args, config.DEVICE))
     model = network.PolicyValueNet().to(config.DEVICE)
     path = args.model or os.path.join(config.SAVE_DIR, "best_model.pth")
     if os.path.exists(path):

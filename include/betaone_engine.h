@@ -33,10 +33,12 @@ extern "C" {
  * bo_train_loss_backward_mix -- additions only; 10: perft on the device -- bo_perft, bo_perft_result -- additions only; 11: endgame
  * tablebases on the device -- bo_tb_create, bo_tb_build, bo_tb_verify, bo_tb_stats, bo_tb_download, bo_tb_upload, bo_tb_probe,
  * bo_tb_destroy -- additions only; 12: held-out validation metrics on the device -- bo_train_metrics and the BO_METRIC_* columns --
- * additions only; 13: a search that waits for its last leaf evaluation is finished without it -- bo_search_close -- addition only).
+ * additions only; 13: a search that waits for its last leaf evaluation is finished without it -- bo_search_close -- addition only;
+ * 14: endgame tablebases inside the search and at the root -- bo_engine_tablebases, bo_engine_tb_stats, bo_debug_tree's terminal codes
+ * 3 / 4 / 5, bo_root_info's terminal code 3 -- additions only).
  * A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 13
+#define BO_ABI_VERSION 14
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -117,7 +119,8 @@ int bo_games_reset_ex(bo_engine *e, int n, const int32_t *slots, const char *con
 
 /* Root facts the host needs before a search: number of legal moves (np.random.dirichlet needs it,
  * mcts.py:191-192) and is_game_over(claim_draw=True) of the current position (0 no, 1 side to move
- * is checkmated, 2 draw; self_play.py:101-102).  Synchronises.  Arrays are [G]. */
+ * is checkmated, 2 draw; self_play.py:101-102; with bo_engine_tablebases' adjudication also 3: the tables give the root as lost for
+ * the side to move -- the game ends as if that side had resigned -- and 2 for a root they give as drawn).  Synchronises.  Arrays are [G]. */
 int bo_root_info(bo_engine *e, int32_t *n_legal, int32_t *terminal, int32_t *ply, void *stream);
 
 /* ---- one search per game, all games in lock step ------------------------------------------------
@@ -814,6 +817,24 @@ int bo_tb_download(bo_tb *tb, uint16_t *codes, int64_t n_entries);
 int bo_tb_upload(bo_tb *tb, const uint16_t *codes, int64_t n_entries, int32_t passes);
 int bo_tb_probe(bo_tb *const *tbs, int32_t n_tb, const bo_position *positions, int32_t n, uint16_t *codes, int32_t *status, void *stream);
 void bo_tb_destroy(bo_tb *tb);
+
+/* ---- (ABI 14, additions) the tables inside the search and at the root: csrc/bo_tree.h, DESIGN "Tablebases in the search" -------------
+ * bo_engine_tablebases: the engine's searches read the set tbs [n_tb <= 64, complete tables on the engine's device] from now on.
+ *   flags bit 0: probe in the search -- a leaf the rules leave ongoing, with <= 4 men and no castling rights, that the set gives as a
+ *     draw or as a mate in k with halfmove clock + k <= 100 becomes a terminal leaf of value 0 / +-(1 - min(k, 512) / 1024) (the sign as
+ *     for the rule mate: seen by the side that just moved).  The root is never probed in the search.  bo_debug_tree reports such leaves
+ *     with terminal 3 (the side to move wins), 4 (it loses), 5 (draw).  The step then launches the kernel's probing instantiation.
+ *   flags bit 1: adjudicate -- every new root (bo_games_reset*, bo_play, the device turn) the rules leave ongoing and the set covers as
+ *     drawn gets terminal code 2, as lost for the side to move code 3; no search begins there.  No clock condition (tablebase.rescore's rule).
+ *   n_tb = 0 (or flags 0): off -- every path is bit for bit what it is without the call.
+ *   The descriptors are copied; the TABLES are not: they must outlive the engine's use of them (destroy the engine, or turn the set
+ *   off, before bo_tb_destroy).  Call it before a step or a turn is captured into a graph: the kernel arguments are baked into the
+ *   capture.  Synchronises the device's null stream.  BO_E_ARG: more than 64 tables, unknown flag bits, a table on another device;
+ *   BO_E_STATE: an incomplete table (its name in bo_last_error()); BO_E_CONFIG: a fast-mode engine.
+ * bo_engine_tb_stats: per game [G] (any may be NULL): table leaves created and simulations absorbed by table leaves since the game's
+ *   set-up, and 1 where the game's CURRENT root was adjudicated (terminal 2 or 3 from the tables, not from the rules).  Synchronises. */
+int bo_engine_tablebases(bo_engine *e, bo_tb *const *tbs, int32_t n_tb, int32_t flags);
+int bo_engine_tb_stats(bo_engine *e, int32_t *tb_nodes, int32_t *tb_sims, int32_t *adjudicated, void *stream);
 
 #ifdef __cplusplus
 }

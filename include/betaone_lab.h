@@ -23,7 +23,7 @@ typedef struct {
     int32_t parent, n_visits, first_child, n_children;
     float q_value, prior;
     int32_t move;      /* from|to<<6|promo<<12 */
-    int32_t terminal;  /* -1 never visited as leaf, 0 no, 1 mate, 2 draw */
+    int32_t terminal;  /* -1 never visited as leaf, 0 no, 1 mate, 2 draw; a table leaf (bo_engine_tablebases): 3 the side to move wins, 4 loses, 5 draw */
 } bo_node;
 int bo_debug_tree(bo_engine *e, int slot, bo_node *out, int32_t cap, int32_t *n_nodes, void *stream);
 /* The search state of every slot between two steps, out [5][G] int32: phase (0 idle, 1 running, 2 done), sims_done, pending rows, the
