@@ -172,7 +172,13 @@ class Ingested:
 
 
 class Analyser:
-    """The search side: a Rollout's engine and evaluate stage (noise off, root values on), driven batch by batch."""
+    """The search side: a Rollout's engine and evaluate stage (noise off, root values on), driven batch by batch.
+
+    What a batch's read-out is -- which result call fills which pinned buffers -- is three small methods (_make_buffers, _records,
+    _collect) and the hook _took; reanalyse.Reanalyser replaces them and keeps everything else."""
+
+    NAME = "analyse"
+    RECORD_DTYPE = E.ANALYSIS_DTYPE
 
     def __init__(self, model, slots: int, sims: int, max_plies: int, device, mcts_batch_size: Optional[int] = None, use_graph: bool = True,
                  iterations: Optional[int] = None, **search_cfg):
@@ -192,9 +198,8 @@ class Analyser:
         self.dev = self.ro.device
         self.eng = self.ro.eng
         self.slots_dev = torch.arange(self.G, dtype=torch.int32, device=self.dev)
-        self.out_dev = torch.zeros((self.G, 32), dtype=torch.int32, device=self.dev)
         cuda = self.dev.type == "cuda"
-        self.pinned = [torch.zeros((self.G, 32), dtype=torch.int32, pin_memory=cuda) for _ in range(2)]
+        self._make_buffers(cuda)
         self.events = [torch.cuda.Event() for _ in range(2)] if cuda else None
         # evaluate -> step iterations enqueued per batch: what a search is expected to need (Rollout: 1 + ceil(S / MCTS_BATCH_SIZE))
         self.iterations = int(iterations) if iterations else self.ro.expected_evals
@@ -203,27 +208,44 @@ class Analyser:
     def close(self):
         self.ro.close()
 
+    def _make_buffers(self, cuda: bool):
+        self.out_dev = torch.zeros((self.G, 32), dtype=torch.int32, device=self.dev)
+        self.pinned = [torch.zeros((self.G, 32), dtype=torch.int32, pin_memory=cuda) for _ in range(2)]
+
+    def _soft_bits(self) -> int:
+        return self.eng.soft_status_bits()
+
+    def _took(self, ids: np.ndarray, rows: np.ndarray):
+        """Roots `ids` got their records from rows `rows` of the batch _collect returned last."""
+
     def _enqueue(self, ing: Ingested, arrays, b: int, extra: int, buf: int):
         """Batch b of `arrays`: set-up -> begin -> the search's iterations -> result + records -> copy to pinned[buf].  No host wait."""
-        first, ply, played, want, _ = arrays
+        first, ply, want = arrays[0], arrays[1], arrays[3]
         ro, eng, G, s = self.ro, self.eng, self.G, _stream(self.dev)
         eng.reset_dev(G, self.slots_dev.data_ptr(), ing.pos.data_ptr(), ing.T, first.data_ptr() + 8 * b * G, ply.data_ptr() + 4 * b * G, s)
         eng.search_begin_dev(want.data_ptr() + 4 * b * G, ro.nn_in.data_ptr(), s)
         eng.step(0, 0, E.POLICY_NONE, ro.nn_in.data_ptr(), s)
         ro._eval_and_step_n(self.iterations + extra)
-        self._records(played, b, buf)
+        self._records(arrays, b, buf)
         self.n_batches += 1
 
-    def _records(self, played, b: int, buf: int):
-        self.eng.analysis_result(played.data_ptr() + 4 * b * self.G, self.out_dev.data_ptr(), _stream(self.dev))
+    def _records(self, arrays, b: int, buf: int):
+        """Batch b's result call and its copy to pinned[buf], enqueued."""
+        self.eng.analysis_result(arrays[2].data_ptr() + 4 * b * self.G, self.out_dev.data_ptr(), _stream(self.dev))
         self.pinned[buf].copy_(self.out_dev, non_blocking=True)
+        self._recorded(buf)
+
+    def _recorded(self, buf: int):
         if self.events is not None:
             self.events[buf].record(torch.cuda.current_stream(self.dev))
+
+    def _read(self, buf: int) -> np.ndarray:
+        return self.pinned[buf].numpy().copy().view(self.RECORD_DTYPE).reshape(self.G)
 
     def _collect(self, buf: int) -> np.ndarray:
         if self.events is not None:
             self.events[buf].synchronize()
-        rec = self.pinned[buf].numpy().copy().view(E.ANALYSIS_DTYPE).reshape(self.G)
+        rec = self._read(buf)
         if (rec["watch"] != 0).any():  # the evaluate stage's fault word, as Rollout checks it once per ply
             chk = getattr(getattr(self.ro.model, "net", self.ro.model), "check_overflow", None)
             if chk is not None and self.dev.type == "cuda":
@@ -233,9 +255,9 @@ class Analyser:
         return rec
 
     def run(self, ing: Ingested) -> np.ndarray:
-        """One bo_analysis record per root of `ing`, in work-list order."""
+        """One record (RECORD_DTYPE: bo_analysis) per root of `ing`, in work-list order."""
         N, G = ing.n_roots, self.G
-        out = np.zeros(N, E.ANALYSIS_DTYPE)
+        out = np.zeros(N, self.RECORD_DTYPE)
         if N == 0:
             return out
         arrays = ing.work_arrays(self.dev, G)
@@ -246,13 +268,14 @@ class Analyser:
             n = min(G, N - b * G) if order is None else min(G, len(order) - b * G)
             ids = np.arange(b * G, b * G + n) if order is None else order[b * G:b * G + n]
             r = rec[:n]
-            bad = r["status"] & ~self.eng.soft_status_bits()
+            bad = r["status"] & ~self._soft_bits()
             if bad.any():
                 k = int(np.nonzero(bad)[0][0])
-                raise E.EngineError(f"analyse: {ing.name} game {int(ing.w_game[ids[k]])} ply {int(ing.w_ply[ids[k]])}: "
+                raise E.EngineError(f"{self.NAME}: {ing.name} game {int(ing.w_game[ids[k]])} ply {int(ing.w_ply[ids[k]])}: "
                                     f"{self.eng.describe_status(int(bad[k]))}")
             running = r["phase"] == E.PH_RUN
             out[ids[~running]] = r[~running]
+            self._took(ids[~running], np.nonzero(~running)[0])
             return [int(i) for i in ids[running]]
 
         for b in range(nb):  # batch b + 1 is enqueued before batch b's records are read
@@ -274,10 +297,10 @@ class Analyser:
                     if not (rec["phase"] == E.PH_RUN).any():
                         break
                     self.ro._eval_and_step_n(1)
-                    self._records(arr2[2], b, 0)
+                    self._records(arr2, b, 0)
                     rec = self._collect(0)
                 if take(b, rec, order):
-                    raise E.EngineError("analyse: a search did not finish")
+                    raise E.EngineError(f"{self.NAME}: a search did not finish")
         return out
 
 

@@ -14,6 +14,7 @@
 #include "bo_pgn.h"
 #include "bo_san.h"
 #include "bo_analyse.h"
+#include "bo_reanalyse.h"
 #include "bo_perft.h"
 #include "bo_tb.h"
 #include "bo_nn_fused.h"
@@ -204,19 +205,7 @@ static bool parse_uci_moves(const char *s, std::vector<bo_mv> *out) {
     return true;
 }
 
-static DPos from_abi(const bo_position &p) {
-    DPos d;
-    memset(&d, 0, sizeof(d));
-    for (int i = 0; i < 8; i++) d.bb[i] = p.bb[i];
-    d.flags = (p.turn ? F_TURN : 0u) | ((p.castling & 0xFu) << F_CASTLE_SHIFT) | ((uint32_t)(p.ep_square + 1) << F_EP_SHIFT);
-    if (p.ep_key >= 0) d.flags |= (uint32_t)(p.ep_key + 1) << F_EPKEY_SHIFT;
-    // ep_key == -1 ("no ep component in the key") with a raw ep square present is re-derived on the device by
-    // finish_key(); that is deterministic and gives -1 again.  Tracker keys taken from python-chess key tuples
-    // carry ep_square == ep_key.
-    d.halfmove = p.halfmove_clock;
-    d.fullmove = p.fullmove_number;
-    return d;
-}
+static DPos from_abi(const bo_position &p) { return dpos_from_abi(p); }  // (bo_reanalyse.h: shared with bo_k_records_ring)
 static void to_abi(const DPos &d, bo_position *p) {
     for (int i = 0; i < 8; i++) p->bb[i] = d.bb[i];
     p->turn = (int)(d.flags & F_TURN);
@@ -1569,6 +1558,38 @@ extern "C" int bo_analysis_result(bo_engine *e, const int32_t *played_dev, bo_an
     if (!e->d.c.root_q) return fail(BO_E_STATE, "bo_analysis_result: call bo_engine_root_values(e, 1) first");
     RT(RT_LAUNCH(bo_k_result, e->d.c.G, stream, e->d));
     RT(RT_LAUNCH(bo_k_analysis, e->d.c.G, stream, e->d, (const int *)played_dev, (int *)out));
+    return BO_OK;
+}
+
+// ---- reanalysis of self-play records (bo_reanalyse.h; ABI 15) ----------------------------------------------------------------------
+static_assert(sizeof(bo_reanalysis) == BO_REANALYSIS_WORDS * 4, "bo_reanalysis is BO_REANALYSIS_WORDS words");
+static_assert(BO_ST_PI_OVERFLOW == ST_PI_OVERFLOW, "status bits");
+static_assert(sizeof(DPos) == BO_PGN_POSITION_BYTES, "a ring entry");
+
+// n bo_position -> n ring entries, one lane each.  Asynchronous; both arrays are device memory.
+extern "C" int bo_records_ring(const bo_position *pos_dev, int64_t n, void *ring_out_dev, void *stream) {
+    if (n < 0 || n > ((int64_t)1 << 36)) return fail(BO_E_ARG, "bo_records_ring: n out of range");
+    if (n == 0) return BO_OK;
+    if (!pos_dev || !ring_out_dev) return fail(BO_E_ARG, "bo_records_ring: null argument");
+    RT(RT_LAUNCH(bo_k_records_ring, (int)((n + 63) / 64), stream, pos_dev, (long long)n, (DPos *)ring_out_dev));
+    return BO_OK;
+}
+
+// bo_k_result + bo_k_reanalysis: one bo_reanalysis record and one pi row of W entries per slot.  Asynchronous.
+extern "C" int bo_reanalysis_result(bo_engine *e, const int32_t *played_action_dev, const int64_t *root_dev, const int32_t *old_ptr_dev,
+                                    const int32_t *old_idx_dev, const float *old_val_dev, int32_t W, bo_reanalysis *out, int32_t *pi_idx_out,
+                                    float *pi_val_out, void *stream) {
+    if (!e || !out || !pi_idx_out || !pi_val_out) return fail(BO_E_ARG, "bo_reanalysis_result: null argument");
+    if (W < 1 || W > BO_RES_CAP) return fail(BO_E_ARG, "bo_reanalysis_result: W must be 1 .. BO_RES_CAP");
+    const int n_old = (root_dev ? 1 : 0) + (old_ptr_dev ? 1 : 0) + (old_idx_dev ? 1 : 0) + (old_val_dev ? 1 : 0);
+    if (n_old != 0 && n_old != 4) return fail(BO_E_ARG, "bo_reanalysis_result: root_dev, old_ptr_dev, old_idx_dev and old_val_dev are given together or not at all");
+    if (e->fast) return fail(BO_E_CONFIG, "bo_reanalysis_result: reference-semantics engines only");
+    if (!e->d.c.root_q) return fail(BO_E_STATE, "bo_reanalysis_result: call bo_engine_root_values(e, 1) first");
+    ReanalysisArgs a;
+    a.played = played_action_dev; a.root = (const long long *)root_dev; a.old_ptr = old_ptr_dev; a.old_idx = old_idx_dev; a.old_val = old_val_dev;
+    a.W = W; a.out = (int *)out; a.pi_idx = pi_idx_out; a.pi_val = pi_val_out;
+    RT(RT_LAUNCH(bo_k_result, e->d.c.G, stream, e->d));
+    RT(RT_LAUNCH(bo_k_reanalysis, e->d.c.G, stream, e->d, a));
     return BO_OK;
 }
 

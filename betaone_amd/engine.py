@@ -25,8 +25,10 @@ RES_CAP = 256
 POLICY_NONE, POLICY_LOGITS, POLICY_PROBS = 0, 1, 2
 
 STATUS_BITS = {1: "node overflow", 2: "depth overflow", 4: "NaN PUCT score", 8: "ply overflow",
-               16: "illegal action", 32: "leaf cache overflow", 64: "tracker overflow", 128: "position range outside the array"}
+               16: "illegal action", 32: "leaf cache overflow", 64: "tracker overflow", 128: "position range outside the array",
+               256: "pi wider than the record's rows"}
 ST_PLY_OVERFLOW, ST_ILLEGAL_ACTION = 8, 16   # per-GAME conditions (the reference aborts that game only); the rest are engine faults
+ST_PI_OVERFLOW = 256  # bo_reanalysis_result: a condition of one record (its status word only), never a slot's own status
 ST_NODE_OVERFLOW = 1  # reference mode: a fault (the node arrays are sized for the search).  Fast mode: the game's arena was full at an
 #                       expansion or a re-root -- the leaf stayed unexpanded (its value was still backed up) / the subtree that did not
 #                       fit was dropped; the search is valid, only narrower.  Sticky per slot until the slot is reset.
@@ -76,6 +78,9 @@ ANALYSIS_DTYPE = np.dtype([("terminal", "<i4"), ("n_legal", "<i4"), ("total_visi
                            ("played_is_child", "<i4"), ("played_visits", "<i4"), ("played_q", "<f4"), ("pv_len", "<i4"),
                            ("pv", "<i4", (PV_CAP,)), ("phase", "<i4"), ("status", "<i4"), ("ply", "<i4"), ("sims_done", "<i4"),
                            ("watch", "<i4"), ("reserved", "<i4", (2,))])  # the same record as a NumPy dtype (a [G, 32] int32 buffer .view()ed)
+REANALYSIS_DTYPE = np.dtype([("terminal", "<i4"), ("n_legal", "<i4"), ("total_visits", "<i4"), ("best_idx", "<i4"), ("root_value", "<f4"),
+                             ("pi_n", "<i4"), ("played_prob", "<f4"), ("has_old", "<i4"), ("agree", "<i4"), ("tv", "<f4"), ("phase", "<i4"),
+                             ("status", "<i4"), ("ply", "<i4"), ("sims_done", "<i4"), ("watch", "<i4"), ("reserved", "<i4")])  # bo_reanalysis
 PH_IDLE, PH_RUN, PH_DONE = 0, 1, 2
 
 
@@ -191,6 +196,8 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_games_reset_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bo_search_begin_dev": (C.c_int, [C.c_void_p] * 4),
     "bo_analysis_result": (C.c_int, [C.c_void_p] * 4),
+    "bo_records_ring": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bo_reanalysis_result": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 4),
     "bo_pgn_after": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 4),
     "bo_pgn_spans": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "bo_pgn_movetext": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int64,
@@ -237,7 +244,7 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 14  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 15  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
 # BO_METRIC_ROW_* / BO_METRIC_* of include/betaone_engine.h by name (bo_train_metrics; tests/test_validate_emu.py compares with the header)
 METRIC_ROW = {name: k for k, name in enumerate((
@@ -428,6 +435,13 @@ class Engine:
     def analysis_result(self, played_ptr: int, out_ptr: int, stream: int = 0):
         """bo_analysis_result: G records of ANALYSIS_DTYPE into out (device or pinned memory); played: device int32 [G] or 0."""
         self._check(self.lib.bo_analysis_result(self.h, played_ptr or None, out_ptr, stream))
+
+    def reanalysis_result(self, played_action_ptr: int, root_ptr: int, old_ptr_ptr: int, old_idx_ptr: int, old_val_ptr: int, W: int,
+                          out_ptr: int, pi_idx_ptr: int, pi_val_ptr: int, stream: int = 0):
+        """bo_reanalysis_result: G records of REANALYSIS_DTYPE into out and G pi rows of W entries (device or pinned memory).  played_action:
+        device int32 [G] or 0; root (int64 [G]) / old_ptr / old_idx / old_val: the old pi on the device, together or all 0."""
+        self._check(self.lib.bo_reanalysis_result(self.h, played_action_ptr or None, root_ptr or None, old_ptr_ptr or None, old_idx_ptr or None,
+                                                  old_val_ptr or None, int(W), out_ptr, pi_idx_ptr, pi_val_ptr, stream))
 
     def root_info(self, stream: int = 0):
         nl, tm, ply = (np.zeros(self.G, dtype=np.int32) for _ in range(3))

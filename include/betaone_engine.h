@@ -35,10 +35,11 @@ extern "C" {
  * bo_tb_destroy -- additions only; 12: held-out validation metrics on the device -- bo_train_metrics and the BO_METRIC_* columns --
  * additions only; 13: a search that waits for its last leaf evaluation is finished without it -- bo_search_close -- addition only;
  * 14: endgame tablebases inside the search and at the root -- bo_engine_tablebases, bo_engine_tb_stats, bo_debug_tree's terminal codes
- * 3 / 4 / 5, bo_root_info's terminal code 3 -- additions only).
+ * 3 / 4 / 5, bo_root_info's terminal code 3 -- additions only; 15: reanalysis of self-play records -- bo_records_ring,
+ * bo_reanalysis_result, status bit BO_ST_PI_OVERFLOW -- additions only).
  * A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 14
+#define BO_ABI_VERSION 15
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -58,7 +59,9 @@ enum {
 enum {
     BO_ST_NODE_OVERFLOW = 1, BO_ST_DEPTH_OVERFLOW = 2, BO_ST_NAN_SCORE = 4, BO_ST_PLY_OVERFLOW = 8,
     BO_ST_ILLEGAL_ACTION = 16, BO_ST_UL_OVERFLOW = 32, BO_ST_TRK_OVERFLOW = 64,
-    BO_ST_BAD_RANGE = 128   /* (ABI 8) bo_games_reset_dev: the slot's positions are not inside the array */
+    BO_ST_BAD_RANGE = 128,  /* (ABI 8) bo_games_reset_dev: the slot's positions are not inside the array */
+    BO_ST_PI_OVERFLOW = 256 /* (ABI 15) bo_reanalysis_result: the search's pi has more entries than the rows hold.  A condition of one
+                             * record: set in bo_reanalysis.status only, never in the slot's own status word */
 };
 
 enum { BO_POLICY_NONE = 0, BO_POLICY_LOGITS = 1, BO_POLICY_PROBS = 2 };
@@ -729,6 +732,46 @@ int bo_analysis_result(bo_engine *e, const int32_t *played_dev, bo_analysis *out
 int bo_pgn_after(const void *pos_dev, const int32_t *act_dev, int64_t capacity, int32_t n, const int64_t *idx_dev, void *pos_out_dev,
                  int32_t *move_out_dev, void *stream);
 int bo_pgn_spans(const bo_pgn *p, int64_t *begin, int64_t *end);
+
+/* ---- (ABI 15, additions) reanalysis of self-play records: csrc/bo_reanalyse.h, betaone_amd/reanalyse.py ---------------------------
+ * The positions a .bog record stores are searched again with a newer net; the record gets that search's pi and root value.  The search
+ * is the analysis path above (bo_games_reset_dev, bo_search_begin_dev, bo_step); these two calls are its ends.
+ *
+ * bo_records_ring: n bo_position in DEVICE memory -- the concatenated positions of a file's games, n_plies + 1 per game, as they sit in
+ * the record bodies -- become n ring entries (BO_PGN_POSITION_BYTES each) in ring_out_dev: what bo_pgn_replay writes for the same
+ * positions, byte for byte (flag word, resolved e.p. key, key hash, and the "reached by an irreversible move" bit, which entry i takes
+ * from entry i - 1 when it is that position's child).  One lane per position.  n == 0 does nothing.  Asynchronous.
+ * bo_reanalysis_result: the result kernel of bo_search_result, then per slot one bo_reanalysis record into out[G] and one pi row into
+ * pi_idx_out / pi_val_out [G][W] (device memory, or pinned device-mapped host memory; each word is stored once).  1 <= W <= BO_RES_CAP
+ * (BO_E_ARG).  Needs bo_engine_root_values(e, 1) (BO_E_STATE) and a reference-semantics engine (BO_E_CONFIG).  Asynchronous.
+ *   played_action_dev [G] (may be NULL): the ACTION INDEX the game played from the slot's root (-1 none).
+ *   root_dev [G] int64: the root's index r into old_ptr_dev (-1: the root has no old pi); its old entries are old_idx_dev / old_val_dev
+ *     [old_ptr_dev[r] .. old_ptr_dev[r + 1]).  The four old-pi pointers are given together or are all NULL (no root has an old pi).
+ *   terminal, n_legal, phase, status, ply, sims_done, watch: as in bo_analysis; the fields below and the rows are written only for
+ *     phase 2 with terminal 0 -- the rows of every other slot are not touched.
+ *   The rows: the first min(pi_n, W) entries of bo_search_result's row, in its order and with its bits, then (-1, 0).  pi_n: the
+ *     entries the search produced; pi_n > W sets BO_ST_PI_OVERFLOW in the record's status.
+ *   total_visits, best_idx: bo_search_result's.  root_value: the root's q_value (side to move).  played_prob: the row's value at
+ *     played_action_dev[g] (the whole row, not only its first W entries), 0 when it is absent.
+ *   has_old: root_dev[g] >= 0.  tv: 0.5 * (sum over the new entries in row order of |new - old(a)| + sum over the old entries whose
+ *     action the new row does not have, in stored order, of old), old(a) the first old entry with action a or 0; accumulated in float64
+ *     in exactly that order, rounded once to float32.  agree: the old pi's first maximum in stored order names the same action as the
+ *     new row's first maximum in row order (0 for an empty old pi).  The new row's first maximum is best_idx unless visit counts tie:
+ *     best_idx breaks ties in legal-move order, the row is in child order.  has_old 0 gives tv 0 and agree 0. */
+#define BO_REANALYSIS_WORDS 16
+typedef struct bo_reanalysis {
+    int32_t terminal, n_legal, total_visits, best_idx;
+    float root_value;
+    int32_t pi_n;
+    float played_prob;
+    int32_t has_old, agree;
+    float tv;
+    int32_t phase, status, ply, sims_done, watch, reserved;
+} bo_reanalysis;
+int bo_records_ring(const bo_position *pos_dev, int64_t n, void *ring_out_dev, void *stream);
+int bo_reanalysis_result(bo_engine *e, const int32_t *played_action_dev, const int64_t *root_dev, const int32_t *old_ptr_dev,
+                         const int32_t *old_idx_dev, const float *old_val_dev, int32_t W, bo_reanalysis *out, int32_t *pi_idx_out,
+                         float *pi_val_out, void *stream);
 
 /* ---- (ABI 10, additions) perft on the device: csrc/bo_perft.h, betaone_amd/perft.py ------------------------------------------------
  * perft(depth) = the number of move sequences of length `depth` from a root, as python-chess's Board perft counts them: draw rules are
