@@ -16,6 +16,7 @@
 #include "bo_analyse.h"
 #include "bo_reanalyse.h"
 #include "bo_perft.h"
+#include "bo_book.h"
 #include "bo_tb.h"
 #include "bo_nn_fused.h"
 #include "bo_conv.h"
@@ -1590,6 +1591,32 @@ extern "C" int bo_reanalysis_result(bo_engine *e, const int32_t *played_action_d
     a.W = W; a.out = (int *)out; a.pi_idx = pi_idx_out; a.pi_val = pi_val_out;
     RT(RT_LAUNCH(bo_k_result, e->d.c.G, stream, e->d));
     RT(RT_LAUNCH(bo_k_reanalysis, e->d.c.G, stream, e->d, a));
+    return BO_OK;
+}
+
+// ---- opening books (bo_book.h; ABI 16) ---------------------------------------------------------------------------------------------
+static_assert(BO_BOOK_NO_COMBINE == BOOK_NO_COMBINE && BO_BOOK_EVAL_ONE == BOOK_EVAL_ONE, "book constants");
+
+// n work items into a table of T slots, one lane per item.  Asynchronous; every pointer is device memory.
+extern "C" int bo_book_insert(const void *pos_dev, int64_t capacity, int64_t n, const int64_t *entry_dev, const int32_t *ply_dev,
+                              const int32_t *result_dev, const float *eval_dev, const int32_t *back_dev, int64_t T, int32_t *owner_dev,
+                              int64_t *first_dev, int32_t *n_dev, int32_t *w_dev, int32_t *d_dev, int32_t *l_dev, int32_t *n_eval_dev,
+                              int32_t *min_ply_dev, int64_t *sum_eval_dev, int32_t *gid_out_dev, int32_t *status_dev, uint32_t flags,
+                              void *stream) {
+    if (n < 0 || n > (int64_t)0x7fffffff) return fail(BO_E_ARG, "bo_book_insert: n out of range (0 .. 2^31 - 1)");
+    if (capacity < 0) return fail(BO_E_ARG, "bo_book_insert: negative capacity");
+    if (T < 1 || T > ((int64_t)1 << 30) || (T & (T - 1)) != 0) return fail(BO_E_ARG, "bo_book_insert: T must be a power of two, 1 .. 2^30");
+    if (flags & ~(uint32_t)BO_BOOK_NO_COMBINE) return fail(BO_E_ARG, "bo_book_insert: unknown flag bits");
+    if (!owner_dev || !first_dev || !n_dev || !w_dev || !d_dev || !l_dev || !n_eval_dev || !min_ply_dev || !sum_eval_dev || !status_dev)
+        return fail(BO_E_ARG, "bo_book_insert: null table column or status");
+    if (n == 0) return BO_OK;
+    if ((capacity > 0 && !pos_dev) || !entry_dev || !ply_dev || !result_dev || !back_dev || !gid_out_dev)
+        return fail(BO_E_ARG, "bo_book_insert: null argument");
+    BookArgs a;
+    a.pos = (const DPos *)pos_dev; a.capacity = capacity; a.n = n; a.T = T; a.entry = entry_dev; a.ply = ply_dev; a.result = result_dev;
+    a.back = back_dev; a.eval = eval_dev; a.owner = owner_dev; a.first = first_dev; a.cnt = n_dev; a.w = w_dev; a.d = d_dev; a.l = l_dev;
+    a.n_eval = n_eval_dev; a.min_ply = min_ply_dev; a.sum_eval = sum_eval_dev; a.gid = gid_out_dev; a.status = status_dev; a.flags = flags;
+    RT(RT_LAUNCH(bo_k_book_insert, (int)((n + 63) / 64), stream, a));
     return BO_OK;
 }
 

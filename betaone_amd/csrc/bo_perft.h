@@ -30,9 +30,25 @@ enum { PF_CAPTURES = 0, PF_EP = 1, PF_CASTLES = 2, PF_PROMOTIONS = 3, PF_CHECKS 
 
 #if defined(BO_WAVE_EMU)
 BO_DEV void bo_atomic_add_u64(uint64_t *p, uint64_t v) { *p += v; }
+// (bo_book.h) the emulator runs one lane at a time and one workgroup after another: plain operations
+BO_DEV int32_t bo_atomic_cas_i32(int32_t *p, int32_t expect, int32_t v) { const int32_t o = *p; if (o == expect) *p = v; return o; }
+BO_DEV void bo_atomic_add_i32(int32_t *p, int32_t v) { *p += v; }
+BO_DEV void bo_atomic_min_i32(int32_t *p, int32_t v) { if (v < *p) *p = v; }
+BO_DEV void bo_atomic_add_i64(int64_t *p, int64_t v) { *p += v; }
+BO_DEV void bo_atomic_min_i64(int64_t *p, int64_t v) { if (v < *p) *p = v; }
 #else
 // global_atomic_add_x2 without a return value
 BO_DEV void bo_atomic_add_u64(uint64_t *p, uint64_t v) { (void)atomicAdd((unsigned long long *)p, (unsigned long long)v); }
+// (bo_book.h) relaxed, agent scope: read-modify-writes that every XCD sees at the same place; on an LDS address they become ds_* operations.
+// The compare-and-swap returns the word it found (== expect: the swap happened).
+BO_DEV int32_t bo_atomic_cas_i32(int32_t *p, int32_t expect, int32_t v) {
+    (void)__hip_atomic_compare_exchange_strong(p, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return expect;
+}
+BO_DEV void bo_atomic_add_i32(int32_t *p, int32_t v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+BO_DEV void bo_atomic_min_i32(int32_t *p, int32_t v) { (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+BO_DEV void bo_atomic_add_i64(int64_t *p, int64_t v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+BO_DEV void bo_atomic_min_i64(int64_t *p, int64_t v) { (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #endif
 
 // inclusive prefix sum over lanes in ASCENDING lane order

@@ -36,10 +36,10 @@ extern "C" {
  * additions only; 13: a search that waits for its last leaf evaluation is finished without it -- bo_search_close -- addition only;
  * 14: endgame tablebases inside the search and at the root -- bo_engine_tablebases, bo_engine_tb_stats, bo_debug_tree's terminal codes
  * 3 / 4 / 5, bo_root_info's terminal code 3 -- additions only; 15: reanalysis of self-play records -- bo_records_ring,
- * bo_reanalysis_result, status bit BO_ST_PI_OVERFLOW -- additions only).
+ * bo_reanalysis_result, status bit BO_ST_PI_OVERFLOW -- additions only; 16: opening books -- bo_book_insert -- addition only).
  * A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 15
+#define BO_ABI_VERSION 16
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -772,6 +772,41 @@ int bo_records_ring(const bo_position *pos_dev, int64_t n, void *ring_out_dev, v
 int bo_reanalysis_result(bo_engine *e, const int32_t *played_action_dev, const int64_t *root_dev, const int32_t *old_ptr_dev,
                          const int32_t *old_idx_dev, const float *old_val_dev, int32_t W, bo_reanalysis *out, int32_t *pi_idx_out,
                          float *pi_val_out, void *stream);
+
+/* ---- (ABI 16, addition) opening books from games: csrc/bo_book.h, betaone_amd/book.py -----------------------------------------------
+ * Every position of every game inside a ply window, grouped by its exact transposition key, with integer aggregates per group.  The
+ * positions are ring entries (BO_PGN_POSITION_BYTES each) that bo_pgn_replay / bo_records_ring left in pos_dev[capacity]; the entry's own
+ * khash word is the probe start and a filter (read, never recomputed), equality is the exact key: the eight bitboards, the side to
+ * move, the castling rights and the en-passant square where a capture is legal.  Entries with an equal key and different khash words
+ * (a caller's error) are never merged.  Engine-less; one lane per item; asynchronous on `stream`; every pointer is device memory the
+ * caller owns.
+ *   Work item i (n items, 0 <= n < 2^31): entry_dev[i] (int64 index into the ring), ply_dev[i], result_dev[i] (0 unknown, 1 white won,
+ *     2 draw, 3 black won), eval_dev[i] (float32 seen by the side to move at the entry; NaN: none; eval_dev may be NULL: no item has
+ *     one), back_dev[i]: how many entries directly in front of entry_dev[i] belong to the same game and the window.  An item with an
+ *     equal key among those entries is SKIPPED: a game counts once per position, at the lowest ply it reaches it.
+ *   The table: T slots, T a power of two <= 2^30, as columns the caller prepares: owner int32 [T] = -1, first int64 [T] = INT64_MAX,
+ *     min_ply int32 [T] = INT32_MAX, and n, w, d, l, n_eval int32 [T] = 0, sum_eval int64 [T] = 0.  After the call a slot with
+ *     owner >= 0 is one group: owner = the index of the item that claimed the slot, first = the smallest entry index in the group,
+ *     n = items (games) counted, w / d / l = those with result 1 / 2 / 3, n_eval = those with an eval, sum_eval = the sum of
+ *     lrintf(clamp(eval, -1, 1) * BO_BOOK_EVAL_ONE) in WHITE's view (negated where black is to move), min_ply = the lowest ply.
+ *     Integers only: the columns of a group do not depend on the order of the items (its slot and its owner can; compare by first).
+ *     One call fills one table: owner holds indices into THIS call's item arrays.
+ *   gid_out_dev [n] int32: the item's slot; -1 skipped (counted already, or a bad entry); -2 overflow: T probes found neither an empty
+ *     slot nor the item's group -- nothing of it is counted; run again with a larger T.
+ *   status_dev int32 [2], ADDED TO: [0] overflow items, [1] bad entries -- an entry outside [0, capacity) contributes nothing, and
+ *     nothing outside the ring is ever read (back_dev is cut at entry 0).
+ *   flags: BO_BOOK_NO_COMBINE -- every lane issues its own atomics; without it the lanes of a wave that found the same slot combine
+ *     first (same columns either way).
+ * BO_E_ARG: n or capacity negative, T no power of two or out of range, unknown flag bits, a NULL column or status, and with n > 0 any
+ * other NULL pointer but eval_dev.  n == 0 does nothing.  Probing is linear, one relaxed agent-scope compare-and-swap on owner per
+ * probed slot; no workgroup waits for another. */
+#define BO_BOOK_NO_COMBINE 1u
+#define BO_BOOK_EVAL_ONE (1 << 20)
+int bo_book_insert(const void *pos_dev, int64_t capacity, int64_t n, const int64_t *entry_dev, const int32_t *ply_dev,
+                   const int32_t *result_dev, const float *eval_dev /* may be NULL */, const int32_t *back_dev, int64_t T,
+                   int32_t *owner_dev, int64_t *first_dev, int32_t *n_dev, int32_t *w_dev, int32_t *d_dev, int32_t *l_dev,
+                   int32_t *n_eval_dev, int32_t *min_ply_dev, int64_t *sum_eval_dev, int32_t *gid_out_dev, int32_t *status_dev,
+                   uint32_t flags, void *stream);
 
 /* ---- (ABI 10, additions) perft on the device: csrc/bo_perft.h, betaone_amd/perft.py ------------------------------------------------
  * perft(depth) = the number of move sequences of length `depth` from a root, as python-chess's Board perft counts them: draw rules are
