@@ -17,6 +17,7 @@
 #include "bo_reanalyse.h"
 #include "bo_perft.h"
 #include "bo_book.h"
+#include "bo_merge.h"
 #include "bo_tb.h"
 #include "bo_nn_fused.h"
 #include "bo_conv.h"
@@ -38,6 +39,7 @@
 #include <vector>
 #include <algorithm>
 #include <deque>
+#include <memory>
 #include <type_traits>
 
 static thread_local std::string g_err;
@@ -1229,6 +1231,7 @@ struct bo_replay_s {
     int *rep = nullptr, *pi_n = nullptr, *pi_idx = nullptr, *s_slot = nullptr, *s_k = nullptr;
     float *pi_val = nullptr, *z = nullptr, *q = nullptr;   // q: the root value beside z (z itself for a record without one)
     int64_t n_valued = 0;                                 // resident records that carry a root value
+    uint64_t epoch = 0;                                   // counts the games added: a bo_replay_merge is good for the epoch it was made in
     int s_cap = 0;
     struct Game { int64_t start; int32_t n_rec; int32_t game_id; bool valued; };
     std::deque<Game> games;
@@ -1280,6 +1283,7 @@ static int replay_add_game(const char *who, bo_replay *r, int32_t game_id, const
     if (need > r->cap) return fail(BO_E_ARG, std::string(who) + ": the game is longer than the buffer");
     for (int i = 0; i < n_records; i++)
         if (pi_ptr[i + 1] - pi_ptr[i] > r->W || pi_ptr[i + 1] < pi_ptr[i]) return fail(BO_E_ARG, std::string(who) + ": a pi has more entries than the buffer's pi_width");
+    r->epoch++;  // (before the first eviction: a merge made earlier is stale from here on, whatever becomes of this call)
     int64_t lost = 0;
     auto evict_front = [&]() {
         const auto &g = r->games.front();
@@ -1412,6 +1416,243 @@ extern "C" int bo_replay_sample_sparse_q(bo_replay *r, int32_t n, const int64_t 
     RT(RT_LAUNCH(bo_k_replay_encode_sparse_q, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
                  (const float *)r->pi_val, (const float *)r->z, (const float *)r->q, r->W, (const int *)r->s_slot, (const int *)r->s_k, states_dev,
                  (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev));
+    RT(rt_sync(stream));
+    return BO_OK;
+}
+
+// ---- merged targets (bo_merge.h; ABI 17) ---------------------------------------------------------------------------------------------
+static_assert(BO_MERGE_KEY_INPUT == MERGE_KEY_INPUT && BO_MERGE_KEY_POSITION == MERGE_KEY_POSITION, "merge constants");
+
+struct bo_replay_merge_s {
+    bo_replay *r = nullptr;
+    uint64_t epoch = 0;
+    int key = 0, Wm = 0;
+    int64_t n = 0, G = 0, T = 0, largest = 0, in_multi = 0;
+    double group_ms = 0.0, merge_ms = 0.0;
+    std::vector<int32_t> group_of;   // [records of the buffer] the record's group, -1 = not covered
+    std::vector<int64_t> rep_of;     // [n] work-list order: the representative of the item's group
+    std::vector<int64_t> reps;       // [G] ascending
+    std::vector<int32_t> count;      // [G]
+    int *m_idx = nullptr, *s_grp = nullptr;
+    float *m_val = nullptr, *m_z = nullptr, *m_q = nullptr;
+    int s_cap = 0;
+    std::vector<int> h_grp;
+};
+
+extern "C" void bo_replay_merge_destroy(bo_replay_merge *m) {
+    if (!m) return;
+    rt_free(m->m_idx); rt_free(m->m_val); rt_free(m->m_z); rt_free(m->m_q); rt_free(m->s_grp);
+    delete m;
+}
+
+namespace {
+struct MergeScratch {  // device scratch of one bo_replay_merge_create_ex call
+    std::vector<void *> p;
+    ~MergeScratch() { for (void *q : p) rt_free(q); }
+    template <class T> int get(T **out, size_t n) {
+        void *q = nullptr;
+        const int rc = rt_malloc(&q, n * sizeof(T));
+        if (!rc) p.push_back(q);
+        *out = (T *)q;
+        return rc;
+    }
+};
+#if !defined(BO_WAVE_EMU)
+struct MergeClock {  // device events around the kernels (timing events: rt_event has none)
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    MergeClock() { for (auto &x : e) (void)hipEventCreate(&x); }
+    ~MergeClock() { for (auto &x : e) if (x) (void)hipEventDestroy(x); }
+    void mark(int i, void *s) { if (e[i]) (void)hipEventRecord(e[i], (hipStream_t)s); }
+    double ms(int i) { float t = 0.0f; return (e[i] && e[i + 1] && hipEventElapsedTime(&t, e[i], e[i + 1]) == hipSuccess) ? (double)t : 0.0; }
+};
+#else
+struct MergeClock { void mark(int, void *) {} double ms(int) { return 0.0; } };
+#endif
+}  // namespace
+
+extern "C" int bo_replay_merge_create_ex(bo_replay *r, int64_t n, const int64_t *record_index, int32_t key, int64_t table_slots, void *stream,
+                                         bo_replay_merge **out) {
+    const std::string who = "bo_replay_merge_create";
+    if (!r || !out) return fail(BO_E_ARG, who + ": null argument");
+    if (key != MERGE_KEY_INPUT && key != MERGE_KEY_POSITION) return fail(BO_E_ARG, who + ": unknown key (0 = input, 1 = position)");
+    if (!record_index) n = r->n_records;
+    if (n < 1) return fail(BO_E_ARG, who + ": no records");
+    if (r->n_records > (int64_t)MERGE_CANON_NONE) return fail(BO_E_ARG, who + ": more than 0x7f7f7f7f resident records");
+    int64_t T = table_slots;
+    if (n > ((int64_t)1 << 29)) return fail(BO_E_ARG, who + ": more than 2^29 records");
+    if (T == 0) for (T = 64; T < 2 * n; T <<= 1) {}
+    if (T < 1 || T > ((int64_t)1 << 30) || (T & (T - 1)) != 0) return fail(BO_E_ARG, who + ": table_slots must be 0 or a power of two, 1 .. 2^30");
+    if (r->prefix.empty()) {
+        int64_t acc = 0;
+        for (const auto &g : r->games) { r->prefix.push_back(acc); acc += g.n_rec; }
+        r->prefix.push_back(acc);
+    }
+    std::unique_ptr<bo_replay_merge, void (*)(bo_replay_merge *)> m(new bo_replay_merge(), bo_replay_merge_destroy);
+    m->r = r; m->epoch = r->epoch; m->key = key; m->n = n; m->T = T;
+    m->group_of.assign((size_t)r->n_records, -1);
+    std::vector<int> h_slot((size_t)n), h_k((size_t)n), h_rec((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t q = record_index ? record_index[i] : i;
+        if (q < 0 || q >= r->n_records) return fail(BO_E_ARG, who + ": record index out of range");
+        if (m->group_of[(size_t)q] != -1) return fail(BO_E_ARG, who + ": record " + std::to_string(q) + " is listed twice");
+        m->group_of[(size_t)q] = -2;
+        const size_t g = (size_t)(std::upper_bound(r->prefix.begin(), r->prefix.end(), q) - r->prefix.begin()) - 1;
+        h_k[(size_t)i] = (int)(q - r->prefix[g]);
+        h_slot[(size_t)i] = (int)(r->games[g].start + h_k[(size_t)i]);
+        h_rec[(size_t)i] = (int)q;
+    }
+    RT(rt_set_device(r->device));
+    MergeScratch sc;
+    MergeClock clk;
+    MergeGroupArgs ga = {};
+    int *d_slot = nullptr, *d_k = nullptr, *d_rec = nullptr;
+    int rc = sc.get(&d_slot, (size_t)n);
+    if (!rc) rc = sc.get(&d_k, (size_t)n);
+    if (!rc) rc = sc.get(&d_rec, (size_t)n);
+    if (!rc) rc = sc.get(&ga.owner, (size_t)T);
+    if (!rc) rc = sc.get(&ga.canon, (size_t)T);
+    if (!rc) rc = sc.get(&ga.gid, (size_t)n);
+    if (!rc) rc = sc.get(&ga.status, 1);
+    if (!rc) rc = rt_h2d(d_slot, h_slot.data(), (size_t)n * 4, stream);
+    if (!rc) rc = rt_h2d(d_k, h_k.data(), (size_t)n * 4, stream);
+    if (!rc) rc = rt_h2d(d_rec, h_rec.data(), (size_t)n * 4, stream);
+    if (!rc) rc = rt_memset(ga.owner, 0xFF, (size_t)T * 4, stream);
+    if (!rc) rc = rt_memset(ga.canon, 0x7F, (size_t)T * 4, stream);
+    if (!rc) rc = rt_memset(ga.status, 0, 4, stream);
+    ga.pos = r->pos; ga.rep = r->rep; ga.slot = d_slot; ga.k = d_k; ga.rec = d_rec; ga.n = n; ga.T = T; ga.key = key;
+    clk.mark(0, stream);
+    if (!rc) rc = RT_LAUNCH(bo_k_replay_group, (int)((n + 63) / 64), stream, ga);
+    clk.mark(1, stream);
+    std::vector<int32_t> gid((size_t)n), canon((size_t)T);
+    int32_t over = 0;
+    if (!rc) rc = rt_d2h(gid.data(), ga.gid, (size_t)n * 4, stream);
+    if (!rc) rc = rt_d2h(canon.data(), ga.canon, (size_t)T * 4, stream);
+    if (!rc) rc = rt_d2h(&over, ga.status, 4, stream);
+    if (!rc) rc = rt_sync(stream);
+    if (rc) return fail(BO_E_HIP, who + ": " + rt_errstr(rc));
+    m->group_ms = clk.ms(0);
+    if (over)
+        return fail(BO_E_STATE, who + ": table overflow: " + std::to_string(over) + " of " + std::to_string(n) + " records found no slot among " +
+                                    std::to_string(T));
+    // groups in ascending order of their representative, members in ascending record index: a stable counting sort on the host
+    m->rep_of.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t s = gid[(size_t)i];
+        if (s < 0 || s >= T || canon[(size_t)s] < 0 || canon[(size_t)s] >= r->n_records || m->group_of[(size_t)canon[(size_t)s]] == -1)
+            return fail(BO_E_STATE, who + ": inconsistent table");
+        m->rep_of[(size_t)i] = canon[(size_t)s];
+    }
+    std::vector<int64_t> order((size_t)n);
+    for (int64_t i = 0; i < n; i++) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return h_rec[(size_t)x] < h_rec[(size_t)y]; });
+    for (int64_t j = 0; j < n; j++) {  // ascending record index: a group's representative comes before its other members
+        const int64_t i = order[(size_t)j];
+        if (m->rep_of[(size_t)i] == h_rec[(size_t)i]) {
+            m->group_of[(size_t)h_rec[(size_t)i]] = (int32_t)m->reps.size();
+            m->reps.push_back(h_rec[(size_t)i]);
+        }
+    }
+    const int64_t G = m->G = (int64_t)m->reps.size();
+    m->count.assign((size_t)G, 0);
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t g = m->group_of[(size_t)m->rep_of[(size_t)i]];
+        if (g < 0) return fail(BO_E_STATE, who + ": inconsistent table");
+        m->group_of[(size_t)h_rec[(size_t)i]] = g;
+        m->count[(size_t)g]++;
+    }
+    std::vector<int> off((size_t)G + 1, 0), fill((size_t)G), mslot((size_t)n);
+    for (int64_t g = 0; g < G; g++) {
+        off[(size_t)g + 1] = off[(size_t)g] + m->count[(size_t)g];
+        fill[(size_t)g] = off[(size_t)g];
+        m->largest = std::max<int64_t>(m->largest, m->count[(size_t)g]);
+        m->in_multi += m->count[(size_t)g] > 1 ? m->count[(size_t)g] : 0;
+    }
+    for (int64_t j = 0; j < n; j++) {
+        const int64_t i = order[(size_t)j];
+        mslot[(size_t)fill[(size_t)m->group_of[(size_t)h_rec[(size_t)i]]]++] = h_slot[(size_t)i];
+    }
+    MergeArgs ma = {};
+    int *d_off = nullptr, *d_mslot = nullptr;
+    rc = sc.get(&d_off, (size_t)G + 1);
+    if (!rc) rc = sc.get(&d_mslot, (size_t)n);
+    if (!rc) rc = sc.get(&ma.usz, (size_t)G);
+    if (!rc) rc = rt_h2d(d_off, off.data(), ((size_t)G + 1) * 4, stream);
+    if (!rc) rc = rt_h2d(d_mslot, mslot.data(), (size_t)n * 4, stream);
+    ma.pi_n = r->pi_n; ma.pi_idx = r->pi_idx; ma.pi_val = r->pi_val; ma.z = r->z; ma.q = r->q; ma.W = r->W; ma.off = d_off; ma.mslot = d_mslot;
+    ma.Wm = 0; ma.out_idx = nullptr; ma.out_val = ma.out_z = ma.out_q = nullptr;
+    clk.mark(1, stream);
+    if (!rc) rc = RT_LAUNCH(bo_k_replay_merge, (int)G, stream, ma);  // the counting pass: the unions' sizes
+    std::vector<int32_t> usz((size_t)G);
+    if (!rc) rc = rt_d2h(usz.data(), ma.usz, (size_t)G * 4, stream);
+    if (!rc) rc = rt_sync(stream);
+    if (rc) return fail(BO_E_HIP, who + ": " + rt_errstr(rc));
+    m->Wm = r->W;
+    for (int64_t g = 0; g < G; g++) {
+        if (usz[(size_t)g] > BO_RES_CAP)
+            return fail(BO_E_ARG, who + ": the group of record " + std::to_string(m->reps[(size_t)g]) + " (" + std::to_string(m->count[(size_t)g]) +
+                                      " records) has more than " + std::to_string(BO_RES_CAP) + " distinct actions in its pis");
+        m->Wm = std::max(m->Wm, (int)usz[(size_t)g]);
+    }
+    const size_t cells = (size_t)G * (size_t)m->Wm;
+    rc = rt_malloc((void **)&m->m_idx, cells * 4);
+    if (!rc) rc = rt_malloc((void **)&m->m_val, cells * 4);
+    if (!rc) rc = rt_malloc((void **)&m->m_z, (size_t)G * 4);
+    if (!rc) rc = rt_malloc((void **)&m->m_q, (size_t)G * 4);
+    ma.Wm = m->Wm; ma.out_idx = m->m_idx; ma.out_val = m->m_val; ma.out_z = m->m_z; ma.out_q = m->m_q;
+    if (!rc) rc = RT_LAUNCH(bo_k_replay_merge, (int)G, stream, ma);
+    clk.mark(2, stream);
+    if (!rc) rc = rt_sync(stream);
+    if (rc) return fail(BO_E_HIP, who + ": " + rt_errstr(rc));
+    m->merge_ms = clk.ms(1);
+    *out = m.release();
+    return BO_OK;
+}
+
+extern "C" int bo_replay_merge_create(bo_replay *r, int64_t n, const int64_t *record_index, int32_t key, bo_replay_merge **out) {
+    return bo_replay_merge_create_ex(r, n, record_index, key, 0, nullptr, out);
+}
+
+extern "C" int bo_replay_merge_info(const bo_replay_merge *m, bo_merge_info *out) {
+    if (!m || !out) return fail(BO_E_ARG, "bo_replay_merge_info: null argument");
+    out->groups = m->G; out->width = m->Wm; out->records = m->n; out->largest_group = m->largest; out->records_in_groups = m->in_multi;
+    out->table_slots = m->T; out->group_ms = m->group_ms; out->merge_ms = m->merge_ms;
+    return BO_OK;
+}
+
+extern "C" int bo_replay_merge_groups(const bo_replay_merge *m, int64_t *representative, int32_t *count) {
+    if (!m || (!representative && !count)) return fail(BO_E_ARG, "bo_replay_merge_groups: null argument");
+    if (representative) memcpy(representative, m->rep_of.data(), (size_t)m->n * sizeof(int64_t));
+    if (count) memcpy(count, m->count.data(), (size_t)m->G * sizeof(int32_t));
+    return BO_OK;
+}
+
+// bo_replay_sample_sparse_q's batch with the targets of the records' groups: pi_idx / pi_val [n, Wm], z [n], q [n].
+extern "C" int bo_replay_sample_merged(bo_replay *r, bo_replay_merge *m, int32_t n, const int64_t *record_index, float *states_dev,
+                                       int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev, void *stream) {
+    if (!r || !m || n < 1 || !record_index || !states_dev || !pi_idx_dev || !pi_val_dev || !z_dev || !q_dev)
+        return fail(BO_E_ARG, "bo_replay_sample_merged: bad arguments");
+    if (m->r != r) return fail(BO_E_ARG, "bo_replay_sample_merged: the merge was made from another buffer");
+    if (m->epoch != r->epoch) return fail(BO_E_ARG, "bo_replay_sample_merged: stale merge: games were added to the buffer after it was made");
+    m->h_grp.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int64_t q = record_index[i];
+        if (q < 0 || q >= r->n_records) return fail(BO_E_ARG, "bo_replay_sample_merged: record index out of range");
+        if (m->group_of[(size_t)q] < 0) return fail(BO_E_ARG, "bo_replay_sample_merged: record " + std::to_string(q) + " is not covered by the merge");
+        m->h_grp[(size_t)i] = m->group_of[(size_t)q];
+    }
+    const int rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_merged");
+    if (rc) return rc;
+    if (n > m->s_cap) {
+        RT(rt_sync(stream));
+        rt_free(m->s_grp);
+        m->s_grp = nullptr; m->s_cap = 0;
+        RT(rt_malloc((void **)&m->s_grp, (size_t)n * 4));
+        m->s_cap = n;
+    }
+    RT(rt_h2d(m->s_grp, m->h_grp.data(), (size_t)n * 4, stream));
+    RT(RT_LAUNCH(bo_k_replay_encode_merged, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->s_slot, (const int *)r->s_k,
+                 (const int *)m->s_grp, m->Wm, (const int *)m->m_idx, (const float *)m->m_val, (const float *)m->m_z, (const float *)m->m_q,
+                 states_dev, (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev));
     RT(rt_sync(stream));
     return BO_OK;
 }

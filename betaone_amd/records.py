@@ -386,32 +386,75 @@ class GpuReplayBuffer:
                                                        val.data_ptr(), zs.data_ptr(), qs.data_ptr(), self._stream()))
         return states, idx, val, zs, qs
 
+    def merge_duplicates(self, index=None, key: str = "input", table_slots: int = 0) -> "MergedTargets":
+        """One target per distinct input among the records `index` (None: every resident record): csrc/bo_merge.h groups the records on
+        the device and averages each group's sparse pi, z and q (float64 sums in ascending record index, one rounding to float32).
+        key "input": records whose 120 planes are equal; "position": records whose current board has the same transposition key
+        (histories and counters ignored).  The result is good until the next add(): batch_merged then raises.  table_slots: the size
+        of the grouping table, a power of two (0: the library picks one of at least twice the records)."""
+        if key not in MERGE_KEYS:
+            raise ValueError(f"merge_duplicates: key {key!r}: one of {sorted(MERGE_KEYS)}")
+        if index is not None:
+            index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+            if index.size == 0:
+                raise ValueError("merge_duplicates: an empty index")
+        h = C.c_void_p()
+        self._check(self.lib.bo_replay_merge_create_ex(self.h, 0 if index is None else int(index.size),
+                                                       None if index is None else index.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                       MERGE_KEYS[key], int(table_slots), self._stream(), C.byref(h)))
+        return MergedTargets(self, h, key, np.arange(len(self), dtype=np.int64) if index is None else index.copy())
+
+    def batch_merged(self, merged: "MergedTargets", record_index):
+        """batch_sparse_q's five-tuple for these records with the targets of their groups: the states are the records' own, pi_idx /
+        pi_val are [n, merged.width], values and root values the groups' means.  A record outside the merge, or a merge made before
+        the last add(), raises."""
+        if merged.h is None:
+            raise ValueError("batch_merged: the merge is closed")
+        q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
+        n, W = int(q.size), merged.width
+        kw = dict(dtype=torch.float32, device=self.device)
+        states, zs, qs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw), torch.empty((n, 1), **kw)
+        idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
+        self._check(self.lib.bo_replay_sample_merged(self.h, merged.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), states.data_ptr(),
+                                                     idx.data_ptr(), val.data_ptr(), zs.data_ptr(), qs.data_ptr(), self._stream()))
+        return states, idx, val, zs, qs
+
     def sample(self, batch_size: int, rng: Optional[np.random.Generator] = None):
         rng = rng if rng is not None else np.random.default_rng()
         return self.batch(rng.integers(0, len(self), size=int(batch_size)))
 
     def loader(self, batch_size: int, steps: Optional[int] = None, seed: Optional[int] = None, shuffle: bool = True, sparse: bool = False,
-               with_q: bool = False, index=None):
+               with_q: bool = False, index=None, merged: Optional["MergedTargets"] = None):
         """An iterable with DataLoader's contract for train_network (train.py:252: `for states, t_policies, t_values in dataloader`):
         one epoch over the resident records in a random order (shuffle=True, the reference's DataLoader(shuffle=True)), or `steps` batches
         drawn with replacement.  Batches are made on the buffer's device; the loop's `.to(config.DEVICE)` finds them there.
         sparse=True: the same batches as batch_sparse's (states, pi_idx, pi_val, values); with_q=True (sparse only): batch_sparse_q's
         five-tuples, the same records in the same order.
         index: draw only from these record indices (validate.holdout_games keeps held-out games out of training with it): an epoch is
-        one pass over them, `steps` batches are drawn from them with replacement.  None: every resident record, the draws as ever."""
+        one pass over them, `steps` batches are drawn from them with replacement.  None: every resident record, the draws as ever.
+        merged (sparse only): the same draws, each record with the targets of its group (batch_merged's five-tuples); the records
+        drawn -- `index`, or all of them -- must lie inside the merge."""
+        if merged is not None and not sparse:
+            raise ValueError("loader: merged needs sparse=True (the dense sampler has no merged targets)")
         if with_q and not sparse:
             raise ValueError("loader: with_q needs sparse=True (the dense sampler has no root values)")
         if index is not None:
             index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
             if index.size == 0 or int(index.min()) < 0 or int(index.max()) >= len(self):
                 raise ValueError(f"loader: index needs at least one record, all inside [0, {len(self)})")
-        return _ReplayLoader(self, int(batch_size), steps, seed, shuffle, sparse, with_q, index)
+        if merged is not None:
+            drawn = np.arange(len(self), dtype=np.int64) if index is None else index
+            if not bool(merged.covers(drawn).all()):
+                raise ValueError("loader: the records to draw from are not all inside the merge (merge_duplicates(index=...))")
+        return _ReplayLoader(self, int(batch_size), steps, seed, shuffle, sparse, with_q, index, merged)
 
 
 class _ReplayLoader:
-    def __init__(self, buf: GpuReplayBuffer, batch_size: int, steps, seed, shuffle, sparse=False, with_q=False, index=None):
+    def __init__(self, buf: GpuReplayBuffer, batch_size: int, steps, seed, shuffle, sparse=False, with_q=False, index=None, merged=None):
         self.buf, self.batch_size, self.steps, self.seed, self.shuffle = buf, batch_size, steps, seed, shuffle
         self.make = buf.batch_sparse_q if with_q else buf.batch_sparse if sparse else buf.batch
+        if merged is not None:
+            self.make = lambda q: buf.batch_merged(merged, q)
         self.index = index
 
     def _n(self) -> int:
@@ -431,6 +474,71 @@ class _ReplayLoader:
         order = rng.permutation(n) if self.shuffle else np.arange(n)
         for i in range(0, n, self.batch_size):
             yield self.make(pick(order[i:i + self.batch_size]))
+
+
+MERGE_KEYS = {"input": 0, "position": 1}   # BO_MERGE_KEY_* of include/betaone_engine.h
+
+
+class _MergeInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("groups", "width", "records", "largest_group", "records_in_groups", "table_slots")] + \
+               [("group_ms", C.c_double), ("merge_ms", C.c_double)]
+
+
+class MergedTargets:
+    """What GpuReplayBuffer.merge_duplicates returns: the groups of records with equal inputs and, on the device, one averaged target
+    per group.  representatives: the lowest record index of every group, ascending; counts: the groups' sizes in that order."""
+
+    def __init__(self, buf: GpuReplayBuffer, h, key: str, index: np.ndarray):
+        self.buf, self.h, self.key, self.index = buf, h, key, index
+        info = _MergeInfo()
+        buf._check(buf.lib.bo_replay_merge_info(h, C.byref(info)))
+        self.n_groups, self.width, self.n_records = int(info.groups), int(info.width), int(info.records)
+        self.largest_group, self.records_in_groups, self.table_slots = int(info.largest_group), int(info.records_in_groups), int(info.table_slots)
+        self.group_ms, self.merge_ms = float(info.group_ms), float(info.merge_ms)
+        rep = np.empty(self.n_records, dtype=np.int64)
+        self.counts = np.empty(self.n_groups, dtype=np.int32)
+        buf._check(buf.lib.bo_replay_merge_groups(h, rep.ctypes.data_as(C.POINTER(C.c_int64)), self.counts.ctypes.data_as(E._I32P)))
+        self.representatives = np.unique(rep)
+        assert self.representatives.size == self.n_groups
+        self._rep_of = np.full(len(buf), -1, dtype=np.int64)   # by record index; -1 = not covered
+        self._rep_of[index] = rep
+
+    def covers(self, record_index) -> np.ndarray:
+        q = np.asarray(record_index, dtype=np.int64)
+        inside = (q >= 0) & (q < self._rep_of.size)
+        return inside & (self._rep_of[np.where(inside, q, 0)] >= 0)
+
+    def representative_of(self, record_index):
+        """The lowest record index of the group of each record."""
+        q = np.asarray(record_index, dtype=np.int64)
+        if not bool(np.all(self.covers(q))):
+            raise ValueError("MergedTargets: a record outside the merge")
+        return self._rep_of[q]
+
+    def group_of(self, record_index):
+        """The group (an index into representatives / counts) of each record."""
+        r = np.searchsorted(self.representatives, self.representative_of(record_index))
+        return int(r) if np.ndim(record_index) == 0 else r
+
+    def report(self) -> dict:
+        """groups, records, the share of records in groups larger than one, the largest group, and the groups counted by size in
+        powers of two: histogram["2^k"] = groups of 2^k .. 2^(k+1) - 1 records."""
+        hist = {}
+        for k, c in zip(*np.unique(np.floor(np.log2(self.counts.astype(np.float64))).astype(np.int64), return_counts=True)):
+            hist[f"2^{int(k)}"] = int(c)
+        return {"key": self.key, "groups": self.n_groups, "records": self.n_records, "width": self.width,
+                "duplicate_share": self.records_in_groups / self.n_records, "largest_group": self.largest_group, "histogram": hist}
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.buf.lib.bo_replay_merge_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def all_gather_bytes(payload: bytes, device: Optional[torch.device] = None, group=None) -> List[bytes]:

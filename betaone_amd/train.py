@@ -12,6 +12,7 @@ backward passes are PyTorch's (MIOpen); only the loss and its gradient are hand-
     python -m betaone_amd.train --iteration 3 --data-dir data --save-dir checkpoints --candidate cand.pth
     python -m betaone_amd.train --value-mix 0.5 ...     # records of selfplay_main --record-values, or of a run with resignation
     python -m betaone_amd.train --holdout-fraction 0.05 ...   # 5 % of the games never train; validated after every epoch (validate.py)
+    python -m betaone_amd.train --merge-duplicates input ...  # records with equal inputs train on their group's mean pi, z and q (csrc/bo_merge.h)
     python -m betaone_amd.match checkpoints/best_model.pth cand.pth --promote checkpoints/best_model.pth
 """
 from __future__ import annotations
@@ -312,6 +313,12 @@ def main(argv=None) -> int:
     ap.add_argument("--value-mix", type=float, default=0.0, metavar="A",
                     help="regress the value head on (1 - A) z + A q, q the records' root values (selfplay_main --record-values or a resign "
                          "threshold); 0 = the game's outcome alone, as the reference trains")
+    ap.add_argument("--merge-duplicates", choices=sorted(R.MERGE_KEYS), default=None, metavar="KEY",
+                    help="average the targets of training records that recur: 'input' merges records whose 120 planes are equal, 'position' "
+                         "those whose current board is (GpuReplayBuffer.merge_duplicates); held-out games never contribute")
+    ap.add_argument("--merge-sample", choices=("records", "groups"), default="records",
+                    help="with --merge-duplicates: 'records' draws as ever and replaces each record's targets by its group's; 'groups' draws "
+                         "one record per group, so every distinct input counts once per epoch")
     ap.add_argument("--holdout-fraction", type=float, default=0.0, metavar="F",
                     help="keep this share of the games (whole games, chosen by a hash of iteration, game id and --holdout-seed) out of "
                          "training and evaluate them after every epoch (betaone_amd.validate); 0 = train on everything")
@@ -322,6 +329,8 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.value_mix != 0.0 and a.dense_loss:
         ap.error("--value-mix needs the sparse loss: not with --dense-loss")
+    if a.merge_duplicates and a.dense_loss:
+        ap.error("--merge-duplicates needs the sparse loss: not with --dense-loss")
     if not 0.0 <= a.value_mix <= 1.0:
         ap.error(f"--value-mix {a.value_mix}: a mix in [0, 1]")
     if not 0.0 <= a.holdout_fraction < 1.0:
@@ -387,12 +396,24 @@ def main(argv=None) -> int:
     if a.value_mix > 0.0:
         log(f"value target (1 - {a.value_mix}) z + {a.value_mix} q: {with_values} of {len(buf)} records carry a root value (the rest train on z)")
 
+    merged = merge_report = None
+    draw_index = train_index
+    if a.merge_duplicates:  # over the training records only: a held-out game's targets never reach a training target
+        merged = buf.merge_duplicates(index=train_index, key=a.merge_duplicates)
+        merge_report = dict(merged.report(), sample=a.merge_sample)
+        if a.merge_sample == "groups":
+            draw_index = merged.representatives
+        merge_report["records_per_epoch"] = int(len(buf) if draw_index is None else draw_index.size)
+        log(f"merged targets ({a.merge_duplicates}): {merged.n_groups} groups of {merged.n_records} records, "
+            f"{100.0 * merge_report['duplicate_share']:.1f}% of them in groups larger than one, largest {merged.largest_group}, "
+            f"pi width {merged.width}; sampling {a.merge_sample}: {merge_report['records_per_epoch']} per epoch")
+
     amp = not a.no_amp
     scaler = torch.GradScaler(dev.type, enabled=amp)
     epochs = []
     for ep in range(a.epochs):
         loader = buf.loader(a.batch, steps=a.steps_per_epoch, seed=a.seed * 1000003 + iteration * 1009 + ep, sparse=not a.dense_loss,
-                            with_q=a.value_mix > 0.0, index=train_index)
+                            with_q=a.value_mix > 0.0, index=draw_index, merged=merged)
         lr = optimizer.param_groups[0]["lr"]
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
@@ -414,6 +435,8 @@ def main(argv=None) -> int:
             val = f"; val policy {fmt(o['policy_ce'])} top1 {fmt(o['policy_top1'])} value {fmt(o['value_mse_z'])}"
         log(f"epoch {ep + 1}/{a.epochs}: loss {r['loss'][0]:.4f} policy {r['loss'][1]:.4f} value {r['loss'][2]:.4f} "
             f"({r['steps']} steps, {r['samples'] / dt if dt > 0 else 0:.0f} samples/s){val}")
+    if merged is not None:
+        merged.close()
     buf.close()
 
     os.makedirs(a.save_dir, exist_ok=True)
@@ -429,6 +452,8 @@ def main(argv=None) -> int:
                    "amp": amp, "batch": a.batch, "value_mix": a.value_mix, "epochs": epochs, "checkpoint": ck_path, "weights": weights}
         if held_index is not None:
             summary.update(holdout_fraction=a.holdout_fraction, holdout_seed=a.holdout_seed, held_out_records=int(held_index.size))
+        if merge_report is not None:
+            summary["merge"] = merge_report
         with open(a.out, "w") as f:
             json.dump(summary, f, indent=1)
     return 0

@@ -39,7 +39,7 @@ extern "C" {
  * bo_reanalysis_result, status bit BO_ST_PI_OVERFLOW -- additions only; 16: opening books -- bo_book_insert -- addition only).
  * A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 16
+#define BO_ABI_VERSION 17
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -478,6 +478,44 @@ int bo_replay_values(bo_replay *rb, int64_t *n_records_with_value);
 int bo_replay_sample_sparse_q(bo_replay *rb, int32_t n, const int64_t *record_index, float *states_dev, int32_t *pi_idx_dev,
                               float *pi_val_dev, float *z_dev, float *q_dev, void *stream);
 void bo_replay_destroy(bo_replay *rb);
+
+/* ---- (ABI 17, addition) merged targets: csrc/bo_merge.h, records.GpuReplayBuffer.merge_duplicates ----------------------------------
+ * The records of a training window whose inputs coincide (every game's ply 0, the shared opening plies) are grouped on the device and
+ * each group gets ONE target: the mean of its members' sparse pi (the union of their actions in ascending order), z and q -- summed in
+ * float64 over the members in ascending record index, divided by the count and rounded once to float32.  A group of one keeps its
+ * record's entries in the record's order and z, q bit for bit.
+ *   key BO_MERGE_KEY_INPUT: two records are equal iff bo_replay_sample writes the same 120 planes for them (up to 8 boards with their
+ *     repetition planes, turn, castling, both counters, the en-passant square).  BO_MERGE_KEY_POSITION: the transposition key of the
+ *     current board alone (histories and counters are ignored; the legal moves are the same).
+ *   bo_replay_merge_create: record_index [n] distinct resident records in any order (n <= 2^29), or NULL: every resident record (n is
+ *     ignored).
+ *     The result does not depend on the order of the list.  Synchronous (null stream).  _ex: table_slots = the grouping table's size, a
+ *     power of two up to 2^30 (0: the smallest one >= 2 n, at least 64); a table with fewer slots than there are groups is BO_E_STATE ("table
+ *     overflow").  A group whose pis hold more than 256 distinct actions (impossible for legal pis) is BO_E_ARG, naming the group's
+ *     representative record.
+ *   bo_replay_merge_info: groups; width Wm = max(pi_width, largest union); records covered; largest group; records in groups of more
+ *     than one; the table's size; device-event times of the grouping kernel and of the two merge launches (0 where there are none).
+ *   bo_replay_merge_groups: representative [records] = per covered record, in the order of the list the merge was made from, the LOWEST
+ *     record index of its group; count [groups] in ascending order of the groups' representatives.  Either may be NULL.
+ *   bo_replay_sample_merged: bo_replay_sample_sparse_q's batch -- states bit-identical for the same indices -- with the targets of the
+ *     records' groups: pi_idx / pi_val [n, Wm] (unused slots -1 / 0), z [n], q [n].  One launch.  BO_E_ARG: a merge of another buffer;
+ *     a record the merge does not cover; a "stale merge" -- any bo_replay_add_game* on the buffer after the merge was made (records
+ *     move and leave: make a new one). */
+typedef struct bo_replay_merge_s bo_replay_merge;
+#define BO_MERGE_KEY_INPUT 0
+#define BO_MERGE_KEY_POSITION 1
+typedef struct bo_merge_info {
+    int64_t groups, width, records, largest_group, records_in_groups, table_slots;
+    double group_ms, merge_ms;
+} bo_merge_info;
+int bo_replay_merge_create(bo_replay *rb, int64_t n, const int64_t *record_index, int32_t key, bo_replay_merge **out);
+int bo_replay_merge_create_ex(bo_replay *rb, int64_t n, const int64_t *record_index, int32_t key, int64_t table_slots, void *stream,
+                              bo_replay_merge **out);
+int bo_replay_merge_info(const bo_replay_merge *m, bo_merge_info *out);
+int bo_replay_merge_groups(const bo_replay_merge *m, int64_t *representative, int32_t *count);
+int bo_replay_sample_merged(bo_replay *rb, bo_replay_merge *m, int32_t n, const int64_t *record_index, float *states_dev,
+                            int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev, void *stream);
+void bo_replay_merge_destroy(bo_replay_merge *m);
 
 /* ---- (ABI 4) the residual tower of ONE board (a few boards) as ONE launch spread over the chip: csrc/bo_tower_b1.h ----------------
  * Replaces, for uci.py's single-position searches (/root/reference/uci.py:60-93 -> mcts.py:183-185: PolicyValueNet.forward at
