@@ -1233,6 +1233,9 @@ struct bo_replay_s {
     int64_t n_valued = 0;                                 // resident records that carry a root value
     uint64_t epoch = 0;                                   // counts the games added: a bo_replay_merge is good for the epoch it was made in
     int s_cap = 0;
+    int *s_sym = nullptr;                                 // [sym_cap] a batch's symmetry codes (the _sym samplers)
+    int sym_cap = 0;
+    std::vector<int> h_sym;
     struct Game { int64_t start; int32_t n_rec; int32_t game_id; bool valued; };
     std::deque<Game> games;
     std::vector<int64_t> prefix;   // prefix[i] = records of games[0..i) (rebuilt after an add)
@@ -1263,7 +1266,7 @@ extern "C" int bo_replay_create(int64_t capacity_positions, int pi_width, int de
 
 extern "C" void bo_replay_destroy(bo_replay *r) {
     if (!r) return;
-    rt_free(r->pos); rt_free(r->rep); rt_free(r->pi_n); rt_free(r->pi_idx); rt_free(r->pi_val); rt_free(r->z); rt_free(r->q); rt_free(r->s_slot); rt_free(r->s_k);
+    rt_free(r->pos); rt_free(r->rep); rt_free(r->pi_n); rt_free(r->pi_idx); rt_free(r->pi_val); rt_free(r->z); rt_free(r->q); rt_free(r->s_slot); rt_free(r->s_k); rt_free(r->s_sym);
     delete r;
 }
 
@@ -1416,6 +1419,71 @@ extern "C" int bo_replay_sample_sparse_q(bo_replay *r, int32_t n, const int64_t 
     RT(RT_LAUNCH(bo_k_replay_encode_sparse_q, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
                  (const float *)r->pi_val, (const float *)r->z, (const float *)r->q, r->W, (const int *)r->s_slot, (const int *)r->s_k, states_dev,
                  (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev));
+    RT(rt_sync(stream));
+    return BO_OK;
+}
+
+// ---- board symmetries in the samplers (bo_sym.h; ABI 18) ------------------------------------------------------------------------------
+// A batch's symmetry codes: checked on the host (0..3, before anything is uploaded or launched) and uploaded to r->s_sym on `stream`.
+static int replay_check_sym(int32_t n, const int32_t *sym, const char *who) {
+    if (!sym) return fail(BO_E_ARG, std::string(who) + ": bad arguments");
+    for (int i = 0; i < n; i++)
+        if (sym[i] < 0 || sym[i] > 3) return fail(BO_E_ARG, std::string(who) + ": symmetry code " + std::to_string(sym[i]) + " of sample " + std::to_string(i) + " is not in 0..3");
+    return BO_OK;
+}
+static int replay_stage_sym(bo_replay *r, int32_t n, const int32_t *sym, void *stream) {
+    r->h_sym.assign(sym, sym + n);
+    if (n > r->sym_cap) {
+        RT(rt_sync(stream));
+        rt_free(r->s_sym);
+        r->s_sym = nullptr; r->sym_cap = 0;
+        RT(rt_malloc((void **)&r->s_sym, (size_t)n * 4));
+        r->sym_cap = n;
+    }
+    RT(rt_h2d(r->s_sym, r->h_sym.data(), (size_t)n * 4, stream));
+    return BO_OK;
+}
+
+extern "C" int bo_replay_sample_sym(bo_replay *r, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev, float *pi_dev,
+                                    float *z_dev, int32_t *applied_dev, void *stream) {
+    if (!r || n < 1 || !record_index || !states_dev || !pi_dev || !z_dev) return fail(BO_E_ARG, "bo_replay_sample_sym: bad arguments");
+    int rc = replay_check_sym(n, sym, "bo_replay_sample_sym");
+    if (!rc) rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_sym");
+    if (!rc) rc = replay_stage_sym(r, n, sym, stream);
+    if (rc) return rc;
+    RT(RT_LAUNCH(bo_k_replay_encode_sym, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
+                 (const float *)r->pi_val, (const float *)r->z, r->W, (const int *)r->s_slot, (const int *)r->s_k, (const int *)r->s_sym,
+                 states_dev, pi_dev, z_dev, (int *)applied_dev));
+    RT(rt_sync(stream));
+    return BO_OK;
+}
+
+extern "C" int bo_replay_sample_sparse_sym(bo_replay *r, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev,
+                                           int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, int32_t *applied_dev, void *stream) {
+    if (!r || n < 1 || !record_index || !states_dev || !pi_idx_dev || !pi_val_dev || !z_dev) return fail(BO_E_ARG, "bo_replay_sample_sparse_sym: bad arguments");
+    int rc = replay_check_sym(n, sym, "bo_replay_sample_sparse_sym");
+    if (!rc) rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_sparse_sym");
+    if (!rc) rc = replay_stage_sym(r, n, sym, stream);
+    if (rc) return rc;
+    RT(RT_LAUNCH(bo_k_replay_encode_sparse_sym, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
+                 (const float *)r->pi_val, (const float *)r->z, r->W, (const int *)r->s_slot, (const int *)r->s_k, (const int *)r->s_sym,
+                 states_dev, (int *)pi_idx_dev, pi_val_dev, z_dev, (int *)applied_dev));
+    RT(rt_sync(stream));
+    return BO_OK;
+}
+
+extern "C" int bo_replay_sample_sparse_q_sym(bo_replay *r, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev,
+                                             int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev, int32_t *applied_dev,
+                                             void *stream) {
+    if (!r || n < 1 || !record_index || !states_dev || !pi_idx_dev || !pi_val_dev || !z_dev || !q_dev)
+        return fail(BO_E_ARG, "bo_replay_sample_sparse_q_sym: bad arguments");
+    int rc = replay_check_sym(n, sym, "bo_replay_sample_sparse_q_sym");
+    if (!rc) rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_sparse_q_sym");
+    if (!rc) rc = replay_stage_sym(r, n, sym, stream);
+    if (rc) return rc;
+    RT(RT_LAUNCH(bo_k_replay_encode_sparse_q_sym, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n,
+                 (const int *)r->pi_idx, (const float *)r->pi_val, (const float *)r->z, (const float *)r->q, r->W, (const int *)r->s_slot,
+                 (const int *)r->s_k, (const int *)r->s_sym, states_dev, (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev, (int *)applied_dev));
     RT(rt_sync(stream));
     return BO_OK;
 }
@@ -1627,20 +1695,28 @@ extern "C" int bo_replay_merge_groups(const bo_replay_merge *m, int64_t *represe
 }
 
 // bo_replay_sample_sparse_q's batch with the targets of the records' groups: pi_idx / pi_val [n, Wm], z [n], q [n].
-extern "C" int bo_replay_sample_merged(bo_replay *r, bo_replay_merge *m, int32_t n, const int64_t *record_index, float *states_dev,
-                                       int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev, void *stream) {
+// sym (NULL: none): the batch under a board symmetry per sample (bo_replay_sample_merged_sym).
+static int replay_sample_merged(const char *who_c, bo_replay *r, bo_replay_merge *m, int32_t n, const int64_t *record_index, const int32_t *sym,
+                                bool with_sym, float *states_dev, int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev,
+                                int32_t *applied_dev, void *stream) {
+    const std::string who(who_c);
     if (!r || !m || n < 1 || !record_index || !states_dev || !pi_idx_dev || !pi_val_dev || !z_dev || !q_dev)
-        return fail(BO_E_ARG, "bo_replay_sample_merged: bad arguments");
-    if (m->r != r) return fail(BO_E_ARG, "bo_replay_sample_merged: the merge was made from another buffer");
-    if (m->epoch != r->epoch) return fail(BO_E_ARG, "bo_replay_sample_merged: stale merge: games were added to the buffer after it was made");
+        return fail(BO_E_ARG, who + ": bad arguments");
+    if (with_sym) {
+        const int rcs = replay_check_sym(n, sym, who_c);
+        if (rcs) return rcs;
+    }
+    if (m->r != r) return fail(BO_E_ARG, who + ": the merge was made from another buffer");
+    if (m->epoch != r->epoch) return fail(BO_E_ARG, who + ": stale merge: games were added to the buffer after it was made");
     m->h_grp.resize((size_t)n);
     for (int i = 0; i < n; i++) {
         const int64_t q = record_index[i];
-        if (q < 0 || q >= r->n_records) return fail(BO_E_ARG, "bo_replay_sample_merged: record index out of range");
-        if (m->group_of[(size_t)q] < 0) return fail(BO_E_ARG, "bo_replay_sample_merged: record " + std::to_string(q) + " is not covered by the merge");
+        if (q < 0 || q >= r->n_records) return fail(BO_E_ARG, who + ": record index out of range");
+        if (m->group_of[(size_t)q] < 0) return fail(BO_E_ARG, who + ": record " + std::to_string(q) + " is not covered by the merge");
         m->h_grp[(size_t)i] = m->group_of[(size_t)q];
     }
-    const int rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_merged");
+    int rc = replay_stage_indices(r, n, record_index, stream, who_c);
+    if (!rc && with_sym) rc = replay_stage_sym(r, n, sym, stream);
     if (rc) return rc;
     if (n > m->s_cap) {
         RT(rt_sync(stream));
@@ -1650,11 +1726,29 @@ extern "C" int bo_replay_sample_merged(bo_replay *r, bo_replay_merge *m, int32_t
         m->s_cap = n;
     }
     RT(rt_h2d(m->s_grp, m->h_grp.data(), (size_t)n * 4, stream));
-    RT(RT_LAUNCH(bo_k_replay_encode_merged, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->s_slot, (const int *)r->s_k,
-                 (const int *)m->s_grp, m->Wm, (const int *)m->m_idx, (const float *)m->m_val, (const float *)m->m_z, (const float *)m->m_q,
-                 states_dev, (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev));
+    if (with_sym)
+        RT(RT_LAUNCH(bo_k_replay_encode_merged_sym, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->s_slot,
+                     (const int *)r->s_k, (const int *)m->s_grp, m->Wm, (const int *)m->m_idx, (const float *)m->m_val, (const float *)m->m_z,
+                     (const float *)m->m_q, (const int *)r->s_sym, states_dev, (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev, (int *)applied_dev));
+    else
+        RT(RT_LAUNCH(bo_k_replay_encode_merged, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->s_slot, (const int *)r->s_k,
+                     (const int *)m->s_grp, m->Wm, (const int *)m->m_idx, (const float *)m->m_val, (const float *)m->m_z, (const float *)m->m_q,
+                     states_dev, (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev));
     RT(rt_sync(stream));
     return BO_OK;
+}
+
+extern "C" int bo_replay_sample_merged(bo_replay *r, bo_replay_merge *m, int32_t n, const int64_t *record_index, float *states_dev,
+                                       int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev, void *stream) {
+    return replay_sample_merged("bo_replay_sample_merged", r, m, n, record_index, nullptr, false, states_dev, pi_idx_dev, pi_val_dev, z_dev, q_dev,
+                                nullptr, stream);
+}
+
+extern "C" int bo_replay_sample_merged_sym(bo_replay *r, bo_replay_merge *m, int32_t n, const int64_t *record_index, const int32_t *sym,
+                                           float *states_dev, int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev,
+                                           int32_t *applied_dev, void *stream) {
+    return replay_sample_merged("bo_replay_sample_merged_sym", r, m, n, record_index, sym, true, states_dev, pi_idx_dev, pi_val_dev, z_dev, q_dev,
+                                applied_dev, stream);
 }
 
 // ---- PGN pretraining (bo_pgn.h) --------------------------------------------------------------------------------------------------

@@ -150,6 +150,11 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_replay_merge_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), _I32P]),
     "bo_replay_sample_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)] + [C.c_void_p] * 6),
     "bo_replay_merge_destroy": (None, [C.c_void_p]),
+    # (ABI 18) the samplers under a board symmetry per sample: host codes after the indices, the applied codes (device, may be NULL) last
+    "bo_replay_sample_sym": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _I32P] + [C.c_void_p] * 5),
+    "bo_replay_sample_sparse_sym": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _I32P] + [C.c_void_p] * 6),
+    "bo_replay_sample_sparse_q_sym": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _I32P] + [C.c_void_p] * 7),
+    "bo_replay_sample_merged_sym": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _I32P] + [C.c_void_p] * 7),
     "bo_nn_b1_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "bo_nn_b1_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "bo_nn_b1_status": (C.c_int, [C.c_void_p, _I32P, C.c_void_p]),
@@ -251,7 +256,7 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 17  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 18  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
 # BO_METRIC_ROW_* / BO_METRIC_* of include/betaone_engine.h by name (bo_train_metrics; tests/test_validate_emu.py compares with the header)
 METRIC_ROW = {name: k for k, name in enumerate((

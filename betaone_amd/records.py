@@ -352,34 +352,69 @@ class GpuReplayBuffer:
         self.n_evicted += lost
         return lost
 
-    def batch(self, record_index) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(states [n,120,8,8], policies [n,4672], values [n,1]) of the records with these indices (0 = oldest resident record)."""
+    def _sym_codes(self, sym, n: int, who: str):
+        """The per-record symmetry codes of a batch (csrc/bo_sym.h: bit 0 colour flip, bit 1 file mirror) as the library takes them,
+        and the tensor that receives the codes it applied."""
+        t = np.ascontiguousarray(sym, dtype=np.int32).reshape(-1)
+        if t.size != n:
+            raise ValueError(f"{who}: {t.size} symmetry codes for {n} records")
+        return t, torch.empty((n,), dtype=torch.int32, device=self.device)
+
+    def batch(self, record_index, sym=None):
+        """(states [n,120,8,8], policies [n,4672], values [n,1]) of the records with these indices (0 = oldest resident record).
+        sym (one code 0..3 per record: bit 0 = colour flip, bit 1 = file mirror): each record under that board symmetry -- the planes of
+        the transformed game, pi scattered to the transformed moves -- and a fourth element, applied [n] int32: the code that was
+        applied (the mirror bit is dropped while the record's position has a castling right)."""
         q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
         n = int(q.size)
         kw = dict(dtype=torch.float32, device=self.device)
+        if sym is not None:
+            t, applied = self._sym_codes(sym, n, "batch")
         states, pis, zs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, E.NUM_ACTIONS), **kw), torch.empty((n, 1), **kw)
+        if sym is not None:
+            self._check(self.lib.bo_replay_sample_sym(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), t.ctypes.data_as(E._I32P),
+                                                      states.data_ptr(), pis.data_ptr(), zs.data_ptr(), applied.data_ptr(), self._stream()))
+            return states, pis, zs, applied
         self._check(self.lib.bo_replay_sample(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), states.data_ptr(), pis.data_ptr(), zs.data_ptr(),
                                               self._stream()))
         return states, pis, zs
 
-    def batch_sparse(self, record_index) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    def batch_sparse(self, record_index, sym=None):
         """(states [n,120,8,8], pi_idx [n,W] int32, pi_val [n,W], values [n,1]) of the records with these indices: the states and
-        values of batch(), pi as the records keep it (W = pi_width; unused slots -1 / 0) for train.sparse_policy_value_loss."""
+        values of batch(), pi as the records keep it (W = pi_width; unused slots -1 / 0) for train.sparse_policy_value_loss.
+        sym: as batch(); pi_idx holds the transformed moves' indices in the records' entry order, and applied [n] comes last."""
         q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
         n, W = int(q.size), self.pi_width
         kw = dict(dtype=torch.float32, device=self.device)
+        if sym is not None:
+            t, applied = self._sym_codes(sym, n, "batch_sparse")
+            states, zs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw)
+            idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
+            self._check(self.lib.bo_replay_sample_sparse_sym(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), t.ctypes.data_as(E._I32P),
+                                                             states.data_ptr(), idx.data_ptr(), val.data_ptr(), zs.data_ptr(),
+                                                             applied.data_ptr(), self._stream()))
+            return states, idx, val, zs, applied
         states, zs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw)
         idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
         self._check(self.lib.bo_replay_sample_sparse(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), states.data_ptr(), idx.data_ptr(),
                                                      val.data_ptr(), zs.data_ptr(), self._stream()))
         return states, idx, val, zs
 
-    def batch_sparse_q(self, record_index) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    def batch_sparse_q(self, record_index, sym=None):
         """batch_sparse plus the records' root values q [n,1] (the search's value of the position for the side to move, as z is the
-        game's; q == z for a record without one) for train.sparse_policy_value_loss_mix.  One launch writes all five."""
+        game's; q == z for a record without one) for train.sparse_policy_value_loss_mix.  One launch writes all five.
+        sym: as batch_sparse(); z and q are from the side to move's point of view and do not change; applied [n] comes last."""
         q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
         n, W = int(q.size), self.pi_width
         kw = dict(dtype=torch.float32, device=self.device)
+        if sym is not None:
+            t, applied = self._sym_codes(sym, n, "batch_sparse_q")
+            states, zs, qs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw), torch.empty((n, 1), **kw)
+            idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
+            self._check(self.lib.bo_replay_sample_sparse_q_sym(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), t.ctypes.data_as(E._I32P),
+                                                               states.data_ptr(), idx.data_ptr(), val.data_ptr(), zs.data_ptr(), qs.data_ptr(),
+                                                               applied.data_ptr(), self._stream()))
+            return states, idx, val, zs, qs, applied
         states, zs, qs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw), torch.empty((n, 1), **kw)
         idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
         self._check(self.lib.bo_replay_sample_sparse_q(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), states.data_ptr(), idx.data_ptr(),
@@ -404,17 +439,26 @@ class GpuReplayBuffer:
                                                        MERGE_KEYS[key], int(table_slots), self._stream(), C.byref(h)))
         return MergedTargets(self, h, key, np.arange(len(self), dtype=np.int64) if index is None else index.copy())
 
-    def batch_merged(self, merged: "MergedTargets", record_index):
+    def batch_merged(self, merged: "MergedTargets", record_index, sym=None):
         """batch_sparse_q's five-tuple for these records with the targets of their groups: the states are the records' own, pi_idx /
         pi_val are [n, merged.width], values and root values the groups' means.  A record outside the merge, or a merge made before
-        the last add(), raises."""
+        the last add(), raises.
+        sym: as batch_sparse_q(): the group's mean targets are transformed on the way out (the grouping is untouched); applied [n]
+        comes last."""
         if merged.h is None:
             raise ValueError("batch_merged: the merge is closed")
         q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
         n, W = int(q.size), merged.width
         kw = dict(dtype=torch.float32, device=self.device)
+        if sym is not None:
+            t, applied = self._sym_codes(sym, n, "batch_merged")
         states, zs, qs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw), torch.empty((n, 1), **kw)
         idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
+        if sym is not None:
+            self._check(self.lib.bo_replay_sample_merged_sym(self.h, merged.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                             t.ctypes.data_as(E._I32P), states.data_ptr(), idx.data_ptr(), val.data_ptr(),
+                                                             zs.data_ptr(), qs.data_ptr(), applied.data_ptr(), self._stream()))
+            return states, idx, val, zs, qs, applied
         self._check(self.lib.bo_replay_sample_merged(self.h, merged.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), states.data_ptr(),
                                                      idx.data_ptr(), val.data_ptr(), zs.data_ptr(), qs.data_ptr(), self._stream()))
         return states, idx, val, zs, qs
@@ -424,7 +468,7 @@ class GpuReplayBuffer:
         return self.batch(rng.integers(0, len(self), size=int(batch_size)))
 
     def loader(self, batch_size: int, steps: Optional[int] = None, seed: Optional[int] = None, shuffle: bool = True, sparse: bool = False,
-               with_q: bool = False, index=None, merged: Optional["MergedTargets"] = None):
+               with_q: bool = False, index=None, merged: Optional["MergedTargets"] = None, augment: Optional[str] = None):
         """An iterable with DataLoader's contract for train_network (train.py:252: `for states, t_policies, t_values in dataloader`):
         one epoch over the resident records in a random order (shuffle=True, the reference's DataLoader(shuffle=True)), or `steps` batches
         drawn with replacement.  Batches are made on the buffer's device; the loop's `.to(config.DEVICE)` finds them there.
@@ -433,7 +477,13 @@ class GpuReplayBuffer:
         index: draw only from these record indices (validate.holdout_games keeps held-out games out of training with it): an epoch is
         one pass over them, `steps` batches are drawn from them with replacement.  None: every resident record, the draws as ever.
         merged (sparse only): the same draws, each record with the targets of its group (batch_merged's five-tuples); the records
-        drawn -- `index`, or all of them -- must lie inside the merge."""
+        drawn -- `index`, or all of them -- must lie inside the merge.
+        augment ("colour", "mirror", "both"; None: off): every sample under a board symmetry drawn uniformly from the allowed codes
+        ({0, 1}, {0, 2}, {0, 1, 2, 3}) by a SECOND generator, seeded from `seed` and a fixed salt: the records drawn are those of the
+        same loader without augment, in the same order.  The tuples are the same too; the codes that were applied to the last batch
+        (the mirror is dropped for a record with a castling right) are kept as loader.last_applied."""
+        if augment is not None and augment not in AUGMENT_CODES:
+            raise ValueError(f"loader: augment {augment!r}: None or one of {sorted(AUGMENT_CODES)}")
         if merged is not None and not sparse:
             raise ValueError("loader: merged needs sparse=True (the dense sampler has no merged targets)")
         if with_q and not sparse:
@@ -446,16 +496,38 @@ class GpuReplayBuffer:
             drawn = np.arange(len(self), dtype=np.int64) if index is None else index
             if not bool(merged.covers(drawn).all()):
                 raise ValueError("loader: the records to draw from are not all inside the merge (merge_duplicates(index=...))")
-        return _ReplayLoader(self, int(batch_size), steps, seed, shuffle, sparse, with_q, index, merged)
+        return _ReplayLoader(self, int(batch_size), steps, seed, shuffle, sparse, with_q, index, merged, augment)
+
+
+AUGMENT_CODES = {"colour": (0, 1), "mirror": (0, 2), "both": (0, 1, 2, 3)}   # the transform codes of csrc/bo_sym.h a loader draws from
+AUGMENT_SALT = 0x53594D4D   # "SYMM": the second generator of an augmenting loader is seeded from (seed, salt)
 
 
 class _ReplayLoader:
-    def __init__(self, buf: GpuReplayBuffer, batch_size: int, steps, seed, shuffle, sparse=False, with_q=False, index=None, merged=None):
+    def __init__(self, buf: GpuReplayBuffer, batch_size: int, steps, seed, shuffle, sparse=False, with_q=False, index=None, merged=None,
+                 augment=None):
         self.buf, self.batch_size, self.steps, self.seed, self.shuffle = buf, batch_size, steps, seed, shuffle
-        self.make = buf.batch_sparse_q if with_q else buf.batch_sparse if sparse else buf.batch
+        plain = buf.batch_sparse_q if with_q else buf.batch_sparse if sparse else buf.batch
         if merged is not None:
-            self.make = lambda q: buf.batch_merged(merged, q)
+            plain = lambda q, **kw: buf.batch_merged(merged, q, **kw)  # noqa: E731
+        self.make = plain
         self.index = index
+        self.augment, self.last_applied = augment, None
+        if augment is not None:
+            self._counts = torch.zeros(4, dtype=torch.int64, device=buf.device)   # kept on the device: counting waits for no kernel
+            self.make = lambda q: self._augmented(plain, q)
+
+    def _augmented(self, plain, q):
+        codes = np.asarray(AUGMENT_CODES[self.augment], dtype=np.int32)
+        out = plain(q, sym=codes[self._sym_rng.integers(0, codes.size, size=len(q))])
+        self.last_applied = out[-1]
+        self._counts += (out[-1].view(-1, 1) == torch.arange(4, dtype=torch.int32, device=out[-1].device)).sum(0)
+        return out[:-1]
+
+    @property
+    def applied_counts(self) -> np.ndarray:
+        """Samples handed out under each applied code 0..3 over the loader's life (zeros without augment)."""
+        return self._counts.cpu().numpy() if self.augment is not None else np.zeros(4, dtype=np.int64)
 
     def _n(self) -> int:
         return len(self.buf) if self.index is None else int(self.index.size)
@@ -465,6 +537,8 @@ class _ReplayLoader:
 
     def __iter__(self):
         rng = np.random.default_rng(self.seed)
+        if self.augment is not None:
+            self._sym_rng = np.random.default_rng(None if self.seed is None else [int(self.seed), AUGMENT_SALT])
         n = self._n()
         pick = (lambda k: k) if self.index is None else (lambda k: self.index[k])
         if self.steps is not None:

@@ -27,6 +27,7 @@ import sys
 import time
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -319,6 +320,10 @@ def main(argv=None) -> int:
     ap.add_argument("--merge-sample", choices=("records", "groups"), default="records",
                     help="with --merge-duplicates: 'records' draws as ever and replaces each record's targets by its group's; 'groups' draws "
                          "one record per group, so every distinct input counts once per epoch")
+    ap.add_argument("--augment", choices=("none",) + tuple(sorted(R.AUGMENT_CODES)), default="none",
+                    help="hand every training sample out under a random board symmetry (csrc/bo_sym.h): 'colour' = as it is or with the "
+                         "colours swapped, 'mirror' = as it is or with the files mirrored (records with a castling right stay as they are), "
+                         "'both' = one of the four; held-out validation stays untransformed")
     ap.add_argument("--holdout-fraction", type=float, default=0.0, metavar="F",
                     help="keep this share of the games (whole games, chosen by a hash of iteration, game id and --holdout-seed) out of "
                          "training and evaluate them after every epoch (betaone_amd.validate); 0 = train on everything")
@@ -411,9 +416,13 @@ def main(argv=None) -> int:
     amp = not a.no_amp
     scaler = torch.GradScaler(dev.type, enabled=amp)
     epochs = []
+    augment = None if a.augment == "none" else a.augment
+    applied_codes = np.zeros(4, dtype=np.int64)   # samples trained under each applied symmetry code
+    if augment:
+        log(f"augment {augment}: every sample under one of the codes {list(R.AUGMENT_CODES[augment])} (bit 0 colour flip, bit 1 file mirror)")
     for ep in range(a.epochs):
         loader = buf.loader(a.batch, steps=a.steps_per_epoch, seed=a.seed * 1000003 + iteration * 1009 + ep, sparse=not a.dense_loss,
-                            with_q=a.value_mix > 0.0, index=draw_index, merged=merged)
+                            with_q=a.value_mix > 0.0, index=draw_index, merged=merged, augment=augment)
         lr = optimizer.param_groups[0]["lr"]
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
@@ -421,6 +430,7 @@ def main(argv=None) -> int:
         r = train_steps(model, optimizer, scheduler, scaler, loader, sparse=not a.dense_loss, amp=amp, log_every=a.log_every, log=log,
                         value_mix=a.value_mix)
         dt = time.perf_counter() - t0  # (train_steps ends reading the losses: the device is done)
+        applied_codes += loader.applied_counts if augment else np.array([r["samples"], 0, 0, 0], dtype=np.int64)
         epochs.append({"epoch": ep, "steps": r["steps"], "samples": r["samples"], "loss": r["loss"][0], "policy_loss": r["loss"][1],
                        "value_loss": r["loss"][2], "lr": lr, "clipped": r["clipped"], "seconds": dt,
                        "steps_per_s": r["steps"] / dt if dt > 0 else None, "samples_per_s": r["samples"] / dt if dt > 0 else None,
@@ -449,7 +459,8 @@ def main(argv=None) -> int:
     log(f"checkpoint {ck_path}; weights {weights}")
     if a.out:
         summary = {"iteration": iteration, "records": sum(e["samples"] for e in epochs[:1]), "loss": "dense" if a.dense_loss else "sparse",
-                   "amp": amp, "batch": a.batch, "value_mix": a.value_mix, "epochs": epochs, "checkpoint": ck_path, "weights": weights}
+                   "amp": amp, "batch": a.batch, "value_mix": a.value_mix, "epochs": epochs, "checkpoint": ck_path, "weights": weights,
+                   "augment": a.augment, "applied_codes": {str(t): int(c) for t, c in enumerate(applied_codes)}}
         if held_index is not None:
             summary.update(holdout_fraction=a.holdout_fraction, holdout_seed=a.holdout_seed, held_out_records=int(held_index.size))
         if merge_report is not None:

@@ -196,11 +196,14 @@ def bucket_labels(buckets: Optional[str], edges: Sequence[int] = (10, 20)) -> Li
 
 
 def evaluate(model, buf: R.GpuReplayBuffer, record_index, *, batch: int, amp: bool, buckets: Optional[str] = None, with_q: bool = False,
-             edges: Sequence[int] = (10, 20)) -> Dict:
+             edges: Sequence[int] = (10, 20), sym: Optional[int] = None) -> Dict:
     """One validation pass of `model` over the records `record_index` of `buf`, in index order, `batch` at a time (the last batch may be
     short): model.eval() under torch.no_grad() (and torch.autocast when amp), the metrics of every batch added on the device, one copy
     at the end.  buckets: None, "phase" (edges: the men counts that end a bucket) or "calibration".  The model's train / eval mode is
-    restored.  Returns MetricsAccumulator.result() with "labels"."""
+    restored.  Returns MetricsAccumulator.result() with "labels".
+    sym (a transform code 1..3 of csrc/bo_sym.h; None: as the records are): every record is sampled under that board symmetry -- the net
+    sees the twin position and is scored against the twin's targets, so the tables of two passes compare side by side.  A record with a
+    castling right drops the mirror bit; the result gains "sym" and "applied_codes" (records per applied code)."""
     labels = bucket_labels(buckets, edges)
     index = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
     if index.size == 0:
@@ -208,10 +211,16 @@ def evaluate(model, buf: R.GpuReplayBuffer, record_index, *, batch: int, amp: bo
     acc = MetricsAccumulator(len(labels), buf.device)
     was_training = model.training
     model.eval()
+    codes = torch.zeros(4, dtype=torch.int64, device=buf.device)
     try:
         with torch.no_grad():
             for i in range(0, index.size, int(batch)):
-                b = (buf.batch_sparse_q if with_q else buf.batch_sparse)(index[i:i + int(batch)])
+                part = index[i:i + int(batch)]
+                if sym is None:
+                    b = (buf.batch_sparse_q if with_q else buf.batch_sparse)(part)
+                else:
+                    b = (buf.batch_sparse_q if with_q else buf.batch_sparse)(part, sym=np.full(part.size, int(sym), dtype=np.int32))
+                    codes += torch.bincount(b[-1].long(), minlength=4)[:4]
                 states = b[0]
                 with torch.autocast(states.device.type, enabled=amp):
                     logits, value = model(states)
@@ -221,7 +230,71 @@ def evaluate(model, buf: R.GpuReplayBuffer, record_index, *, batch: int, amp: bo
         model.train(was_training)
     out = acc.result()
     out["labels"] = labels
+    if sym is not None:
+        out["sym"] = int(sym)
+        out["applied_codes"] = {str(t): int(c) for t, c in enumerate(codes.cpu().tolist())}
     return out
+
+
+def without_castling_rights(games: Sequence[dict]) -> np.ndarray:
+    """Per record of the games in order (the buffer's record index space): True where the position has no castling right left, so the
+    file mirror applies to it."""
+    return np.array([int(g["positions"][i].castling) == 0 for g in games for i in range(int(g["n_plies"]))], dtype=bool)
+
+
+def symmetry_consistency(model, buf: R.GpuReplayBuffer, record_index, t: int, batch: int, amp: bool) -> Dict:
+    """How differently `model` scores a position x and its twin T x under the transform code t (csrc/bo_sym.h), over the records
+    `record_index`: per record the net is run on the plain sample and on the transformed one, the twin's logits are gathered back into
+    the original move indexing (symmetry.unmap_logits), and
+        kl               mean KL(p(x) || p(T x) mapped back), both softmaxes and the sum in float64
+        top1_agreement   the share of records whose best move is the same move
+        value_abs_diff   mean |v(x) - v(T x)| (the value is the side to move's: a symmetric net gives 0)
+    are taken over the records the code was applied to in full (a record with a castling right drops the mirror bit and is left out);
+    "records" counts them.  An equivariant net gives 0, 1, 0."""
+    from . import symmetry as S
+
+    t = int(t)
+    if t not in (1, 2, 3):
+        raise ValueError(f"symmetry_consistency: transform code {t}: 1..3")
+    index = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
+    if index.size == 0:
+        raise ValueError("symmetry_consistency: no records")
+    sums = torch.zeros(4, dtype=torch.float64, device=buf.device)   # records, kl, agreements, |dv|
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for i in range(0, index.size, int(batch)):
+                part = index[i:i + int(batch)]
+                x = buf.batch_sparse(part)[0]
+                tx, _, _, _, applied = buf.batch_sparse(part, sym=np.full(part.size, t, dtype=np.int32))
+                with torch.autocast(x.device.type, enabled=amp):
+                    logits, value = model(x)
+                    logits_t, value_t = model(tx)
+                full = (applied == t).double()
+                lp = torch.log_softmax(logits.double(), dim=1)
+                back = S.unmap_logits(logits_t.double(), applied)
+                lq = torch.log_softmax(back, dim=1)
+                kl = (lp.exp() * (lp - lq)).sum(1)
+                same = (logits.double().argmax(1) == back.argmax(1)).double()
+                dv = (value.double().reshape(-1) - value_t.double().reshape(-1)).abs()
+                sums += torch.stack([full.sum(), (kl * full).sum(), (same * full).sum(), (dv * full).sum()])
+    finally:
+        model.train(was_training)
+    n, kl, same, dv = sums.cpu().tolist()
+    return {"sym": t, "records": int(n), "kl": _mean(kl, n), "top1_agreement": _mean(same, n), "value_abs_diff": _mean(dv, n)}
+
+
+SYMMETRY_NAMES = {1: "colour flip", 2: "file mirror", 3: "colour flip + file mirror"}
+
+
+def format_consistency(rows: Sequence[Dict]) -> str:
+    fmt = lambda x, f: "-" if x is None else format(x, f)  # noqa: E731
+    lines = [f"{'consistency':<26} {'records':>9} {'kl':>12} {'top1 same':>10} {'|dv|':>10}"]
+    for r in rows:
+        lines.append(f"{SYMMETRY_NAMES[r['sym']]:<26} {r['records']:>9d} {fmt(r['kl'], '.6f'):>12} {fmt(r['top1_agreement'], '.4f'):>10} "
+                     f"{fmt(r['value_abs_diff'], '.6f'):>10}")
+    return "\n".join(lines)
 
 
 # ---- the command ---------------------------------------------------------------------------------------------------------------
@@ -287,6 +360,10 @@ def main(argv=None) -> int:
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--no-amp", action="store_true", help="float32 forward")
     ap.add_argument("--with-q", action="store_true", help="also the value's error against the records' root values")
+    ap.add_argument("--symmetry", choices=("colour", "mirror", "both"), default=None,
+                    help="score the records once more under board symmetries (the colour flip, the file mirror, or each of the two and "
+                         "their product) and print how consistently the net treats a position and its twin; the mirror runs over the "
+                         "records without castling rights")
     ap.add_argument("--out", default=None, help="the report as JSON")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -318,6 +395,24 @@ def main(argv=None) -> int:
         reports[name] = evaluate(net, buf, index, batch=a.batch, amp=not a.no_amp, buckets=a.buckets, with_q=a.with_q, edges=edges)
         log(f"{name}: {path}")
         print(format_table(reports[name]), flush=True)
+        if a.symmetry:
+            from . import symmetry as S
+
+            free = without_castling_rights(games)
+            sym_rep = {"passes": [], "consistency": []}
+            for t in S.CODES[a.symmetry]:
+                part = index[free[index]] if t & S.MIRROR else index
+                if part.size == 0:
+                    log(f"{name}: {SYMMETRY_NAMES[t]}: none of the {index.size} records is without castling rights")
+                    continue
+                rep = evaluate(net, buf, part, batch=a.batch, amp=not a.no_amp, buckets=a.buckets, with_q=a.with_q, edges=edges, sym=t)
+                log(f"{name} under the {SYMMETRY_NAMES[t]}: {part.size} of {index.size} records")
+                print(format_table(rep), flush=True)
+                sym_rep["passes"].append(dict(rep, name=SYMMETRY_NAMES[t], records_scored=int(part.size)))
+                sym_rep["consistency"].append(symmetry_consistency(net, buf, part, t, a.batch, not a.no_amp))
+            if sym_rep["consistency"]:
+                print(format_consistency(sym_rep["consistency"]), flush=True)
+            reports[name]["symmetry"] = sym_rep
     buf.close()
     out = {"records": int(index.size), "games": held_games, "iterations": sorted(files), "holdout_fraction": a.holdout_fraction,
            "seed": a.seed, "buckets": a.buckets, "bucket_edges": edges, "batch": a.batch, "amp": not a.no_amp, "model_path": a.model,

@@ -36,10 +36,11 @@ extern "C" {
  * additions only; 13: a search that waits for its last leaf evaluation is finished without it -- bo_search_close -- addition only;
  * 14: endgame tablebases inside the search and at the root -- bo_engine_tablebases, bo_engine_tb_stats, bo_debug_tree's terminal codes
  * 3 / 4 / 5, bo_root_info's terminal code 3 -- additions only; 15: reanalysis of self-play records -- bo_records_ring,
- * bo_reanalysis_result, status bit BO_ST_PI_OVERFLOW -- additions only; 16: opening books -- bo_book_insert -- addition only).
+ * bo_reanalysis_result, status bit BO_ST_PI_OVERFLOW -- additions only; 16: opening books -- bo_book_insert -- addition only;
+ * 18: board symmetries in the replay samplers -- bo_replay_sample_sym, _sparse_sym, _sparse_q_sym, _merged_sym -- additions only).
  * A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 17
+#define BO_ABI_VERSION 18
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -516,6 +517,24 @@ int bo_replay_merge_groups(const bo_replay_merge *m, int64_t *representative, in
 int bo_replay_sample_merged(bo_replay *rb, bo_replay_merge *m, int32_t n, const int64_t *record_index, float *states_dev,
                             int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev, void *stream);
 void bo_replay_merge_destroy(bo_replay_merge *m);
+
+/* ---- (ABI 18, additions) board symmetries in the samplers: csrc/bo_sym.h ------------------------------------------------------------
+ * The four samplers with one transform code per sample: sym [n] on the HOST, bit 0 = colour flip (colours swapped, ranks mirrored, turn
+ * toggled, castling K<->k Q<->q, en-passant square ^ 56), bit 1 = file mirror (a <-> h, en-passant square ^ 7).  The mirror bit is
+ * dropped for a sample whose CURRENT position has any castling right; applied [n] int32 on the DEVICE (may be NULL) receives the code
+ * that was applied.  All eight history boards of a sample get that code; both move counters are kept.  The pi indices are those of the
+ * transformed moves (utils.move_to_index of the mirrored move); entry order, values, z and q do not change.  Code 0 for every sample
+ * writes, bit for bit, what the call without _sym writes.  Same checks as those calls; a code outside 0..3 is BO_E_ARG and nothing is
+ * launched. */
+int bo_replay_sample_sym(bo_replay *rb, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev, float *pi_dev,
+                         float *z_dev, int32_t *applied_dev, void *stream);
+int bo_replay_sample_sparse_sym(bo_replay *rb, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev,
+                                int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, int32_t *applied_dev, void *stream);
+int bo_replay_sample_sparse_q_sym(bo_replay *rb, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev,
+                                  int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev, int32_t *applied_dev, void *stream);
+int bo_replay_sample_merged_sym(bo_replay *rb, bo_replay_merge *m, int32_t n, const int64_t *record_index, const int32_t *sym,
+                                float *states_dev, int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev, int32_t *applied_dev,
+                                void *stream);
 
 /* ---- (ABI 4) the residual tower of ONE board (a few boards) as ONE launch spread over the chip: csrc/bo_tower_b1.h ----------------
  * Replaces, for uci.py's single-position searches (/root/reference/uci.py:60-93 -> mcts.py:183-185: PolicyValueNet.forward at
