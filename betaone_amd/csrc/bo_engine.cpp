@@ -1228,18 +1228,18 @@ struct bo_replay_s {
     int device = 0, W = 2;
     int64_t cap = 0, head = 0, n_records = 0;
     DPos *pos = nullptr;
-    int *rep = nullptr, *pi_n = nullptr, *pi_idx = nullptr, *s_slot = nullptr, *s_k = nullptr;
+    int *rep = nullptr, *pi_n = nullptr, *pi_idx = nullptr;
     float *pi_val = nullptr, *z = nullptr, *q = nullptr;   // q: the root value beside z (z itself for a record without one)
     int64_t n_valued = 0;                                 // resident records that carry a root value
     uint64_t epoch = 0;                                   // counts the games added: a bo_replay_merge is good for the epoch it was made in
-    int s_cap = 0;
-    int *s_sym = nullptr;                                 // [sym_cap] a batch's symmetry codes (the _sym samplers)
-    int sym_cap = 0;
-    std::vector<int> h_sym;
     struct Game { int64_t start; int32_t n_rec; int32_t game_id; bool valued; };
     std::deque<Game> games;
-    std::vector<int64_t> prefix;   // prefix[i] = records of games[0..i) (rebuilt after an add)
-    std::vector<int> h_slot, h_k;
+    std::vector<int64_t> prefix;   // prefix[i] = records of games[0..i) (rebuilt after an add: replay_prefix)
+    // a batch's staging block: rows of n ints each -- slot, k and, where the sampler has them, sym and group -- filled on the host and
+    // uploaded in one copy
+    std::vector<int> h_stage;
+    int *stage = nullptr;
+    size_t stage_cap = 0;
 };
 
 extern "C" int bo_replay_create(int64_t capacity_positions, int pi_width, int device, bo_replay **out) {
@@ -1266,7 +1266,7 @@ extern "C" int bo_replay_create(int64_t capacity_positions, int pi_width, int de
 
 extern "C" void bo_replay_destroy(bo_replay *r) {
     if (!r) return;
-    rt_free(r->pos); rt_free(r->rep); rt_free(r->pi_n); rt_free(r->pi_idx); rt_free(r->pi_val); rt_free(r->z); rt_free(r->q); rt_free(r->s_slot); rt_free(r->s_k); rt_free(r->s_sym);
+    rt_free(r->pos); rt_free(r->rep); rt_free(r->pi_n); rt_free(r->pi_idx); rt_free(r->pi_val); rt_free(r->z); rt_free(r->q); rt_free(r->stage);
     delete r;
 }
 
@@ -1353,139 +1353,19 @@ extern "C" int bo_replay_values(bo_replay *r, int64_t *n_records_with_value) {
     return BO_OK;
 }
 
-// A batch's ring slots and plies: record_index[i] in [0, records) counts the resident records oldest game first (ChessDataset's index
-// space over load_recent_data's concatenation, train.py:179-219), uploaded to r->s_slot / r->s_k on `stream`.
-static int replay_stage_indices(bo_replay *r, int32_t n, const int64_t *record_index, void *stream, const char *who) {
-    if (r->prefix.empty()) {
-        r->prefix.reserve(r->games.size() + 1);
-        int64_t acc = 0;
-        for (const auto &g : r->games) { r->prefix.push_back(acc); acc += g.n_rec; }
-        r->prefix.push_back(acc);
-    }
-    r->h_slot.resize((size_t)n); r->h_k.resize((size_t)n);
-    for (int i = 0; i < n; i++) {
-        const int64_t q = record_index[i];
-        if (q < 0 || q >= r->n_records) return fail(BO_E_ARG, std::string(who) + ": record index out of range");
-        const size_t g = (size_t)(std::upper_bound(r->prefix.begin(), r->prefix.end(), q) - r->prefix.begin()) - 1;
-        const int k = (int)(q - r->prefix[g]);
-        r->h_slot[(size_t)i] = (int)(r->games[g].start + k);
-        r->h_k[(size_t)i] = k;
-    }
-    if (n > r->s_cap) {
-        RT(rt_sync(stream));  // (the previous batch's index arrays may still be read)
-        rt_free(r->s_slot); rt_free(r->s_k);
-        r->s_slot = r->s_k = nullptr; r->s_cap = 0;
-        RT(rt_malloc((void **)&r->s_slot, (size_t)n * 4));
-        RT(rt_malloc((void **)&r->s_k, (size_t)n * 4));
-        r->s_cap = n;
-    }
-    RT(rt_h2d(r->s_slot, r->h_slot.data(), (size_t)n * 4, stream));
-    RT(rt_h2d(r->s_k, r->h_k.data(), (size_t)n * 4, stream));
-    return BO_OK;
+// record_index q in [0, records) counts the resident records oldest game first (ChessDataset's index space over load_recent_data's
+// concatenation, train.py:179-219): its ring slot and its ply in its game.
+static void replay_prefix(bo_replay *r) {
+    if (!r->prefix.empty()) return;
+    r->prefix.reserve(r->games.size() + 1);
+    int64_t acc = 0;
+    for (const auto &g : r->games) { r->prefix.push_back(acc); acc += g.n_rec; }
+    r->prefix.push_back(acc);
 }
-
-// A batch: states [n,120,8,8], pi [n,4672], z [n] are written on `stream` (no wait).
-extern "C" int bo_replay_sample(bo_replay *r, int32_t n, const int64_t *record_index, float *states_dev, float *pi_dev, float *z_dev, void *stream) {
-    if (!r || n < 1 || !record_index || !states_dev || !pi_dev || !z_dev) return fail(BO_E_ARG, "bo_replay_sample: bad arguments");
-    const int rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample");
-    if (rc) return rc;
-    RT(RT_LAUNCH(bo_k_replay_encode, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
-                 (const float *)r->pi_val, (const float *)r->z, r->W, (const int *)r->s_slot, (const int *)r->s_k, states_dev, pi_dev, z_dev));
-    // the pageable host index arrays are re-used by the next call: wait for their upload (the encode kernel itself is not waited for)
-    RT(rt_sync(stream));
-    return BO_OK;
-}
-
-// The same batch with pi as the records keep it: pi_idx / pi_val [n, W] (W = the buffer's pi_width; unused slots -1 / 0).
-extern "C" int bo_replay_sample_sparse(bo_replay *r, int32_t n, const int64_t *record_index, float *states_dev, int32_t *pi_idx_dev,
-                                       float *pi_val_dev, float *z_dev, void *stream) {
-    if (!r || n < 1 || !record_index || !states_dev || !pi_idx_dev || !pi_val_dev || !z_dev) return fail(BO_E_ARG, "bo_replay_sample_sparse: bad arguments");
-    const int rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_sparse");
-    if (rc) return rc;
-    RT(RT_LAUNCH(bo_k_replay_encode_sparse, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
-                 (const float *)r->pi_val, (const float *)r->z, r->W, (const int *)r->s_slot, (const int *)r->s_k, states_dev, (int *)pi_idx_dev,
-                 pi_val_dev, z_dev));
-    RT(rt_sync(stream));
-    return BO_OK;
-}
-
-// bo_replay_sample_sparse with the records' root values: q [n] beside z [n], from the same launch.
-extern "C" int bo_replay_sample_sparse_q(bo_replay *r, int32_t n, const int64_t *record_index, float *states_dev, int32_t *pi_idx_dev,
-                                         float *pi_val_dev, float *z_dev, float *q_dev, void *stream) {
-    if (!r || n < 1 || !record_index || !states_dev || !pi_idx_dev || !pi_val_dev || !z_dev || !q_dev)
-        return fail(BO_E_ARG, "bo_replay_sample_sparse_q: bad arguments");
-    const int rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_sparse_q");
-    if (rc) return rc;
-    RT(RT_LAUNCH(bo_k_replay_encode_sparse_q, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
-                 (const float *)r->pi_val, (const float *)r->z, (const float *)r->q, r->W, (const int *)r->s_slot, (const int *)r->s_k, states_dev,
-                 (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev));
-    RT(rt_sync(stream));
-    return BO_OK;
-}
-
-// ---- board symmetries in the samplers (bo_sym.h; ABI 18) ------------------------------------------------------------------------------
-// A batch's symmetry codes: checked on the host (0..3, before anything is uploaded or launched) and uploaded to r->s_sym on `stream`.
-static int replay_check_sym(int32_t n, const int32_t *sym, const char *who) {
-    if (!sym) return fail(BO_E_ARG, std::string(who) + ": bad arguments");
-    for (int i = 0; i < n; i++)
-        if (sym[i] < 0 || sym[i] > 3) return fail(BO_E_ARG, std::string(who) + ": symmetry code " + std::to_string(sym[i]) + " of sample " + std::to_string(i) + " is not in 0..3");
-    return BO_OK;
-}
-static int replay_stage_sym(bo_replay *r, int32_t n, const int32_t *sym, void *stream) {
-    r->h_sym.assign(sym, sym + n);
-    if (n > r->sym_cap) {
-        RT(rt_sync(stream));
-        rt_free(r->s_sym);
-        r->s_sym = nullptr; r->sym_cap = 0;
-        RT(rt_malloc((void **)&r->s_sym, (size_t)n * 4));
-        r->sym_cap = n;
-    }
-    RT(rt_h2d(r->s_sym, r->h_sym.data(), (size_t)n * 4, stream));
-    return BO_OK;
-}
-
-extern "C" int bo_replay_sample_sym(bo_replay *r, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev, float *pi_dev,
-                                    float *z_dev, int32_t *applied_dev, void *stream) {
-    if (!r || n < 1 || !record_index || !states_dev || !pi_dev || !z_dev) return fail(BO_E_ARG, "bo_replay_sample_sym: bad arguments");
-    int rc = replay_check_sym(n, sym, "bo_replay_sample_sym");
-    if (!rc) rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_sym");
-    if (!rc) rc = replay_stage_sym(r, n, sym, stream);
-    if (rc) return rc;
-    RT(RT_LAUNCH(bo_k_replay_encode_sym, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
-                 (const float *)r->pi_val, (const float *)r->z, r->W, (const int *)r->s_slot, (const int *)r->s_k, (const int *)r->s_sym,
-                 states_dev, pi_dev, z_dev, (int *)applied_dev));
-    RT(rt_sync(stream));
-    return BO_OK;
-}
-
-extern "C" int bo_replay_sample_sparse_sym(bo_replay *r, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev,
-                                           int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, int32_t *applied_dev, void *stream) {
-    if (!r || n < 1 || !record_index || !states_dev || !pi_idx_dev || !pi_val_dev || !z_dev) return fail(BO_E_ARG, "bo_replay_sample_sparse_sym: bad arguments");
-    int rc = replay_check_sym(n, sym, "bo_replay_sample_sparse_sym");
-    if (!rc) rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_sparse_sym");
-    if (!rc) rc = replay_stage_sym(r, n, sym, stream);
-    if (rc) return rc;
-    RT(RT_LAUNCH(bo_k_replay_encode_sparse_sym, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n, (const int *)r->pi_idx,
-                 (const float *)r->pi_val, (const float *)r->z, r->W, (const int *)r->s_slot, (const int *)r->s_k, (const int *)r->s_sym,
-                 states_dev, (int *)pi_idx_dev, pi_val_dev, z_dev, (int *)applied_dev));
-    RT(rt_sync(stream));
-    return BO_OK;
-}
-
-extern "C" int bo_replay_sample_sparse_q_sym(bo_replay *r, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev,
-                                             int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev, int32_t *applied_dev,
-                                             void *stream) {
-    if (!r || n < 1 || !record_index || !states_dev || !pi_idx_dev || !pi_val_dev || !z_dev || !q_dev)
-        return fail(BO_E_ARG, "bo_replay_sample_sparse_q_sym: bad arguments");
-    int rc = replay_check_sym(n, sym, "bo_replay_sample_sparse_q_sym");
-    if (!rc) rc = replay_stage_indices(r, n, record_index, stream, "bo_replay_sample_sparse_q_sym");
-    if (!rc) rc = replay_stage_sym(r, n, sym, stream);
-    if (rc) return rc;
-    RT(RT_LAUNCH(bo_k_replay_encode_sparse_q_sym, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->pi_n,
-                 (const int *)r->pi_idx, (const float *)r->pi_val, (const float *)r->z, (const float *)r->q, r->W, (const int *)r->s_slot,
-                 (const int *)r->s_k, (const int *)r->s_sym, states_dev, (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev, (int *)applied_dev));
-    RT(rt_sync(stream));
-    return BO_OK;
+static void replay_locate(const bo_replay *r, int64_t q, int *slot, int *k) {
+    const size_t g = (size_t)(std::upper_bound(r->prefix.begin(), r->prefix.end(), q) - r->prefix.begin()) - 1;
+    *k = (int)(q - r->prefix[g]);
+    *slot = (int)(r->games[g].start + *k);
 }
 
 // ---- merged targets (bo_merge.h; ABI 17) ---------------------------------------------------------------------------------------------
@@ -1501,15 +1381,13 @@ struct bo_replay_merge_s {
     std::vector<int64_t> rep_of;     // [n] work-list order: the representative of the item's group
     std::vector<int64_t> reps;       // [G] ascending
     std::vector<int32_t> count;      // [G]
-    int *m_idx = nullptr, *s_grp = nullptr;
+    int *m_idx = nullptr;
     float *m_val = nullptr, *m_z = nullptr, *m_q = nullptr;
-    int s_cap = 0;
-    std::vector<int> h_grp;
 };
 
 extern "C" void bo_replay_merge_destroy(bo_replay_merge *m) {
     if (!m) return;
-    rt_free(m->m_idx); rt_free(m->m_val); rt_free(m->m_z); rt_free(m->m_q); rt_free(m->s_grp);
+    rt_free(m->m_idx); rt_free(m->m_val); rt_free(m->m_z); rt_free(m->m_q);
     delete m;
 }
 
@@ -1550,11 +1428,7 @@ extern "C" int bo_replay_merge_create_ex(bo_replay *r, int64_t n, const int64_t 
     if (n > ((int64_t)1 << 29)) return fail(BO_E_ARG, who + ": more than 2^29 records");
     if (T == 0) for (T = 64; T < 2 * n; T <<= 1) {}
     if (T < 1 || T > ((int64_t)1 << 30) || (T & (T - 1)) != 0) return fail(BO_E_ARG, who + ": table_slots must be 0 or a power of two, 1 .. 2^30");
-    if (r->prefix.empty()) {
-        int64_t acc = 0;
-        for (const auto &g : r->games) { r->prefix.push_back(acc); acc += g.n_rec; }
-        r->prefix.push_back(acc);
-    }
+    replay_prefix(r);
     std::unique_ptr<bo_replay_merge, void (*)(bo_replay_merge *)> m(new bo_replay_merge(), bo_replay_merge_destroy);
     m->r = r; m->epoch = r->epoch; m->key = key; m->n = n; m->T = T;
     m->group_of.assign((size_t)r->n_records, -1);
@@ -1564,9 +1438,7 @@ extern "C" int bo_replay_merge_create_ex(bo_replay *r, int64_t n, const int64_t 
         if (q < 0 || q >= r->n_records) return fail(BO_E_ARG, who + ": record index out of range");
         if (m->group_of[(size_t)q] != -1) return fail(BO_E_ARG, who + ": record " + std::to_string(q) + " is listed twice");
         m->group_of[(size_t)q] = -2;
-        const size_t g = (size_t)(std::upper_bound(r->prefix.begin(), r->prefix.end(), q) - r->prefix.begin()) - 1;
-        h_k[(size_t)i] = (int)(q - r->prefix[g]);
-        h_slot[(size_t)i] = (int)(r->games[g].start + h_k[(size_t)i]);
+        replay_locate(r, q, &h_slot[(size_t)i], &h_k[(size_t)i]);
         h_rec[(size_t)i] = (int)q;
     }
     RT(rt_set_device(r->device));
@@ -1694,61 +1566,119 @@ extern "C" int bo_replay_merge_groups(const bo_replay_merge *m, int64_t *represe
     return BO_OK;
 }
 
-// bo_replay_sample_sparse_q's batch with the targets of the records' groups: pi_idx / pi_val [n, Wm], z [n], q [n].
-// sym (NULL: none): the batch under a board symmetry per sample (bo_replay_sample_merged_sym).
-static int replay_sample_merged(const char *who_c, bo_replay *r, bo_replay_merge *m, int32_t n, const int64_t *record_index, const int32_t *sym,
-                                bool with_sym, float *states_dev, int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev,
-                                int32_t *applied_dev, void *stream) {
+// ---- the samplers (bo_replay.h, bo_merge.h; board symmetries: bo_sym.h, ABI 18) -------------------------------------------------------
+// A batch of n records, written on `stream` (the kernel is not waited for): states [n,120,8,8] and z [n] always;
+//   dense                  pi [n,4672]
+//   sparse, sparse_q       pi as the records keep it: pi_idx / pi_val [n, W] (W = the buffer's pi_width; unused places -1 / 0); sparse_q
+//                          also the records' root values q [n], from the same launch
+//   merged                 sparse_q's batch with the targets of the records' groups: pi_idx / pi_val [n, Wm], z and q the groups' means
+// with_sym: sample i under the board symmetry sym[i] (0..3); applied (may be NULL) [n] = the code that was applied.
+// A refused call has written nothing and launched nothing: everything is checked on the host first.
+enum { REPLAY_DENSE, REPLAY_SPARSE, REPLAY_SPARSE_Q, REPLAY_MERGED };
+
+static int replay_sample(const char *who_c, int kind, bool with_sym, bo_replay *r, bo_replay_merge *m, int32_t n, const int64_t *record_index,
+                         const int32_t *sym, ReplayArgs a, void *stream) {
+    static void (*const kernels[4][2])(ReplayArgs) = {{bo_k_replay_encode, bo_k_replay_encode_sym},
+                                                      {bo_k_replay_encode_sparse, bo_k_replay_encode_sparse_sym},
+                                                      {bo_k_replay_encode_sparse_q, bo_k_replay_encode_sparse_q_sym},
+                                                      {bo_k_replay_encode_merged, bo_k_replay_encode_merged_sym}};
     const std::string who(who_c);
-    if (!r || !m || n < 1 || !record_index || !states_dev || !pi_idx_dev || !pi_val_dev || !z_dev || !q_dev)
+    const bool merged = kind == REPLAY_MERGED;
+    if (!r || (merged && !m) || n < 1 || !record_index || !a.states || !a.zs || (kind == REPLAY_DENSE ? !a.pis : !a.out_idx || !a.out_val) ||
+        (kind >= REPLAY_SPARSE_Q && !a.qs) || (with_sym && !sym))
         return fail(BO_E_ARG, who + ": bad arguments");
-    if (with_sym) {
-        const int rcs = replay_check_sym(n, sym, who_c);
-        if (rcs) return rcs;
-    }
-    if (m->r != r) return fail(BO_E_ARG, who + ": the merge was made from another buffer");
-    if (m->epoch != r->epoch) return fail(BO_E_ARG, who + ": stale merge: games were added to the buffer after it was made");
-    m->h_grp.resize((size_t)n);
+    for (int i = 0; with_sym && i < n; i++)
+        if (sym[i] < 0 || sym[i] > 3) return fail(BO_E_ARG, who + ": symmetry code " + std::to_string(sym[i]) + " of sample " + std::to_string(i) + " is not in 0..3");
+    if (merged && m->r != r) return fail(BO_E_ARG, who + ": the merge was made from another buffer");
+    if (merged && m->epoch != r->epoch) return fail(BO_E_ARG, who + ": stale merge: games were added to the buffer after it was made");
+    // locate: the staging rows slot, k, then sym and group where the sampler has them
+    replay_prefix(r);
+    const size_t N = (size_t)n, rows = 2 + (with_sym ? 1 : 0) + (merged ? 1 : 0);
+    r->h_stage.resize(rows * N);
+    int *h_slot = r->h_stage.data(), *h_k = h_slot + N, *h_sym = h_k + N, *h_grp = h_k + (rows - 2) * N;
     for (int i = 0; i < n; i++) {
         const int64_t q = record_index[i];
         if (q < 0 || q >= r->n_records) return fail(BO_E_ARG, who + ": record index out of range");
+        replay_locate(r, q, &h_slot[i], &h_k[i]);
+        if (with_sym) h_sym[i] = sym[i];
+        if (!merged) continue;
         if (m->group_of[(size_t)q] < 0) return fail(BO_E_ARG, who + ": record " + std::to_string(q) + " is not covered by the merge");
-        m->h_grp[(size_t)i] = m->group_of[(size_t)q];
+        h_grp[i] = m->group_of[(size_t)q];
     }
-    int rc = replay_stage_indices(r, n, record_index, stream, who_c);
-    if (!rc && with_sym) rc = replay_stage_sym(r, n, sym, stream);
-    if (rc) return rc;
-    if (n > m->s_cap) {
-        RT(rt_sync(stream));
-        rt_free(m->s_grp);
-        m->s_grp = nullptr; m->s_cap = 0;
-        RT(rt_malloc((void **)&m->s_grp, (size_t)n * 4));
-        m->s_cap = n;
+    // stage: one upload
+    if (r->h_stage.size() > r->stage_cap) {
+        RT(rt_sync(stream));  // (the previous batch's rows may still be read)
+        rt_free(r->stage);
+        r->stage = nullptr; r->stage_cap = 0;
+        RT(rt_malloc((void **)&r->stage, r->h_stage.size() * 4));
+        r->stage_cap = r->h_stage.size();
     }
-    RT(rt_h2d(m->s_grp, m->h_grp.data(), (size_t)n * 4, stream));
-    if (with_sym)
-        RT(RT_LAUNCH(bo_k_replay_encode_merged_sym, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->s_slot,
-                     (const int *)r->s_k, (const int *)m->s_grp, m->Wm, (const int *)m->m_idx, (const float *)m->m_val, (const float *)m->m_z,
-                     (const float *)m->m_q, (const int *)r->s_sym, states_dev, (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev, (int *)applied_dev));
-    else
-        RT(RT_LAUNCH(bo_k_replay_encode_merged, n, stream, (const DPos *)r->pos, (const int *)r->rep, (const int *)r->s_slot, (const int *)r->s_k,
-                     (const int *)m->s_grp, m->Wm, (const int *)m->m_idx, (const float *)m->m_val, (const float *)m->m_z, (const float *)m->m_q,
-                     states_dev, (int *)pi_idx_dev, pi_val_dev, z_dev, q_dev));
+    RT(rt_h2d(r->stage, r->h_stage.data(), r->h_stage.size() * 4, stream));
+    a.pos = r->pos; a.rep = r->rep;
+    a.s_slot = r->stage; a.s_k = r->stage + N;
+    a.s_sym = with_sym ? r->stage + 2 * N : nullptr;
+    a.s_grp = merged ? r->stage + (rows - 1) * N : nullptr;
+    if (merged) { a.pi_n = nullptr; a.pi_idx = m->m_idx; a.pi_val = m->m_val; a.z = m->m_z; a.q = m->m_q; a.W = m->Wm; }
+    else { a.pi_n = r->pi_n; a.pi_idx = r->pi_idx; a.pi_val = r->pi_val; a.z = r->z; a.q = r->q; a.W = r->W; }
+    RT(RT_LAUNCH(kernels[kind][with_sym ? 1 : 0], n, stream, a));
+    // the pageable host staging is re-used by the next call: wait for its upload (the encode kernel itself is not waited for)
     RT(rt_sync(stream));
     return BO_OK;
 }
 
+static ReplayArgs replay_out(float *states, float *pis, int32_t *out_idx, float *out_val, float *zs, float *qs, int32_t *applied) {
+    ReplayArgs a = {};
+    a.states = states; a.pis = pis; a.out_idx = (int *)out_idx; a.out_val = out_val; a.zs = zs; a.qs = qs; a.applied = (int *)applied;
+    return a;
+}
+
+extern "C" int bo_replay_sample(bo_replay *r, int32_t n, const int64_t *record_index, float *states_dev, float *pi_dev, float *z_dev, void *stream) {
+    return replay_sample("bo_replay_sample", REPLAY_DENSE, false, r, nullptr, n, record_index, nullptr,
+                         replay_out(states_dev, pi_dev, nullptr, nullptr, z_dev, nullptr, nullptr), stream);
+}
+
+extern "C" int bo_replay_sample_sparse(bo_replay *r, int32_t n, const int64_t *record_index, float *states_dev, int32_t *pi_idx_dev,
+                                       float *pi_val_dev, float *z_dev, void *stream) {
+    return replay_sample("bo_replay_sample_sparse", REPLAY_SPARSE, false, r, nullptr, n, record_index, nullptr,
+                         replay_out(states_dev, nullptr, pi_idx_dev, pi_val_dev, z_dev, nullptr, nullptr), stream);
+}
+
+extern "C" int bo_replay_sample_sparse_q(bo_replay *r, int32_t n, const int64_t *record_index, float *states_dev, int32_t *pi_idx_dev,
+                                         float *pi_val_dev, float *z_dev, float *q_dev, void *stream) {
+    return replay_sample("bo_replay_sample_sparse_q", REPLAY_SPARSE_Q, false, r, nullptr, n, record_index, nullptr,
+                         replay_out(states_dev, nullptr, pi_idx_dev, pi_val_dev, z_dev, q_dev, nullptr), stream);
+}
+
 extern "C" int bo_replay_sample_merged(bo_replay *r, bo_replay_merge *m, int32_t n, const int64_t *record_index, float *states_dev,
                                        int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev, void *stream) {
-    return replay_sample_merged("bo_replay_sample_merged", r, m, n, record_index, nullptr, false, states_dev, pi_idx_dev, pi_val_dev, z_dev, q_dev,
-                                nullptr, stream);
+    return replay_sample("bo_replay_sample_merged", REPLAY_MERGED, false, r, m, n, record_index, nullptr,
+                         replay_out(states_dev, nullptr, pi_idx_dev, pi_val_dev, z_dev, q_dev, nullptr), stream);
+}
+
+extern "C" int bo_replay_sample_sym(bo_replay *r, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev, float *pi_dev,
+                                    float *z_dev, int32_t *applied_dev, void *stream) {
+    return replay_sample("bo_replay_sample_sym", REPLAY_DENSE, true, r, nullptr, n, record_index, sym,
+                         replay_out(states_dev, pi_dev, nullptr, nullptr, z_dev, nullptr, applied_dev), stream);
+}
+
+extern "C" int bo_replay_sample_sparse_sym(bo_replay *r, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev,
+                                           int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, int32_t *applied_dev, void *stream) {
+    return replay_sample("bo_replay_sample_sparse_sym", REPLAY_SPARSE, true, r, nullptr, n, record_index, sym,
+                         replay_out(states_dev, nullptr, pi_idx_dev, pi_val_dev, z_dev, nullptr, applied_dev), stream);
+}
+
+extern "C" int bo_replay_sample_sparse_q_sym(bo_replay *r, int32_t n, const int64_t *record_index, const int32_t *sym, float *states_dev,
+                                             int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev, int32_t *applied_dev,
+                                             void *stream) {
+    return replay_sample("bo_replay_sample_sparse_q_sym", REPLAY_SPARSE_Q, true, r, nullptr, n, record_index, sym,
+                         replay_out(states_dev, nullptr, pi_idx_dev, pi_val_dev, z_dev, q_dev, applied_dev), stream);
 }
 
 extern "C" int bo_replay_sample_merged_sym(bo_replay *r, bo_replay_merge *m, int32_t n, const int64_t *record_index, const int32_t *sym,
                                            float *states_dev, int32_t *pi_idx_dev, float *pi_val_dev, float *z_dev, float *q_dev,
                                            int32_t *applied_dev, void *stream) {
-    return replay_sample_merged("bo_replay_sample_merged_sym", r, m, n, record_index, sym, true, states_dev, pi_idx_dev, pi_val_dev, z_dev, q_dev,
-                                applied_dev, stream);
+    return replay_sample("bo_replay_sample_merged_sym", REPLAY_MERGED, true, r, m, n, record_index, sym,
+                         replay_out(states_dev, nullptr, pi_idx_dev, pi_val_dev, z_dev, q_dev, applied_dev), stream);
 }
 
 // ---- PGN pretraining (bo_pgn.h) --------------------------------------------------------------------------------------------------

@@ -12,10 +12,10 @@
 //   bo_k_replay_merge          one wave per group, members in ascending record index (the host's stable sort): the union of the
 //                              members' actions in ascending order, per action the float64 sum of the members' values in member order,
 //                              divided by the count and rounded once to float32; z and q the same.  A group of one is a copy.
-//   bo_k_replay_encode_merged  the per-step sampler: the planes of the sampled record itself (replay_planes, shared with the other
-//                              samplers), the targets of its group, one launch.  _sym: the same body under a board symmetry per sample.
+//   bo_k_replay_encode_merged  the per-step sampler: the planes of the sampled record itself, the targets of its group, one launch --
+//                              bo_replay.h's replay_encode with the group's row as the target row.  _sym: under a board symmetry.
 //
-// Key `input`: two records are equal iff replay_planes writes the same 120 planes for them -- compared block by block on what
+// Key `input`: two records are equal iff replay_planes_rep writes the same 120 planes for them -- compared block by block on what
 // encode_block and encode_scalars show: per history block the twelve piece-and-colour boards and min(rep, 2) (a block in front of the
 // game's first ply is all zero), and of the current board the turn and castling bits, both counters and the en-passant square.
 // Key `position`: key_equal of the current board alone.
@@ -27,7 +27,7 @@
 // by the atomic min (relaxed, agent scope; bo_perft.h's wrappers); gid[i] is the item's own word.
 #pragma once
 #include "bo_perft.h"   // the atomic wrappers
-#include "bo_replay.h"  // replay_planes
+#include "bo_replay.h"  // ReplayArgs, replay_encode
 
 #define MERGE_KEY_INPUT 0
 #define MERGE_KEY_POSITION 1
@@ -247,31 +247,8 @@ BO_KERNEL void bo_k_replay_merge(MergeArgs a) {
     if (lane == 0) { a.out_z[g] = (float)(zs / dn); a.out_q[g] = (float)(qs / dn); }
 }
 
-// sample b = the record in ring slot s_slot[b], ply s_k[b], with the targets of group s_grp[b].  SYM: under the board symmetry
-// s_sym[b] (bo_sym.h) -- the group's mean targets are transformed on the way out; the grouping knows nothing of it.
-template <bool SYM>
-BO_DEV void replay_encode_merged(const DPos *pos, const int *rep, const int *s_slot, const int *s_k, const int *s_grp, int Wm,
-                                 const int *m_idx, const float *m_val, const float *m_z, const float *m_q, const int *s_sym, float *states,
-                                 int *out_idx, float *out_val, float *zs, float *qs, int *applied) {
-    const int b = bo_block(), s = bo_lane();
-    int t = 0;
-    if constexpr (SYM) t = replay_planes_sym(states, b, pos, rep, s_slot[b], s_k[b], s_sym, applied);
-    else replay_planes(states, b, pos, rep, s_slot[b], s_k[b]);
-    const int g = s_grp[b];
-    for (int e = s; e < Wm; e += 64) {
-        const int a = m_idx[(size_t)g * Wm + e];
-        out_idx[(size_t)b * Wm + e] = SYM ? sym_action(a, t) : a;
-        out_val[(size_t)b * Wm + e] = m_val[(size_t)g * Wm + e];
-    }
-    if (s == 0) { zs[b] = m_z[g]; qs[b] = m_q[g]; }
-}
-BO_KERNEL void bo_k_replay_encode_merged(const DPos *pos, const int *rep, const int *s_slot, const int *s_k, const int *s_grp, int Wm,
-                                         const int *m_idx, const float *m_val, const float *m_z, const float *m_q, float *states,
-                                         int *out_idx, float *out_val, float *zs, float *qs) {
-    replay_encode_merged<false>(pos, rep, s_slot, s_k, s_grp, Wm, m_idx, m_val, m_z, m_q, nullptr, states, out_idx, out_val, zs, qs, nullptr);
-}
-BO_KERNEL void bo_k_replay_encode_merged_sym(const DPos *pos, const int *rep, const int *s_slot, const int *s_k, const int *s_grp, int Wm,
-                                             const int *m_idx, const float *m_val, const float *m_z, const float *m_q, const int *s_sym,
-                                             float *states, int *out_idx, float *out_val, float *zs, float *qs, int *applied) {
-    replay_encode_merged<true>(pos, rep, s_slot, s_k, s_grp, Wm, m_idx, m_val, m_z, m_q, s_sym, states, out_idx, out_val, zs, qs, applied);
-}
+// The per-step sampler is bo_replay.h's body with the target rows of a merge: s_grp[b] = the group of sample b, the columns m_idx / m_val
+// [G, Wm], m_z / m_q [G], rows padded already.  SYM: the group's mean targets are transformed on the way out; the grouping knows
+// nothing of it.
+BO_KERNEL void bo_k_replay_encode_merged(ReplayArgs a) { replay_encode<false, true, false>(a); }
+BO_KERNEL void bo_k_replay_encode_merged_sym(ReplayArgs a) { replay_encode<false, true, true>(a); }

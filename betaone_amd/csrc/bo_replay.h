@@ -9,18 +9,22 @@
 // 288), and a batch is made where it is consumed -- one wave per sampled ply writes the 120 planes, the dense pi row and z.
 //   bo_k_replay_counts   once per added game: repetition count of every position of the game (a position's count is the number of
 //                        key-equal positions in the WHOLE game minus one: what bo_k_encode_positions recomputes per encoded ply)
-//   bo_k_replay_encode   one wave per sample: 8 history blocks from the ply's own game (positions are stored game-contiguous),
-//                        scalar planes, dense pi row (zero fill + scatter), z
-//   bo_k_replay_encode_sparse  the same planes and z, pi as the record keeps it ([W] indices and values): for the sparse-target
-//                        loss of bo_train.h, which never needs the dense row
-//   bo_k_replay_encode_sparse_q  the same launch with the record's root value q beside z (bo_train.h: the value target as a mix of the
-//                        two).  A slot keeps one float32 q next to its z: the search's root value at that ply from the side to
-//                        move's point of view, like z -- or z itself where the game was recorded without root values.
-//   bo_k_replay_encode_sym / _sparse_sym / _sparse_q_sym  the same three bodies with SYM = true: sample b is handed out under the board
-//                        symmetry s_sym[b] (bo_sym.h): every DPos is transformed in registers before encode_block / encode_scalars
-//                        write it, the pi indices go through sym_action; entry order, values, z and q are untouched.  applied[b]
-//                        (may be NULL) = the code that was applied: the mirror bit is dropped while the record's current position
-//                        has a castling right.  The kernels above are the instantiation with SYM = false.
+//   bo_k_replay_encode*  one wave per sample, eight one-line instantiations of ONE body, replay_encode<DENSE, WITH_Q, SYM>, over ONE
+//                        argument struct, ReplayArgs: the 120 planes (8 history blocks from the ply's own game -- positions are stored
+//                        game-contiguous -- and the scalar planes, replay_planes_rep), one target row, z.  The next sampler feature is
+//                        a flag of the body, not another copy of it.
+//     bo_k_replay_encode           DENSE: the pi row of 4672, every address written once (replay_row_dense)
+//     bo_k_replay_encode_sparse    pi as the record keeps it ([W] indices and values, replay_row_sparse): for the sparse-target loss
+//                                  of bo_train.h, which never needs the dense row
+//     bo_k_replay_encode_sparse_q  WITH_Q: the record's root value q beside z (bo_train.h: the value target as a mix of the two).  A
+//                                  slot keeps one float32 q next to its z: the search's root value at that ply from the side to
+//                                  move's point of view, like z -- or z itself where the game was recorded without root values.
+//     bo_k_replay_encode_merged    (bo_merge.h) the sparse row and z, q read from the sample's merge group instead of its ring slot
+//     ..._sym                      SYM: sample b is handed out under the board symmetry s_sym[b] (bo_sym.h): every DPos is
+//                                  transformed in registers before encode_block / encode_scalars write it, the pi indices go through
+//                                  sym_action; entry order, values, z and q are untouched.  applied[b] (may be NULL) = the code that
+//                                  was applied: the mirror bit is dropped while the record's current position has a castling right.
+//                        DENSE, WITH_Q and SYM are compile-time: an instance without SYM carries nothing of sym_pos.
 #pragma once
 #include "bo_sym.h"
 #include "bo_tree.h"
@@ -35,7 +39,7 @@ BO_KERNEL void bo_k_replay_counts(const DPos *pos, int n_pos, int *rep) {
 }
 
 // the 120 planes of sample b: the record in ring slot `slot`, the k-th ply of its game (so slots slot - min(7, k) .. slot are its
-// history).  Shared by both samplers, so their states cannot drift apart.
+// history).  Shared by replay_encode and the PGN sampler, so their states cannot drift apart.
 // rep_of(h) = the repetition count of the board in slot h (the PGN sampler of bo_pgn.h counts it live).
 // SYM: every board under the symmetry t (wave-uniform; the code sym_applied gave for the sample).
 template <bool SYM = false, class RepOf> BO_DEV void replay_planes_rep(float *states, int b, const DPos *pos, int slot, int k, RepOf rep_of, int t = 0) {
@@ -51,104 +55,88 @@ template <bool SYM = false, class RepOf> BO_DEV void replay_planes_rep(float *st
         encode_scalars(row, pos[slot]);
     }
 }
-BO_DEV void replay_planes(float *states, int b, const DPos *pos, const int *rep, int slot, int k) {
-    replay_planes_rep(states, b, pos, slot, k, [rep](int h) { return rep[h]; });
-}
-// the planes of sample b under s_sym[b]; returns the applied code (and stores it where the caller asked for it)
-BO_DEV int replay_planes_sym(float *states, int b, const DPos *pos, const int *rep, int slot, int k, const int *s_sym, int *applied) {
-    const int t = sym_applied(pos[slot].flags, s_sym[b]);
-    replay_planes_rep<true>(states, b, pos, slot, k, [rep](int h) { return rep[h]; }, t);
-    if (applied && bo_lane() == 0) applied[b] = t;
-    return t;
-}
 
-// sample i = the record in ring slot s_slot[i], the s_k[i]-th ply of its game
-template <bool SYM>
-BO_DEV void replay_encode_dense(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val, const float *z,
-                                int W, const int *s_slot, const int *s_k, const int *s_sym, float *states, float *pis, float *zs,
-                                int *applied) {
-    const int b = bo_block(), s = bo_lane();
-    const int slot = s_slot[b];
-    int t = 0;
-    if constexpr (SYM) t = replay_planes_sym(states, b, pos, rep, slot, s_k[b], s_sym, applied);
-    else replay_planes(states, b, pos, rep, slot, s_k[b]);
-    // dense pi row: every address has ONE writer (lane = action mod 64), which looks its action up among the ply's few entries
-    float *pr = pis + (size_t)b * BO_NUM_ACTIONS;
-    const int n = pi_n[slot];
-    const int *ix = pi_idx + (size_t)slot * W;
-    const float *vx = pi_val + (size_t)slot * W;
+// One sampler launch, by value (as MergeArgs of bo_merge.h): sample b = the record in ring slot s_slot[b], the s_k[b]-th ply of its game.
+struct ReplayArgs {
+    const DPos *pos;                   // the ring and its repetition counts
+    const int *rep;
+    const int *s_slot, *s_k;           // [n] the staged batch: ring slot and ply of every sample
+    const int *s_sym;                  // [n] SYM: the symmetry asked for (bo_sym.h)
+    const int *s_grp;                  // [n] the target row of sample b; NULL (and always for the dense row): that of its own ring slot
+    // the targets, W entries per row: the buffer's columns by ring slot, or a merge's by group (bo_merge.h: m_idx, m_val, m_z, m_q, Wm)
+    const int *pi_n;                   // entries in use per row; NULL: rows are padded with (-1, 0) already (a merge's)
+    const int *pi_idx;
+    const float *pi_val, *z, *q;
+    int W;
+    float *states;                     // [n, 120, 8, 8]
+    float *pis;                        // dense: [n, 4672]
+    int *out_idx;                      // sparse: [n, W] the row's entries first, then (-1, 0) in the unused places
+    float *out_val;
+    float *zs, *qs;                    // [n]; qs with WITH_Q
+    int *applied;                      // [n] SYM: the code that was applied (may be NULL)
+};
+
+// dense pi row: every address has ONE writer (lane = action mod 64), which looks its action up among the row's few entries
+template <bool SYM> BO_DEV void replay_row_dense(const ReplayArgs &a, int b, int row, int t) {
+    const int s = bo_lane();
+    float *pr = a.pis + (size_t)b * BO_NUM_ACTIONS;
+    const int n = a.pi_n[row];
+    const int *ix = a.pi_idx + (size_t)row * a.W;
+    const float *vx = a.pi_val + (size_t)row * a.W;
     if constexpr (SYM) {
         // the entries' indices are mapped ONCE, entry e by lane e & 63 (n <= W <= BO_RES_CAP), and read back lane by lane in the loop
         int m[BO_RES_CAP / 64];
 #pragma unroll
         for (int r = 0; r < BO_RES_CAP / 64; r++) m[r] = s + 64 * r < n ? sym_action(ix[s + 64 * r], t) : -1;
-        for (int a = s; a < BO_NUM_ACTIONS; a += 64) {
+        for (int c = s; c < BO_NUM_ACTIONS; c += 64) {
             float v = 0.0f;
             for (int e = 0; e < n; e++) {
                 const int r = e >> 6;  // (wave-uniform)
-                v = bo_readlane(r == 0 ? m[0] : r == 1 ? m[1] : r == 2 ? m[2] : m[3], e & 63) == a ? vx[e] : v;
+                v = bo_readlane(r == 0 ? m[0] : r == 1 ? m[1] : r == 2 ? m[2] : m[3], e & 63) == c ? vx[e] : v;
             }
-            pr[a] = v;
+            pr[c] = v;
         }
     } else {
-        for (int a = s; a < BO_NUM_ACTIONS; a += 64) {
+        for (int c = s; c < BO_NUM_ACTIONS; c += 64) {
             float v = 0.0f;
-            for (int e = 0; e < n; e++) v = ix[e] == a ? vx[e] : v;
-            pr[a] = v;
+            for (int e = 0; e < n; e++) v = ix[e] == c ? vx[e] : v;
+            pr[c] = v;
         }
     }
-    if (s == 0) zs[b] = z[slot];
-}
-BO_KERNEL void bo_k_replay_encode(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val, const float *z,
-                                  int W, const int *s_slot, const int *s_k, float *states, float *pis, float *zs) {
-    replay_encode_dense<false>(pos, rep, pi_n, pi_idx, pi_val, z, W, s_slot, s_k, nullptr, states, pis, zs, nullptr);
-}
-BO_KERNEL void bo_k_replay_encode_sym(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val,
-                                      const float *z, int W, const int *s_slot, const int *s_k, const int *s_sym, float *states, float *pis,
-                                      float *zs, int *applied) {
-    replay_encode_dense<true>(pos, rep, pi_n, pi_idx, pi_val, z, W, s_slot, s_k, s_sym, states, pis, zs, applied);
 }
 
-// the same sample with its pi as stored: out_idx / out_val [n, W], the record's entries first, then (-1, 0) in the unused slots
-template <bool WITH_Q, bool SYM = false>
-BO_DEV void replay_encode_sparse(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val, const float *z,
-                                 const float *q, int W, const int *s_slot, const int *s_k, float *states, int *out_idx, float *out_val,
-                                 float *zs, float *qs, const int *s_sym = nullptr, int *applied = nullptr) {
-    const int b = bo_block(), s = bo_lane();
-    const int slot = s_slot[b];
-    int t = 0;
-    if constexpr (SYM) t = replay_planes_sym(states, b, pos, rep, slot, s_k[b], s_sym, applied);
-    else replay_planes(states, b, pos, rep, slot, s_k[b]);
-    const int n = pi_n[slot];
-    for (int e = s; e < W; e += 64) {
+// the row as it is kept: a record's entries in the record's order, or a merge group's union
+template <bool SYM> BO_DEV void replay_row_sparse(const ReplayArgs &a, int b, int row, int t) {
+    const int n = a.pi_n ? a.pi_n[row] : a.W;
+    for (int e = bo_lane(); e < a.W; e += 64) {
         const bool used = e < n;
-        const int a = used ? pi_idx[(size_t)slot * W + e] : -1;
-        out_idx[(size_t)b * W + e] = SYM ? sym_action(a, t) : a;
-        out_val[(size_t)b * W + e] = used ? pi_val[(size_t)slot * W + e] : 0.0f;
-    }
-    if (s == 0) {
-        zs[b] = z[slot];
-        if (WITH_Q) qs[b] = q[slot];
+        const int c = used ? a.pi_idx[(size_t)row * a.W + e] : -1;
+        a.out_idx[(size_t)b * a.W + e] = SYM ? sym_action(c, t) : c;
+        a.out_val[(size_t)b * a.W + e] = used ? a.pi_val[(size_t)row * a.W + e] : 0.0f;
     }
 }
-BO_KERNEL void bo_k_replay_encode_sparse(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val,
-                                         const float *z, int W, const int *s_slot, const int *s_k, float *states, int *out_idx,
-                                         float *out_val, float *zs) {
-    replay_encode_sparse<false>(pos, rep, pi_n, pi_idx, pi_val, z, nullptr, W, s_slot, s_k, states, out_idx, out_val, zs, nullptr);
+
+// SYM: sample b is handed out under the symmetry sym_applied gives for s_sym[b]: the boards are transformed in registers, the pi
+// indices go through sym_action; entry order, values, z and q are untouched.
+template <bool DENSE, bool WITH_Q, bool SYM> BO_DEV void replay_encode(const ReplayArgs &a) {
+    const int b = bo_block();
+    const int slot = a.s_slot[b];
+    const int row = !DENSE && a.s_grp ? a.s_grp[b] : slot;  // (read in front of the planes: nothing waits for it behind them)
+    int t = 0;
+    if constexpr (SYM) t = sym_applied(a.pos[slot].flags, a.s_sym[b]);
+    const int *rep = a.rep;
+    replay_planes_rep<SYM>(a.states, b, a.pos, slot, a.s_k[b], [rep](int h) { return rep[h]; }, t);
+    if (SYM && a.applied && bo_lane() == 0) a.applied[b] = t;
+    if constexpr (DENSE) replay_row_dense<SYM>(a, b, row, t);
+    else replay_row_sparse<SYM>(a, b, row, t);
+    if (bo_lane() == 0) {
+        a.zs[b] = a.z[row];
+        if (WITH_Q) a.qs[b] = a.q[row];
+    }
 }
-BO_KERNEL void bo_k_replay_encode_sparse_q(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val,
-                                           const float *z, const float *q, int W, const int *s_slot, const int *s_k, float *states,
-                                           int *out_idx, float *out_val, float *zs, float *qs) {
-    replay_encode_sparse<true>(pos, rep, pi_n, pi_idx, pi_val, z, q, W, s_slot, s_k, states, out_idx, out_val, zs, qs);
-}
-BO_KERNEL void bo_k_replay_encode_sparse_sym(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val,
-                                             const float *z, int W, const int *s_slot, const int *s_k, const int *s_sym, float *states,
-                                             int *out_idx, float *out_val, float *zs, int *applied) {
-    replay_encode_sparse<false, true>(pos, rep, pi_n, pi_idx, pi_val, z, nullptr, W, s_slot, s_k, states, out_idx, out_val, zs, nullptr, s_sym,
-                                      applied);
-}
-BO_KERNEL void bo_k_replay_encode_sparse_q_sym(const DPos *pos, const int *rep, const int *pi_n, const int *pi_idx, const float *pi_val,
-                                               const float *z, const float *q, int W, const int *s_slot, const int *s_k, const int *s_sym,
-                                               float *states, int *out_idx, float *out_val, float *zs, float *qs, int *applied) {
-    replay_encode_sparse<true, true>(pos, rep, pi_n, pi_idx, pi_val, z, q, W, s_slot, s_k, states, out_idx, out_val, zs, qs, s_sym, applied);
-}
+BO_KERNEL void bo_k_replay_encode(ReplayArgs a) { replay_encode<true, false, false>(a); }
+BO_KERNEL void bo_k_replay_encode_sym(ReplayArgs a) { replay_encode<true, false, true>(a); }
+BO_KERNEL void bo_k_replay_encode_sparse(ReplayArgs a) { replay_encode<false, false, false>(a); }
+BO_KERNEL void bo_k_replay_encode_sparse_q(ReplayArgs a) { replay_encode<false, true, false>(a); }
+BO_KERNEL void bo_k_replay_encode_sparse_sym(ReplayArgs a) { replay_encode<false, false, true>(a); }
+BO_KERNEL void bo_k_replay_encode_sparse_q_sym(ReplayArgs a) { replay_encode<false, true, true>(a); }

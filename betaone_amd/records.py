@@ -352,74 +352,52 @@ class GpuReplayBuffer:
         self.n_evicted += lost
         return lost
 
-    def _sym_codes(self, sym, n: int, who: str):
-        """The per-record symmetry codes of a batch (csrc/bo_sym.h: bit 0 colour flip, bit 1 file mirror) as the library takes them,
-        and the tensor that receives the codes it applied."""
-        t = np.ascontiguousarray(sym, dtype=np.int32).reshape(-1)
-        if t.size != n:
-            raise ValueError(f"{who}: {t.size} symmetry codes for {n} records")
-        return t, torch.empty((n,), dtype=torch.int32, device=self.device)
+    def _batch(self, kind: str, record_index, sym=None, merged=None):
+        """One batch of the sampler `kind` ("batch", "batch_sparse", "batch_sparse_q", "batch_merged"): the outputs are allocated once
+        and handed to the entry point of (kind, sym given or not) in the C argument order."""
+        q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
+        n = int(q.size)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)  # noqa: E731
+        states, zs = f32(n, E.INPUT_CHANNELS, 8, 8), f32(n, 1)
+        if kind == "batch":
+            out = (states, f32(n, E.NUM_ACTIONS), zs)
+        else:
+            W = self.pi_width if merged is None else merged.width
+            out = (states, torch.empty((n, W), dtype=torch.int32, device=self.device), f32(n, W), zs)
+            if kind != "batch_sparse":
+                out += (f32(n, 1),)
+        name = {"batch": "bo_replay_sample", "batch_sparse": "bo_replay_sample_sparse", "batch_sparse_q": "bo_replay_sample_sparse_q",
+                "batch_merged": "bo_replay_sample_merged"}[kind]
+        args = [self.h] + ([] if merged is None else [merged.h]) + [n, q.ctypes.data_as(C.POINTER(C.c_int64))]
+        if sym is not None:
+            # the per-record symmetry codes (csrc/bo_sym.h: bit 0 colour flip, bit 1 file mirror), and the tensor for the codes applied
+            t = np.ascontiguousarray(sym, dtype=np.int32).reshape(-1)
+            if t.size != n:
+                raise ValueError(f"{kind}: {t.size} symmetry codes for {n} records")
+            name += "_sym"
+            args.append(t.ctypes.data_as(E._I32P))
+            out += (torch.empty((n,), dtype=torch.int32, device=self.device),)
+        self._check(getattr(self.lib, name)(*args, *(x.data_ptr() for x in out), self._stream()))
+        return out
 
     def batch(self, record_index, sym=None):
         """(states [n,120,8,8], policies [n,4672], values [n,1]) of the records with these indices (0 = oldest resident record).
         sym (one code 0..3 per record: bit 0 = colour flip, bit 1 = file mirror): each record under that board symmetry -- the planes of
         the transformed game, pi scattered to the transformed moves -- and a fourth element, applied [n] int32: the code that was
         applied (the mirror bit is dropped while the record's position has a castling right)."""
-        q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
-        n = int(q.size)
-        kw = dict(dtype=torch.float32, device=self.device)
-        if sym is not None:
-            t, applied = self._sym_codes(sym, n, "batch")
-        states, pis, zs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, E.NUM_ACTIONS), **kw), torch.empty((n, 1), **kw)
-        if sym is not None:
-            self._check(self.lib.bo_replay_sample_sym(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), t.ctypes.data_as(E._I32P),
-                                                      states.data_ptr(), pis.data_ptr(), zs.data_ptr(), applied.data_ptr(), self._stream()))
-            return states, pis, zs, applied
-        self._check(self.lib.bo_replay_sample(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), states.data_ptr(), pis.data_ptr(), zs.data_ptr(),
-                                              self._stream()))
-        return states, pis, zs
+        return self._batch("batch", record_index, sym)
 
     def batch_sparse(self, record_index, sym=None):
         """(states [n,120,8,8], pi_idx [n,W] int32, pi_val [n,W], values [n,1]) of the records with these indices: the states and
         values of batch(), pi as the records keep it (W = pi_width; unused slots -1 / 0) for train.sparse_policy_value_loss.
         sym: as batch(); pi_idx holds the transformed moves' indices in the records' entry order, and applied [n] comes last."""
-        q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
-        n, W = int(q.size), self.pi_width
-        kw = dict(dtype=torch.float32, device=self.device)
-        if sym is not None:
-            t, applied = self._sym_codes(sym, n, "batch_sparse")
-            states, zs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw)
-            idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
-            self._check(self.lib.bo_replay_sample_sparse_sym(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), t.ctypes.data_as(E._I32P),
-                                                             states.data_ptr(), idx.data_ptr(), val.data_ptr(), zs.data_ptr(),
-                                                             applied.data_ptr(), self._stream()))
-            return states, idx, val, zs, applied
-        states, zs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw)
-        idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
-        self._check(self.lib.bo_replay_sample_sparse(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), states.data_ptr(), idx.data_ptr(),
-                                                     val.data_ptr(), zs.data_ptr(), self._stream()))
-        return states, idx, val, zs
+        return self._batch("batch_sparse", record_index, sym)
 
     def batch_sparse_q(self, record_index, sym=None):
         """batch_sparse plus the records' root values q [n,1] (the search's value of the position for the side to move, as z is the
         game's; q == z for a record without one) for train.sparse_policy_value_loss_mix.  One launch writes all five.
         sym: as batch_sparse(); z and q are from the side to move's point of view and do not change; applied [n] comes last."""
-        q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
-        n, W = int(q.size), self.pi_width
-        kw = dict(dtype=torch.float32, device=self.device)
-        if sym is not None:
-            t, applied = self._sym_codes(sym, n, "batch_sparse_q")
-            states, zs, qs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw), torch.empty((n, 1), **kw)
-            idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
-            self._check(self.lib.bo_replay_sample_sparse_q_sym(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), t.ctypes.data_as(E._I32P),
-                                                               states.data_ptr(), idx.data_ptr(), val.data_ptr(), zs.data_ptr(), qs.data_ptr(),
-                                                               applied.data_ptr(), self._stream()))
-            return states, idx, val, zs, qs, applied
-        states, zs, qs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw), torch.empty((n, 1), **kw)
-        idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
-        self._check(self.lib.bo_replay_sample_sparse_q(self.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), states.data_ptr(), idx.data_ptr(),
-                                                       val.data_ptr(), zs.data_ptr(), qs.data_ptr(), self._stream()))
-        return states, idx, val, zs, qs
+        return self._batch("batch_sparse_q", record_index, sym)
 
     def merge_duplicates(self, index=None, key: str = "input", table_slots: int = 0) -> "MergedTargets":
         """One target per distinct input among the records `index` (None: every resident record): csrc/bo_merge.h groups the records on
@@ -447,21 +425,7 @@ class GpuReplayBuffer:
         comes last."""
         if merged.h is None:
             raise ValueError("batch_merged: the merge is closed")
-        q = np.ascontiguousarray(record_index, dtype=np.int64).reshape(-1)
-        n, W = int(q.size), merged.width
-        kw = dict(dtype=torch.float32, device=self.device)
-        if sym is not None:
-            t, applied = self._sym_codes(sym, n, "batch_merged")
-        states, zs, qs = torch.empty((n, E.INPUT_CHANNELS, 8, 8), **kw), torch.empty((n, 1), **kw), torch.empty((n, 1), **kw)
-        idx, val = torch.empty((n, W), dtype=torch.int32, device=self.device), torch.empty((n, W), **kw)
-        if sym is not None:
-            self._check(self.lib.bo_replay_sample_merged_sym(self.h, merged.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                             t.ctypes.data_as(E._I32P), states.data_ptr(), idx.data_ptr(), val.data_ptr(),
-                                                             zs.data_ptr(), qs.data_ptr(), applied.data_ptr(), self._stream()))
-            return states, idx, val, zs, qs, applied
-        self._check(self.lib.bo_replay_sample_merged(self.h, merged.h, n, q.ctypes.data_as(C.POINTER(C.c_int64)), states.data_ptr(),
-                                                     idx.data_ptr(), val.data_ptr(), zs.data_ptr(), qs.data_ptr(), self._stream()))
-        return states, idx, val, zs, qs
+        return self._batch("batch_merged", record_index, sym, merged)
 
     def sample(self, batch_size: int, rng: Optional[np.random.Generator] = None):
         rng = rng if rng is not None else np.random.default_rng()

@@ -6,10 +6,14 @@ position and its twin.
 Plays --games self-play games with a random-init net (the corpus recipe of scripts/merge_cost.py) and adds them to a GpuReplayBuffer.
 Each of the four samplers is then called at --batch records per call (the training batch size) in five variants: today's entry point,
 and the _sym entry point with codes all 0, all 1, all 3 and random.  With --parent-lib the same games are also added to a buffer of a
-library built from the parent commit, and its samplers are a sixth variant.  After --warmup rounds the variants are called in turn,
+library built from the parent commit, and its samplers are a sixth variant ("parent") and, where that library exports the _sym entry
+points, a seventh ("parent sym random": the random codes through the parent's).  After --warmup rounds the variants are called in turn,
 in a new random order every round, --reps rounds; every call is timed by device events around it and by the host clock (the call ends
 in a stream synchronise).  The same record indices are used by every variant of a round.  Reported: median, minimum, maximum and the
-quartiles per variant, and the ratio of medians to the baseline (the parent's sampler where there is one, else today's entry point).
+quartiles per variant, and the ratio of medians to the baseline (the parent's sampler where there is one, else today's entry point);
+with a parent, also whether this tree's median is inside the parent's own spread (no higher than the parent's third quartile), "plain"
+against "parent" and "sym random" against "parent sym random".  The outputs of all eight entry points are compared byte for byte with
+the parent's on 4096 random records.
 Then validate.symmetry_consistency for a random-init net and, with --checkpoint, for those weights."""
 import argparse
 import ctypes as C
@@ -28,7 +32,8 @@ SAMPLERS = ("batch", "batch_sparse", "batch_sparse_q", "batch_merged")
 
 
 def parent_buffer(path, games, width, device):
-    """A GpuReplayBuffer on another build of the library (the parent commit's: it has no _sym entry points, so it is bound by hand)."""
+    """A GpuReplayBuffer on another build of the library (the parent commit's), bound by hand: every bo_replay_* entry point that
+    library exports, the _sym ones included where it has them (buf.has_sym)."""
     from betaone_amd import engine as E
     from betaone_amd import records as R
 
@@ -43,6 +48,7 @@ def parent_buffer(path, games, width, device):
     slots = sum(int(g["n_plies"]) + 1 for g in games) + 64
     buf._check(lib.bo_replay_create(slots, width, device.index or 0, C.byref(h)))
     buf.h = h
+    buf.has_sym = all(hasattr(lib, f"bo_replay_sample{k}_sym") for k in ("", "_sparse", "_sparse_q", "_merged"))
     assert buf.add(games) == 0
     return buf
 
@@ -126,6 +132,8 @@ def main():
                 variants[label] = lambda idx, c=c: call(buf, merged, idx, c)
             if old is not None:
                 variants["parent"] = lambda idx: call(old, old_merged, idx)
+                if old.has_sym:
+                    variants["parent sym random"] = lambda idx, c=codes["sym random"]: call(old, old_merged, idx, c)
             labels = list(variants)
             dev_ms, host_ms = {k: [] for k in labels}, {k: [] for k in labels}
             for r in range(a.warmup + a.reps):
@@ -148,17 +156,27 @@ def main():
             row = {k: dict(device_ms=stat(dev_ms[k]), host_ms=stat(host_ms[k]), ratio_to_baseline=float(np.median(dev_ms[k]) / np.median(dev_ms[base])))
                    for k in labels}
             out["samplers"][f"{name} @ {batch}"] = dict(baseline=base, variants=row)
+            for mine, theirs in (("plain", "parent"), ("sym random", "parent sym random")):
+                if theirs in row:   # this tree's median against the parent's own spread
+                    row[mine]["parent_variant"] = theirs
+                    row[mine]["median_within_parent_q3"] = bool(row[mine]["device_ms"]["median"] <= row[theirs]["device_ms"]["q3"])
             print(f"[symmetry_cost] {name} @ {batch}: " + "; ".join(
                 f"{k} {row[k]['device_ms']['median'] * 1e3:.1f} us ({row[k]['device_ms']['min'] * 1e3:.1f} .. {row[k]['device_ms']['max'] * 1e3:.1f}; "
                 f"x{row[k]['ratio_to_baseline']:.3f})" for k in labels), flush=True)
-    # the outputs: code 0 is today's entry point and, where there is one, the parent's, byte for byte
-    idx = rng.integers(0, n, size=4096)
+    # the outputs: code 0 is today's entry point, and every entry point (the _sym ones with random codes) is the parent's, byte for byte
+    idx, mixed = rng.integers(0, n, size=4096), rng.integers(0, 4, size=4096).astype(np.int32)
+    same = lambda a, b: all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, b))  # noqa: E731  (applied, where only one has it, is left out)
+    out["entry_points_equal_to_parent"] = []
     for name in SAMPLERS:
         f = lambda b, m, **kw: b.batch_merged(m, idx, **kw) if name == "batch_merged" else getattr(b, name)(idx, **kw)  # noqa: E731
         plain, zero = f(buf, merged), f(buf, merged, sym=np.zeros(4096, np.int32))
-        assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(plain, zero)), name
+        assert same(plain, zero), name
         if old is not None:
-            assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(plain, f(old, old_merged))), name
+            assert same(plain, f(old, old_merged)), name
+            out["entry_points_equal_to_parent"].append(name)
+            if old.has_sym:
+                assert same(f(buf, merged, sym=mixed), f(old, old_merged, sym=mixed)), f"{name}, sym"
+                out["entry_points_equal_to_parent"].append(f"{name}, sym")
     out["outputs_equal"] = True
 
     # consistency: how differently a net scores a position and its twin

@@ -607,6 +607,46 @@ def check_refusals(device):
                     same_batch(got, p.sym(name, t) if t else p.plain[name], f"{name}: a batch of {n} with mixed codes", rows=(r, index[r]))
 
 
+# ---- 6b: one staging block under calls of every shape ------------------------------------------------------------------------------------
+
+def check_staging(device):
+    """The samplers share one staging block (rows slot, k and, where a sampler has them, sym and group; n ints each): calls of
+    different row counts and batch sizes interleaved on ONE buffer, so the block grows, shrinks in use and changes its row offsets
+    from call to call; then a refused call larger than anything staged before.  Every batch is compared bit for bit with the rows of
+    the whole-corpus batches, which are taken only after the sequence has run."""
+    from betaone_amd import engine as E
+
+    p = pair(device)
+    rng = np.random.default_rng(31)
+    done = []
+
+    def call(name, n, with_sym):
+        index = rng.integers(0, p.n, size=n)
+        sym = rng.integers(0, 4, size=n) if with_sym else None
+        done.append((name, index, sym, sample(p.buf, name, index, sym=sym, merged=p.merge)))
+
+    for name, n, with_sym in (("sparse", 3, False), ("merged", 130, True), ("dense", 1, False), ("sparse_q", 2, True), ("merged", 130, False),
+                              ("dense", 65, True)):
+        call(name, n, with_sym)
+    bad = rng.integers(0, 4, size=200)
+    bad[137] = 4
+    with pytest.raises(E.EngineError, match="symmetry code 4 of sample 137"):
+        sample(p.buf, "merged", rng.integers(0, p.n, size=200), sym=bad, merged=p.merge)
+    call("sparse_q", 2, True)
+    assert len(done) == 7
+    for name, index, sym, got in done:
+        what = f"{name}: a batch of {index.size}{' with mixed codes' if sym is not None else ''} among calls of other shapes"
+        assert len(got["z"]) == index.size
+        if sym is None:
+            same_batch(got, p.plain[name], what, rows=(np.arange(index.size), index))
+            continue
+        assert np.array_equal(got["applied"], np.where(p.rights[index], sym & 1, sym)), what
+        for t in range(4):
+            r = np.nonzero(got["applied"] == t)[0]
+            if r.size:
+                same_batch(got, p.sym(name, t) if t else p.plain[name], what, rows=(r, index[r]))
+
+
 # ---- 7: the commands -------------------------------------------------------------------------------------------------------------------
 
 def _data(tmp_path):

@@ -41,6 +41,11 @@ def test_refusals_and_odd_batch_sizes():
         SC.check_refusals("cpu")
 
 
+def test_one_staging_block_under_calls_of_every_shape():
+    with H.emulator_backend():
+        SC.check_staging("cpu")
+
+
 def test_train_command_with_augment(tmp_path):
     with H.emulator_backend():
         SC.check_train_command("cpu", tmp_path, extra=("--no-amp",))

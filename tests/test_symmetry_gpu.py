@@ -35,6 +35,10 @@ def test_refusals_and_odd_batch_sizes():
     SC.check_refusals(DEV)
 
 
+def test_one_staging_block_under_calls_of_every_shape():
+    SC.check_staging(DEV)
+
+
 def test_train_command_with_augment(tmp_path):
     SC.check_train_command(DEV, tmp_path)
 
