@@ -1971,7 +1971,7 @@ extern "C" int bo_pgn_movetext_text(int32_t n_plies, const void *san, const uint
     return BO_OK;
 }
 
-// ---- the sparse-target training loss (bo_train.h) -----------------------------------------------------------------------------
+// ---- the sparse-target training loss (bo_train.h) and the validation metrics (bo_metrics.h) --------------------------------------
 // Calls f with a null pointer of the storage type of a BO_DTYPE_* code; false for an unknown code.
 template <class F> static bool train_dtype(int dt, F &&f) {
     switch (dt) {
@@ -1983,114 +1983,98 @@ template <class F> static bool train_dtype(int dt, F &&f) {
     }
     return false;
 }
-#define BO_TRAIN_TYPES(tl, tv) typedef std::remove_pointer_t<decltype(tl)> TL; typedef std::remove_pointer_t<decltype(tv)> TV
 
-static int train_loss_args(const char *who, int32_t n, int32_t W, const void *logits, const void *value, const int32_t *pi_idx,
-                           const float *pi_val, const float *z, const float *row_stats) {
-    if (n < 1 || W < 1 || W > BO_RES_CAP || !logits || !value || !pi_idx || !pi_val || !z || !row_stats) return fail(BO_E_ARG, std::string(who) + ": bad arguments");
+// The one path of the five entry points below: the arguments they share and the entry point's own (extra_ok), then
+// row(TL *, TV *) launches the row kernel of the dtype pair (two null pointers that carry the types), reduce() the kernel behind it.
+// A bad argument wins over an unsupported dtype.
+template <class Row, class Reduce>
+static int train_launch(const char *who, int32_t n, int32_t W, const void *logits, int32_t logits_dtype, const void *value, int32_t value_dtype,
+                        const int32_t *pi_idx, const float *pi_val, const float *z, const void *row_out, bool extra_ok, Row &&row,
+                        Reduce &&reduce) {
+    if (n < 1 || W < 1 || W > BO_RES_CAP || !logits || !value || !pi_idx || !pi_val || !z || !row_out || !extra_ok)
+        return fail(BO_E_ARG, std::string(who) + ": bad arguments");
+    int rc = 0;
+    bool ok = false;
+    train_dtype(logits_dtype, [&](auto *tl) { ok = train_dtype(value_dtype, [&](auto *tv) { rc = row(tl, tv); }); });
+    if (!ok) return fail(BO_E_CONFIG, std::string(who) + ": unsupported dtype");
+    if (!rc) rc = reduce();
+    if (rc) return fail(BO_E_HIP, std::string(who) + ": " + rt_errstr(rc));
     return BO_OK;
 }
+#define BO_TRAIN_TYPES(tl, tv) typedef std::remove_pointer_t<decltype(tl)> TL; typedef std::remove_pointer_t<decltype(tv)> TV
 
 extern "C" int bo_train_loss_forward(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
                                      const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, float *row_stats_dev, float *loss3_dev,
                                      void *stream) {
-    int rc = train_loss_args("bo_train_loss_forward", n, W, logits_dev, value_dev, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev);
-    if (rc) return rc;
-    if (!loss3_dev) return fail(BO_E_ARG, "bo_train_loss_forward: bad arguments");
-    bool ok = false;
-    train_dtype(logits_dtype, [&](auto *tl) {
-        ok = train_dtype(value_dtype, [&](auto *tv) {
+    return train_launch(
+        "bo_train_loss_forward", n, W, logits_dev, logits_dtype, value_dev, value_dtype, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev,
+        loss3_dev != nullptr,
+        [&](auto *tl, auto *tv) {
             BO_TRAIN_TYPES(tl, tv);
-            rc = RT_LAUNCH((bo_k_loss_fwd<TL, TV>), n, stream, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
-                           pi_val_dev, z_dev, row_stats_dev);
-        });
-    });
-    if (!ok) return fail(BO_E_CONFIG, "bo_train_loss_forward: unsupported dtype");
-    if (!rc) rc = RT_LAUNCH(bo_k_loss_reduce, 1, stream, (int)n, (const float *)row_stats_dev, loss3_dev);
-    if (rc) return fail(BO_E_HIP, std::string("bo_train_loss_forward: ") + rt_errstr(rc));
-    return BO_OK;
+            return RT_LAUNCH((bo_k_loss_fwd<TL, TV>), n, stream, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
+                             pi_val_dev, z_dev, row_stats_dev);
+        },
+        [&] { return RT_LAUNCH(bo_k_loss_reduce, 1, stream, (int)n, (const float *)row_stats_dev, loss3_dev); });
 }
 
 extern "C" int bo_train_loss_backward(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
                                       const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, const float *row_stats_dev,
                                       const float *grad_out_dev, void *dlogits_dev, void *dvalue_dev, void *stream) {
-    int rc = train_loss_args("bo_train_loss_backward", n, W, logits_dev, value_dev, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev);
-    if (rc) return rc;
-    if (!grad_out_dev || !dlogits_dev || !dvalue_dev) return fail(BO_E_ARG, "bo_train_loss_backward: bad arguments");
-    bool ok = false;
-    train_dtype(logits_dtype, [&](auto *tl) {
-        ok = train_dtype(value_dtype, [&](auto *tv) {
+    return train_launch(
+        "bo_train_loss_backward", n, W, logits_dev, logits_dtype, value_dev, value_dtype, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev,
+        grad_out_dev && dlogits_dev && dvalue_dev,
+        [&](auto *tl, auto *tv) {
             BO_TRAIN_TYPES(tl, tv);
-            rc = RT_LAUNCH((bo_k_loss_bwd<TL, TV>), n, stream, (int)n, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
-                           pi_val_dev, z_dev, row_stats_dev, grad_out_dev, (TL *)dlogits_dev, (TV *)dvalue_dev);
-        });
-    });
-    if (!ok) return fail(BO_E_CONFIG, "bo_train_loss_backward: unsupported dtype");
-    if (rc) return fail(BO_E_HIP, std::string("bo_train_loss_backward: ") + rt_errstr(rc));
-    return BO_OK;
+            return RT_LAUNCH((bo_k_loss_bwd<TL, TV>), n, stream, (int)n, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
+                             pi_val_dev, z_dev, row_stats_dev, grad_out_dev, (TL *)dlogits_dev, (TV *)dvalue_dev);
+        },
+        [] { return 0; });
 }
 
 // The same with the value target t = (1 - a) z + a q (bo_train.h): q [n] and the mix a (one float32) on the device; row_stats [n,6].
 extern "C" int bo_train_loss_forward_mix(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev,
                                          int32_t value_dtype, const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev,
                                          const float *q_dev, const float *mix_dev, float *row_stats_dev, float *loss5_dev, void *stream) {
-    int rc = train_loss_args("bo_train_loss_forward_mix", n, W, logits_dev, value_dev, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev);
-    if (rc) return rc;
-    if (!q_dev || !mix_dev || !loss5_dev) return fail(BO_E_ARG, "bo_train_loss_forward_mix: bad arguments");
-    bool ok = false;
-    train_dtype(logits_dtype, [&](auto *tl) {
-        ok = train_dtype(value_dtype, [&](auto *tv) {
+    return train_launch(
+        "bo_train_loss_forward_mix", n, W, logits_dev, logits_dtype, value_dev, value_dtype, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev,
+        q_dev && mix_dev && loss5_dev,
+        [&](auto *tl, auto *tv) {
             BO_TRAIN_TYPES(tl, tv);
-            rc = RT_LAUNCH((bo_k_loss_fwd_mix<TL, TV>), n, stream, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
-                           pi_val_dev, z_dev, q_dev, mix_dev, row_stats_dev);
-        });
-    });
-    if (!ok) return fail(BO_E_CONFIG, "bo_train_loss_forward_mix: unsupported dtype");
-    if (!rc) rc = RT_LAUNCH(bo_k_loss_reduce_mix, 1, stream, (int)n, (const float *)row_stats_dev, mix_dev, loss5_dev);
-    if (rc) return fail(BO_E_HIP, std::string("bo_train_loss_forward_mix: ") + rt_errstr(rc));
-    return BO_OK;
+            return RT_LAUNCH((bo_k_loss_fwd_mix<TL, TV>), n, stream, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
+                             pi_val_dev, z_dev, q_dev, mix_dev, row_stats_dev);
+        },
+        [&] { return RT_LAUNCH(bo_k_loss_reduce_mix, 1, stream, (int)n, (const float *)row_stats_dev, mix_dev, loss5_dev); });
 }
 
 extern "C" int bo_train_loss_backward_mix(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev,
                                           int32_t value_dtype, const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev,
                                           const float *q_dev, const float *mix_dev, const float *row_stats_dev, const float *grad_out_dev,
                                           void *dlogits_dev, void *dvalue_dev, void *stream) {
-    int rc = train_loss_args("bo_train_loss_backward_mix", n, W, logits_dev, value_dev, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev);
-    if (rc) return rc;
-    if (!q_dev || !mix_dev || !grad_out_dev || !dlogits_dev || !dvalue_dev) return fail(BO_E_ARG, "bo_train_loss_backward_mix: bad arguments");
-    bool ok = false;
-    train_dtype(logits_dtype, [&](auto *tl) {
-        ok = train_dtype(value_dtype, [&](auto *tv) {
+    return train_launch(
+        "bo_train_loss_backward_mix", n, W, logits_dev, logits_dtype, value_dev, value_dtype, pi_idx_dev, pi_val_dev, z_dev, row_stats_dev,
+        q_dev && mix_dev && grad_out_dev && dlogits_dev && dvalue_dev,
+        [&](auto *tl, auto *tv) {
             BO_TRAIN_TYPES(tl, tv);
-            rc = RT_LAUNCH((bo_k_loss_bwd_mix<TL, TV>), n, stream, (int)n, (int)W, (const TL *)logits_dev, (const TV *)value_dev,
-                           (const int *)pi_idx_dev, pi_val_dev, z_dev, q_dev, mix_dev, row_stats_dev, grad_out_dev, (TL *)dlogits_dev,
-                           (TV *)dvalue_dev);
-        });
-    });
-    if (!ok) return fail(BO_E_CONFIG, "bo_train_loss_backward_mix: unsupported dtype");
-    if (rc) return fail(BO_E_HIP, std::string("bo_train_loss_backward_mix: ") + rt_errstr(rc));
-    return BO_OK;
+            return RT_LAUNCH((bo_k_loss_bwd_mix<TL, TV>), n, stream, (int)n, (int)W, (const TL *)logits_dev, (const TV *)value_dev,
+                             (const int *)pi_idx_dev, pi_val_dev, z_dev, q_dev, mix_dev, row_stats_dev, grad_out_dev, (TL *)dlogits_dev,
+                             (TV *)dvalue_dev);
+        },
+        [] { return 0; });
 }
 
 // Held-out validation metrics (bo_metrics.h): a record per row, then the rows of every bucket added into accum.
 extern "C" int bo_train_metrics(int32_t n, int32_t W, const void *logits_dev, int32_t logits_dtype, const void *value_dev, int32_t value_dtype,
                                 const int32_t *pi_idx_dev, const float *pi_val_dev, const float *z_dev, const float *q_dev,
                                 const int32_t *bucket_dev, int32_t n_buckets, float *rows_dev, double *accum_dev, void *stream) {
-    int rc = train_loss_args("bo_train_metrics", n, W, logits_dev, value_dev, pi_idx_dev, pi_val_dev, z_dev, rows_dev);
-    if (rc) return rc;
-    if (n_buckets < 1 || !accum_dev) return fail(BO_E_ARG, "bo_train_metrics: bad arguments");
-    bool ok = false;
-    train_dtype(logits_dtype, [&](auto *tl) {
-        ok = train_dtype(value_dtype, [&](auto *tv) {
+    return train_launch(
+        "bo_train_metrics", n, W, logits_dev, logits_dtype, value_dev, value_dtype, pi_idx_dev, pi_val_dev, z_dev, rows_dev,
+        n_buckets >= 1 && accum_dev,
+        [&](auto *tl, auto *tv) {
             BO_TRAIN_TYPES(tl, tv);
-            rc = RT_LAUNCH((bo_k_metrics_rows<TL, TV>), n, stream, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
-                           pi_val_dev, z_dev, q_dev, rows_dev);
-        });
-    });
-    if (!ok) return fail(BO_E_CONFIG, "bo_train_metrics: unsupported dtype");
-    if (!rc) rc = RT_LAUNCH(bo_k_metrics_reduce, n_buckets, stream, (int)n, (const float *)rows_dev, (const int *)bucket_dev, accum_dev);
-    if (rc) return fail(BO_E_HIP, std::string("bo_train_metrics: ") + rt_errstr(rc));
-    return BO_OK;
+            return RT_LAUNCH((bo_k_metrics_rows<TL, TV>), n, stream, (int)W, (const TL *)logits_dev, (const TV *)value_dev, (const int *)pi_idx_dev,
+                             pi_val_dev, z_dev, q_dev, rows_dev);
+        },
+        [&] { return RT_LAUNCH(bo_k_metrics_reduce, n_buckets, stream, (int)n, (const float *)rows_dev, (const int *)bucket_dev, accum_dev); });
 }
 
 // ---- introspection -----------------------------------------------------------------------------------------

@@ -53,15 +53,8 @@ BO_LOSS_KERNEL void bo_k_metrics_rows(int W, const TL *logits, const TV *value, 
     const int b = bo_block(), s = bo_lane();
     const TL *xr = logits + (size_t)b * BO_NUM_ACTIONS;
     float x[BO_LOSS_PER_LANE];
-    float m = -__builtin_inff();
-    bool nan = false, nonfinite = false;
-#pragma unroll
-    for (int j = 0; j < BO_LOSS_PER_LANE; j++) {
-        x[j] = bo_ld_f(xr + s + 64 * j);
-        nan |= x[j] != x[j];
-        nonfinite |= !(x[j] - x[j] == 0.0f);
-        m = x[j] > m ? x[j] : m;
-    }
+    bool nan, nonfinite;
+    const float m = bo_loss_row_load(xr, x, nan, nonfinite);
     const bool nonfinite_row = bo_ballot(nonfinite) != 0;   // (here, not at the end: the test would keep the logits alive to there)
     float mx = bo_wave_max_f(m);
     if (bo_ballot(nan)) mx = __builtin_nanf("");  // (as bo_k_loss_fwd)

@@ -65,102 +65,30 @@ BO_DEV void bo_st_f(_Float16 *p, float v) { *p = (_Float16)v; }  // v_cvt_f16_f3
 
 BO_DEV bool bo_loss_valid(int i) { return (unsigned)i < (unsigned)BO_NUM_ACTIONS; }
 
-template <typename TL, typename TV>
-BO_LOSS_KERNEL void bo_k_loss_fwd(int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z,
-                                  float *row_stats) {
-    const int b = bo_block(), s = bo_lane();
-    const TL *xr = logits + (size_t)b * BO_NUM_ACTIONS;
-    float x[BO_LOSS_PER_LANE];
+// A row into the wave's registers: lane s gets the logits of actions s, s + 64, ... and returns the largest of them; nan / nonfinite:
+// the lane saw a NaN / a NaN or an infinity.
+template <typename TL>
+BO_DEV float bo_loss_row_load(const TL *xr, float (&x)[BO_LOSS_PER_LANE], bool &nan, bool &nonfinite) {
+    const int s = bo_lane();
     float m = -__builtin_inff();
-    bool nan = false, nonfinite = false;
+    nan = nonfinite = false;
+#pragma unroll
     for (int j = 0; j < BO_LOSS_PER_LANE; j++) {
         x[j] = bo_ld_f(xr + s + 64 * j);
         nan |= x[j] != x[j];
         nonfinite |= !(x[j] - x[j] == 0.0f);
         m = x[j] > m ? x[j] : m;
     }
-    float mx = bo_wave_max_f(m);
-    if (bo_ballot(nan)) mx = __builtin_nanf("");  // (PyTorch's max propagates NaN; the butterfly compare would drop it)
-    float se = 0.0f;
-    for (int j = 0; j < BO_LOSS_PER_LANE; j++) se += expf(x[j] - mx);
-    const float logsum = logf(bo_wave_sum_f(se));
-    float acc = 0.0f;
-    for (int e = s; e < W; e += 64) {
-        const int i = pi_idx[(size_t)b * W + e];
-        if (bo_loss_valid(i)) acc += pi_val[(size_t)b * W + e] * ((bo_ld_f(xr + i) - mx) - logsum);
-    }
-    acc = bo_wave_sum_f(acc);
-    const bool bad = bo_ballot(nonfinite) != 0;
-    if (s == 0) {
-        float *st = row_stats + (size_t)b * BO_LOSS_STATS;
-        const float d = bo_ld_f(value + b) - z[b];
-        st[0] = mx;
-        st[1] = logsum;
-        st[2] = bad ? __builtin_nanf("") : -acc;
-        st[3] = d * d;
-    }
+    return m;
 }
 
-BO_LOSS_KERNEL void bo_k_loss_reduce(int n, const float *row_stats, float *loss3) {
-    const int s = bo_lane();
-    float p = 0.0f, v = 0.0f;
-    for (int b = s; b < n; b += 64) {
-        p += row_stats[(size_t)b * BO_LOSS_STATS + 2];
-        v += row_stats[(size_t)b * BO_LOSS_STATS + 3];
-    }
-    p = bo_wave_sum_f(p);
-    v = bo_wave_sum_f(v);
-    if (s == 0) {
-        const float pl = p / (float)n, vl = v / (float)n;
-        loss3[0] = pl + vl;
-        loss3[1] = pl;
-        loss3[2] = vl;
-    }
-}
-
-template <typename TL, typename TV>
-BO_LOSS_KERNEL void bo_k_loss_bwd(int n, int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z,
-                                  const float *row_stats, const float *grad3, TL *dlogits, TV *dvalue) {
-    const int b = bo_block(), s = bo_lane();
-    const TL *xr = logits + (size_t)b * BO_NUM_ACTIONS;
-    TL *dr = dlogits + (size_t)b * BO_NUM_ACTIONS;
-    const int *ix = pi_idx + (size_t)b * W;
-    const float *vx = pi_val + (size_t)b * W;
-    // loss3 = [total, policy, value]: the policy term feeds total and policy, the value term total and value
-    const float gp = grad3[0] + grad3[1], gv = grad3[0] + grad3[2];
-    const float gb = gp / (float)n;
-    const float mx = row_stats[(size_t)b * BO_LOSS_STATS], logsum = row_stats[(size_t)b * BO_LOSS_STATS + 1];
-    float S = 0.0f;
-    for (int e = 0; e < W; e++) S += bo_loss_valid(ix[e]) ? vx[e] : 0.0f;  // (pi is normalised in float32: S need not be 1)
-    const float sgb = S * gb;
-    for (int j = 0; j < BO_LOSS_PER_LANE; j++) {
-        const int a = s + 64 * j;
-        float t = 0.0f;
-        for (int e = 0; e < W; e++) t = ix[e] == a ? vx[e] : t;  // one writer per address: the lane of the action looks it up
-        const float sm = expf((bo_ld_f(xr + a) - mx) - logsum);
-        bo_st_f(dr + a, sm * sgb - t * gb);
-    }
-    if (s == 0) bo_st_f(dvalue + b, (2.0f / (float)n) * (bo_ld_f(value + b) - z[b]) * gv);
-}
-
-// ---- the value target as a mix of z and the root value q (header comment) -----------------------------------------------------------
-// The policy side of the kernels above as two functions, for the mix kernels.  The kernels above keep their own text: their
-// instances are compiled as they always were (VGPR counts are part of what profiles/ records), and a mix of 0 is checked against
-// them bit for bit (tests/value_mix_cases.py).
-//
 // A row's logits once through the wave: st[0..2] = max, log sum exp(x - max), the policy term (written by lane 0).
 template <typename TL>
 BO_DEV void bo_loss_row_policy(int W, const TL *xr, const int *ix, const float *vx, float *st) {
     const int s = bo_lane();
     float x[BO_LOSS_PER_LANE];
-    float m = -__builtin_inff();
-    bool nan = false, nonfinite = false;
-    for (int j = 0; j < BO_LOSS_PER_LANE; j++) {
-        x[j] = bo_ld_f(xr + s + 64 * j);
-        nan |= x[j] != x[j];
-        nonfinite |= !(x[j] - x[j] == 0.0f);
-        m = x[j] > m ? x[j] : m;
-    }
+    bool nan, nonfinite;
+    const float m = bo_loss_row_load(xr, x, nan, nonfinite);
     float mx = bo_wave_max_f(m);
     if (bo_ballot(nan)) mx = __builtin_nanf("");  // (PyTorch's max propagates NaN; the butterfly compare would drop it)
     float se = 0.0f;
@@ -204,54 +132,96 @@ BO_DEV float bo_mix_target(float a, float z, float q) {
     return (1.0f - a) * z + a * q;
 }
 
+// the value target of row b: z, or under MIX the mix of z and q
+template <bool MIX>
+BO_DEV float bo_loss_value_target(int b, const float *z, const float *q, const float *mix) {
+    if constexpr (MIX) return bo_mix_target(mix[0], z[b], q[b]);
+    else return z[b];
+}
+
+// ---- the kernels -----------------------------------------------------------------------------------------------------------------------
+// One body each for the forward, the reduce and the backward.  MIX is a compile-time switch: the stride of row_stats, the value target
+// (z, or bo_mix_target) and the value columns that lane 0 writes.  The named kernels below are the instantiations; the plain ones pass
+// no q and no mix.  bo_k_metrics_rows (bo_metrics.h) shares bo_loss_row_load and repeats bo_loss_row_policy's operations in its order
+// for its CE column.
+template <bool MIX, typename TL, typename TV>
+BO_DEV void bo_loss_fwd_row(int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z, const float *q,
+                            const float *mix, float *row_stats) {
+    const int b = bo_block();
+    float *st = row_stats + (size_t)b * (MIX ? BO_LOSS_STATS_MIX : BO_LOSS_STATS);
+    bo_loss_row_policy(W, logits + (size_t)b * BO_NUM_ACTIONS, pi_idx + (size_t)b * W, pi_val + (size_t)b * W, st);
+    if (bo_lane() == 0) {
+        const float v = bo_ld_f(value + b), dz = v - z[b];
+        if constexpr (MIX) {
+            const float d = v - bo_mix_target(mix[0], z[b], q[b]), dq = v - q[b];
+            st[3] = d * d;
+            st[4] = dz * dz;
+            st[5] = dq * dq;
+        } else {
+            st[3] = dz * dz;
+        }
+    }
+}
+
+// One wave: lane s sums rows s, s + 64, ... of every column from 2 on, then a butterfly per column.  out is loss3, or loss5 under MIX.
+template <bool MIX>
+BO_DEV void bo_loss_reduce_cols(int n, const float *row_stats, const float *mix, float *out) {
+    constexpr int STRIDE = MIX ? BO_LOSS_STATS_MIX : BO_LOSS_STATS, COLS = STRIDE - 2;
+    const int s = bo_lane();
+    float a[COLS];
+    for (int c = 0; c < COLS; c++) a[c] = 0.0f;
+    for (int b = s; b < n; b += 64)
+        for (int c = 0; c < COLS; c++) a[c] += row_stats[(size_t)b * STRIDE + 2 + c];
+    for (int c = 0; c < COLS; c++) a[c] = bo_wave_sum_f(a[c]);
+    if (s == 0) {
+        const float pl = a[0] / (float)n, vl = a[1] / (float)n;
+        const bool ok = !MIX || bo_mix_ok(mix[0]);
+        const float nan = __builtin_nanf("");
+        out[0] = ok ? pl + vl : nan;
+        out[1] = ok ? pl : nan;
+        out[2] = vl;                                 // (under an invalid mix NaN already: every row's target is)
+        if constexpr (MIX) {
+            out[3] = ok ? a[2] / (float)n : nan;
+            out[4] = ok ? a[3] / (float)n : nan;
+        }
+    }
+}
+
+template <bool MIX, typename TL, typename TV>
+BO_DEV void bo_loss_bwd_row(int n, int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z,
+                            const float *q, const float *mix, const float *row_stats, const float *grad3, TL *dlogits, TV *dvalue) {
+    constexpr int STRIDE = MIX ? BO_LOSS_STATS_MIX : BO_LOSS_STATS;
+    const int b = bo_block();
+    // the gradient of [total, policy, value]: the policy term feeds total and policy, the value term total and value (loss5's two
+    // diagnostics have none).  It is read first, the statistics are indexed in the call and the target is one expression: in this
+    // order the scalar loads of the prologue come out as profiles/loss_refactor.md has measured them.
+    const float gp = grad3[0] + grad3[1], gv = grad3[0] + grad3[2];
+    bo_loss_row_dlogits(n, W, logits + (size_t)b * BO_NUM_ACTIONS, dlogits + (size_t)b * BO_NUM_ACTIONS, pi_idx + (size_t)b * W,
+                        pi_val + (size_t)b * W, gp, row_stats[(size_t)b * STRIDE], row_stats[(size_t)b * STRIDE + 1]);
+    if (bo_lane() == 0) bo_st_f(dvalue + b, (2.0f / (float)n) * (bo_ld_f(value + b) - bo_loss_value_target<MIX>(b, z, q, mix)) * gv);
+}
+
+template <typename TL, typename TV>
+BO_LOSS_KERNEL void bo_k_loss_fwd(int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z,
+                                  float *row_stats) {
+    bo_loss_fwd_row<false>(W, logits, value, pi_idx, pi_val, z, nullptr, nullptr, row_stats);
+}
 template <typename TL, typename TV>
 BO_LOSS_KERNEL void bo_k_loss_fwd_mix(int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z,
                                       const float *q, const float *mix, float *row_stats) {
-    const int b = bo_block();
-    float *st = row_stats + (size_t)b * BO_LOSS_STATS_MIX;
-    bo_loss_row_policy(W, logits + (size_t)b * BO_NUM_ACTIONS, pi_idx + (size_t)b * W, pi_val + (size_t)b * W, st);
-    if (bo_lane() == 0) {
-        const float v = bo_ld_f(value + b);
-        const float d = v - bo_mix_target(mix[0], z[b], q[b]), dz = v - z[b], dq = v - q[b];
-        st[3] = d * d;
-        st[4] = dz * dz;
-        st[5] = dq * dq;
-    }
+    bo_loss_fwd_row<true>(W, logits, value, pi_idx, pi_val, z, q, mix, row_stats);
 }
-
-// bo_k_loss_reduce's order over five columns (columns 2 and 3 are summed exactly as there)
+BO_LOSS_KERNEL void bo_k_loss_reduce(int n, const float *row_stats, float *loss3) { bo_loss_reduce_cols<false>(n, row_stats, nullptr, loss3); }
 BO_LOSS_KERNEL void bo_k_loss_reduce_mix(int n, const float *row_stats, const float *mix, float *loss5) {
-    const int s = bo_lane();
-    float p = 0.0f, v = 0.0f, vz = 0.0f, vq = 0.0f;
-    for (int b = s; b < n; b += 64) {
-        const float *st = row_stats + (size_t)b * BO_LOSS_STATS_MIX;
-        p += st[2];
-        v += st[3];
-        vz += st[4];
-        vq += st[5];
-    }
-    p = bo_wave_sum_f(p);
-    v = bo_wave_sum_f(v);
-    vz = bo_wave_sum_f(vz);
-    vq = bo_wave_sum_f(vq);
-    if (s == 0) {
-        const float pl = p / (float)n, vl = v / (float)n;
-        const bool ok = bo_mix_ok(mix[0]);
-        const float nan = __builtin_nanf("");
-        loss5[0] = ok ? pl + vl : nan;
-        loss5[1] = ok ? pl : nan;
-        loss5[2] = vl;                               // (NaN already: every row's target is)
-        loss5[3] = ok ? vz / (float)n : nan;
-        loss5[4] = ok ? vq / (float)n : nan;
-    }
+    bo_loss_reduce_cols<true>(n, row_stats, mix, loss5);
 }
-
+template <typename TL, typename TV>
+BO_LOSS_KERNEL void bo_k_loss_bwd(int n, int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z,
+                                  const float *row_stats, const float *grad3, TL *dlogits, TV *dvalue) {
+    bo_loss_bwd_row<false>(n, W, logits, value, pi_idx, pi_val, z, nullptr, nullptr, row_stats, grad3, dlogits, dvalue);
+}
 template <typename TL, typename TV>
 BO_LOSS_KERNEL void bo_k_loss_bwd_mix(int n, int W, const TL *logits, const TV *value, const int *pi_idx, const float *pi_val, const float *z,
                                       const float *q, const float *mix, const float *row_stats, const float *grad3, TL *dlogits, TV *dvalue) {
-    const int b = bo_block();
-    const float gp = grad3[0] + grad3[1], gv = grad3[0] + grad3[2];  // (grad3 is the gradient of loss5[0:3]: the diagnostics have none)
-    bo_loss_row_dlogits(n, W, logits + (size_t)b * BO_NUM_ACTIONS, dlogits + (size_t)b * BO_NUM_ACTIONS, pi_idx + (size_t)b * W,
-                        pi_val + (size_t)b * W, gp, row_stats[(size_t)b * BO_LOSS_STATS_MIX], row_stats[(size_t)b * BO_LOSS_STATS_MIX + 1]);
-    if (bo_lane() == 0) bo_st_f(dvalue + b, (2.0f / (float)n) * (bo_ld_f(value + b) - bo_mix_target(mix[0], z[b], q[b])) * gv);
+    bo_loss_bwd_row<true>(n, W, logits, value, pi_idx, pi_val, z, q, mix, row_stats, grad3, dlogits, dvalue);
 }

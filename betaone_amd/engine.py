@@ -91,6 +91,8 @@ class BoHeadWeights(C.Structure):  # bo_head_weights: device addresses of one ne
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
 _F64P = C.POINTER(C.c_double)
+# the batch every bo_train_* entry point starts with: n, W, logits and their dtype, value and its dtype, pi_idx, pi_val, z
+_TRAIN_BATCH = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3
 
 _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_abi_version": (C.c_int, []),
@@ -190,12 +192,11 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
                          + [C.c_int, C.c_int, C.c_void_p]),
     "bo_nn_merge_rows": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p]),
     "bo_match_select": (C.c_int, [C.c_void_p] * 4),
-    "bo_train_loss_forward": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6),
-    "bo_train_loss_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8),
-    "bo_train_loss_forward_mix": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8),
-    "bo_train_loss_backward_mix": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 10),
-    "bo_train_metrics": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
-                         + [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bo_train_loss_forward": (C.c_int, _TRAIN_BATCH + [C.c_void_p] * 3),
+    "bo_train_loss_backward": (C.c_int, _TRAIN_BATCH + [C.c_void_p] * 5),
+    "bo_train_loss_forward_mix": (C.c_int, _TRAIN_BATCH + [C.c_void_p] * 5),
+    "bo_train_loss_backward_mix": (C.c_int, _TRAIN_BATCH + [C.c_void_p] * 7),
+    "bo_train_metrics": (C.c_int, _TRAIN_BATCH + [C.c_void_p] * 2 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bo_pgn_parse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]),
     "bo_pgn_size": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int64)] * 3),
     "bo_pgn_export": (C.c_int, [C.c_void_p, _I32P, _I32P, C.c_void_p, C.c_void_p, _I32P, _F32P]),

@@ -48,46 +48,70 @@ def _check(lib, rc: int):
         raise E.EngineError(f"training loss: {lib.bo_last_error().decode()}")
 
 
+def _and(names) -> str:
+    return names[0] if len(names) == 1 else ", ".join(names[:-1]) + " and " + names[-1]
+
+
+def check_batch(who, logits, value, pi_idx, pi_val, z, extras=(), device=None, device_name="one device"):
+    """The input check of the loss and of validate.MetricsAccumulator.add: logits [n,4672] and value (n elements) in one of DTYPE_CODES
+    each, pi_idx [n,W] int32, pi_val [n,W] and z (n elements) float32; extras: (name, tensor or None, dtype, elements or None for n) per
+    optional input; everything on `device` (default: the logits').  ValueError / TypeError with `who` in front.  Returns (logits, value,
+    pi_idx, pi_val, z, *the extras' tensors), contiguous."""
+    n, W = pi_idx.shape
+    named = [("logits", logits), ("value", value), ("pi_idx", pi_idx), ("pi_val", pi_val), ("z", z)] + [(k, t) for k, t, _, _ in extras if t is not None]
+    if (logits.dim() != 2 or logits.shape != (n, E.NUM_ACTIONS) or value.numel() != n or pi_val.shape != (n, W) or z.numel() != n
+            or any(t is not None and t.numel() != (n if count is None else count) for _, t, _, count in extras)):
+        raise ValueError(f"{who}: shapes " + " ".join(f"{k} {tuple(t.shape)}" for k, t in named))
+    if logits.dtype not in DTYPE_CODES or value.dtype not in DTYPE_CODES:
+        raise TypeError(f"{who}: logits {logits.dtype} / value {value.dtype}: float32, float16 or bfloat16")
+    want = [("pi_idx", pi_idx, torch.int32), ("pi_val", pi_val, torch.float32), ("z", z, torch.float32)] + [e[:3] for e in extras if e[1] is not None]
+    if any(t.dtype != dt for _, t, dt in want):
+        raise TypeError(f"{who}: {_and([k for k, _, dt in want if dt == torch.int32])} int32, "
+                        f"{_and([k for k, _, dt in want if dt == torch.float32])} float32")
+    dev = logits.device if device is None else device
+    if any(t.device != dev for _, t in named):
+        raise ValueError(f"{who}: all inputs on {device_name}")
+    return tuple(t.contiguous() for t in (logits, value, pi_idx, pi_val, z)) + tuple(None if t is None else t.contiguous() for _, t, _, _ in extras)
+
+
+def batch_args(logits, value, pi_idx, pi_val, z):
+    """The arguments every bo_train_* entry point starts with (engine._TRAIN_BATCH), of checked tensors."""
+    n, W = pi_idx.shape
+    return (n, W, logits.data_ptr(), DTYPE_CODES[logits.dtype], value.data_ptr(), DTYPE_CODES[value.dtype], pi_idx.data_ptr(), pi_val.data_ptr(),
+            z.data_ptr())
+
+
 class _SparseLoss(torch.autograd.Function):
-    """loss3 = [total, policy, value] of bo_train_loss_forward; the backward is bo_train_loss_backward with the gradient of loss3 read
-    from the device (a GradScaler scale reaches the kernel without a host round trip)."""
+    """Without a mix: loss3 = [total, policy, value] of bo_train_loss_forward, row statistics [n,4].  With q and mix: loss5 of
+    bo_train_loss_forward_mix, row statistics [n,6]; both are read on the device.  The backward is the matching bo_train_loss_backward
+    with the gradient of the first three losses read from the device (a GradScaler scale reaches the kernel without a host round
+    trip; loss5's two diagnostics carry none)."""
 
     @staticmethod
-    def forward(ctx, logits, value, pi_idx, pi_val, z):
+    def forward(ctx, logits, value, pi_idx, pi_val, z, q, mix):
         lib = E.load_hip_library()
-        n, W = pi_idx.shape
-        if logits.dim() != 2 or logits.shape != (n, E.NUM_ACTIONS) or value.numel() != n or pi_val.shape != (n, W) or z.numel() != n:
-            raise ValueError(f"sparse loss: shapes logits {tuple(logits.shape)} value {tuple(value.shape)} pi_idx {tuple(pi_idx.shape)} "
-                             f"pi_val {tuple(pi_val.shape)} z {tuple(z.shape)}")
-        if logits.dtype not in DTYPE_CODES or value.dtype not in DTYPE_CODES:
-            raise TypeError(f"sparse loss: logits {logits.dtype} / value {value.dtype}: float32, float16 or bfloat16")
-        if pi_idx.dtype != torch.int32 or pi_val.dtype != torch.float32 or z.dtype != torch.float32:
-            raise TypeError("sparse loss: pi_idx int32, pi_val and z float32")
-        dev = logits.device
-        if any(t.device != dev for t in (value, pi_idx, pi_val, z)):
-            raise ValueError("sparse loss: all inputs on one device")
-        logits, value = logits.contiguous(), value.contiguous()
-        pi_idx, pi_val, z = pi_idx.contiguous(), pi_val.contiguous(), z.contiguous()
-        row_stats = torch.empty((n, ROW_STATS), dtype=torch.float32, device=dev)
-        loss3 = torch.empty(3, dtype=torch.float32, device=dev)
-        _check(lib, lib.bo_train_loss_forward(n, W, logits.data_ptr(), DTYPE_CODES[logits.dtype], value.data_ptr(), DTYPE_CODES[value.dtype],
-                                              pi_idx.data_ptr(), pi_val.data_ptr(), z.data_ptr(), row_stats.data_ptr(), loss3.data_ptr(),
-                                              _stream(logits)))
-        ctx.save_for_backward(logits, value, pi_idx, pi_val, z, row_stats)
-        ctx.value_shape = value.shape
-        return loss3
+        mixed = mix is not None
+        extras = (("q", q, torch.float32, None), ("mix", mix, torch.float32, 1)) if mixed else ()
+        batch = check_batch("sparse loss", logits, value, pi_idx, pi_val, z, extras)
+        n = pi_idx.shape[0]
+        row_stats = torch.empty((n, ROW_STATS_MIX if mixed else ROW_STATS), dtype=torch.float32, device=logits.device)
+        loss = torch.empty(5 if mixed else 3, dtype=torch.float32, device=logits.device)
+        fn = lib.bo_train_loss_forward_mix if mixed else lib.bo_train_loss_forward
+        _check(lib, fn(*batch_args(*batch[:5]), *(t.data_ptr() for t in batch[5:]), row_stats.data_ptr(), loss.data_ptr(), _stream(logits)))
+        ctx.save_for_backward(row_stats, *batch)
+        ctx.value_shape = batch[1].shape
+        return loss
 
     @staticmethod
-    def backward(ctx, g3):
+    def backward(ctx, g):
         lib = E.load_hip_library()
-        logits, value, pi_idx, pi_val, z, row_stats = ctx.saved_tensors
-        n, W = pi_idx.shape
-        g3 = g3.to(torch.float32).contiguous()
-        dlogits, dvalue = torch.empty_like(logits), torch.empty_like(value)
-        _check(lib, lib.bo_train_loss_backward(n, W, logits.data_ptr(), DTYPE_CODES[logits.dtype], value.data_ptr(), DTYPE_CODES[value.dtype],
-                                               pi_idx.data_ptr(), pi_val.data_ptr(), z.data_ptr(), row_stats.data_ptr(), g3.data_ptr(),
-                                               dlogits.data_ptr(), dvalue.data_ptr(), _stream(logits)))
-        return dlogits, dvalue.view(ctx.value_shape), None, None, None
+        row_stats, *batch = ctx.saved_tensors
+        g3 = g[:3].to(torch.float32).contiguous()
+        dlogits, dvalue = torch.empty_like(batch[0]), torch.empty_like(batch[1])
+        fn = lib.bo_train_loss_backward_mix if len(batch) > 5 else lib.bo_train_loss_backward
+        _check(lib, fn(*batch_args(*batch[:5]), *(t.data_ptr() for t in batch[5:]), row_stats.data_ptr(), g3.data_ptr(), dlogits.data_ptr(),
+                       dvalue.data_ptr(), _stream(batch[0])))
+        return dlogits, dvalue.view(ctx.value_shape), None, None, None, None, None
 
 
 def sparse_policy_value_loss(logits, value, pi_idx, pi_val, z):
@@ -95,51 +119,8 @@ def sparse_policy_value_loss(logits, value, pi_idx, pi_val, z):
     policy = mean_b -sum_e pi_val[b,e] * log_softmax(logits[b])[pi_idx[b,e]], value = mean_b (value[b] - z[b])^2, total = their sum.
     logits [B,4672] and value [B,1] (or [B]) in float32, float16 or bfloat16 -- the net's outputs, under torch.autocast too; the three
     losses are float32 tensors on the logits' device.  Computed on the current stream by two HIP kernels (csrc/bo_train.h)."""
-    loss3 = _SparseLoss.apply(logits, value, pi_idx, pi_val, z.reshape(-1))
+    loss3 = _SparseLoss.apply(logits, value, pi_idx, pi_val, z.reshape(-1), None, None)
     return loss3[0], loss3[1], loss3[2]
-
-
-class _SparseLossMix(torch.autograd.Function):
-    """loss5 of bo_train_loss_forward_mix; the backward is bo_train_loss_backward_mix with the gradient of loss5[0:3] (the two
-    diagnostics carry none).  q and mix are read on the device by both."""
-
-    @staticmethod
-    def forward(ctx, logits, value, pi_idx, pi_val, z, q, mix):
-        lib = E.load_hip_library()
-        n, W = pi_idx.shape
-        if (logits.dim() != 2 or logits.shape != (n, E.NUM_ACTIONS) or value.numel() != n or pi_val.shape != (n, W) or z.numel() != n
-                or q.numel() != n or mix.numel() != 1):
-            raise ValueError(f"sparse loss: shapes logits {tuple(logits.shape)} value {tuple(value.shape)} pi_idx {tuple(pi_idx.shape)} "
-                             f"pi_val {tuple(pi_val.shape)} z {tuple(z.shape)} q {tuple(q.shape)} mix {tuple(mix.shape)}")
-        if logits.dtype not in DTYPE_CODES or value.dtype not in DTYPE_CODES:
-            raise TypeError(f"sparse loss: logits {logits.dtype} / value {value.dtype}: float32, float16 or bfloat16")
-        if pi_idx.dtype != torch.int32 or any(t.dtype != torch.float32 for t in (pi_val, z, q, mix)):
-            raise TypeError("sparse loss: pi_idx int32, pi_val, z, q and mix float32")
-        dev = logits.device
-        if any(t.device != dev for t in (value, pi_idx, pi_val, z, q, mix)):
-            raise ValueError("sparse loss: all inputs on one device")
-        logits, value = logits.contiguous(), value.contiguous()
-        pi_idx, pi_val, z, q = pi_idx.contiguous(), pi_val.contiguous(), z.contiguous(), q.contiguous()
-        row_stats = torch.empty((n, ROW_STATS_MIX), dtype=torch.float32, device=dev)
-        loss5 = torch.empty(5, dtype=torch.float32, device=dev)
-        _check(lib, lib.bo_train_loss_forward_mix(n, W, logits.data_ptr(), DTYPE_CODES[logits.dtype], value.data_ptr(), DTYPE_CODES[value.dtype],
-                                                  pi_idx.data_ptr(), pi_val.data_ptr(), z.data_ptr(), q.data_ptr(), mix.data_ptr(),
-                                                  row_stats.data_ptr(), loss5.data_ptr(), _stream(logits)))
-        ctx.save_for_backward(logits, value, pi_idx, pi_val, z, q, mix, row_stats)
-        ctx.value_shape = value.shape
-        return loss5
-
-    @staticmethod
-    def backward(ctx, g5):
-        lib = E.load_hip_library()
-        logits, value, pi_idx, pi_val, z, q, mix, row_stats = ctx.saved_tensors
-        n, W = pi_idx.shape
-        g3 = g5[:3].to(torch.float32).contiguous()
-        dlogits, dvalue = torch.empty_like(logits), torch.empty_like(value)
-        _check(lib, lib.bo_train_loss_backward_mix(n, W, logits.data_ptr(), DTYPE_CODES[logits.dtype], value.data_ptr(), DTYPE_CODES[value.dtype],
-                                                   pi_idx.data_ptr(), pi_val.data_ptr(), z.data_ptr(), q.data_ptr(), mix.data_ptr(),
-                                                   row_stats.data_ptr(), g3.data_ptr(), dlogits.data_ptr(), dvalue.data_ptr(), _stream(logits)))
-        return dlogits, dvalue.view(ctx.value_shape), None, None, None, None, None
 
 
 def sparse_policy_value_loss_mix(logits, value, pi_idx, pi_val, z, q, mix):
@@ -151,7 +132,7 @@ def sparse_policy_value_loss_mix(logits, value, pi_idx, pi_val, z, q, mix):
     outside [0, 1] is not clamped, every loss is NaN."""
     if not isinstance(mix, torch.Tensor):
         mix = torch.tensor([float(mix)], dtype=torch.float32, device=logits.device)
-    loss5 = _SparseLossMix.apply(logits, value, pi_idx, pi_val, z.reshape(-1), q.reshape(-1), mix.reshape(-1))
+    loss5 = _SparseLoss.apply(logits, value, pi_idx, pi_val, z.reshape(-1), q.reshape(-1), mix.reshape(-1))
     return loss5[0], loss5[1], loss5[2], loss5[3].detach(), loss5[4].detach()
 
 

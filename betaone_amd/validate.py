@@ -32,8 +32,8 @@ import torch
 
 from . import engine as E
 from . import records as R
+from .train import batch_args, check_batch
 
-DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # BO_DTYPE_* of include/betaone_engine.h
 CURRENT_PIECE_PLANES = slice(98, 110)  # utils.encode_board: 8 history blocks of 12 piece + 2 repetition planes, the current position last
 CALIBRATION_BINS = 10
 _M64 = (1 << 64) - 1
@@ -131,26 +131,10 @@ class MetricsAccumulator:
     def add(self, logits, value, pi_idx, pi_val, z, q=None, bucket=None):
         """One batch: logits [n,4672] and value [n] or [n,1] (float32, float16 or bfloat16, each its own), pi_idx [n,W] int32,
         pi_val [n,W], z [n] or [n,1] and q (optional) float32, bucket (optional) [n] int32 -- all on the accumulator's device."""
-        n, W = pi_idx.shape
-        z = z.reshape(-1)
-        if logits.dim() != 2 or logits.shape != (n, E.NUM_ACTIONS) or value.numel() != n or pi_val.shape != (n, W) or z.numel() != n \
-                or (q is not None and q.numel() != n) or (bucket is not None and bucket.numel() != n):
-            raise ValueError(f"metrics: shapes logits {tuple(logits.shape)} value {tuple(value.shape)} pi_idx {tuple(pi_idx.shape)} "
-                             f"pi_val {tuple(pi_val.shape)} z {tuple(z.shape)}")
-        if logits.dtype not in DTYPE_CODES or value.dtype not in DTYPE_CODES:
-            raise TypeError(f"metrics: logits {logits.dtype} / value {value.dtype}: float32, float16 or bfloat16")
-        if pi_idx.dtype != torch.int32 or pi_val.dtype != torch.float32 or z.dtype != torch.float32 \
-                or (q is not None and q.dtype != torch.float32) or (bucket is not None and bucket.dtype != torch.int32):
-            raise TypeError("metrics: pi_idx and bucket int32, pi_val, z and q float32")
-        tensors = [t for t in (logits, value, pi_idx, pi_val, z, q, bucket) if t is not None]
-        if any(t.device != self.accum.device for t in tensors):
-            raise ValueError("metrics: all inputs on the accumulator's device")
-        logits, value, pi_idx, pi_val, z = logits.contiguous(), value.contiguous().reshape(-1), pi_idx.contiguous(), pi_val.contiguous(), z.contiguous()
-        q = q.contiguous().reshape(-1) if q is not None else None
-        bucket = bucket.contiguous().reshape(-1) if bucket is not None else None
-        rows = torch.empty((n, E.METRIC_ROW_COLS), dtype=torch.float32, device=self.accum.device)
-        rc = self.lib.bo_train_metrics(n, W, logits.data_ptr(), DTYPE_CODES[logits.dtype], value.data_ptr(), DTYPE_CODES[value.dtype],
-                                       pi_idx.data_ptr(), pi_val.data_ptr(), z.data_ptr(), q.data_ptr() if q is not None else None,
+        *batch, q, bucket = check_batch("metrics", logits, value, pi_idx, pi_val, z, (("q", q, torch.float32, None), ("bucket", bucket, torch.int32, None)),
+                                        device=self.accum.device, device_name="the accumulator's device")
+        rows = torch.empty((pi_idx.shape[0], E.METRIC_ROW_COLS), dtype=torch.float32, device=self.accum.device)
+        rc = self.lib.bo_train_metrics(*batch_args(*batch), q.data_ptr() if q is not None else None,
                                        bucket.data_ptr() if bucket is not None else None, self.n_buckets, rows.data_ptr(),
                                        self.accum.data_ptr(), _stream(logits))
         if rc != 0:

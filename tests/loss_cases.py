@@ -452,6 +452,60 @@ def check_nonfinite(case, pair, device):
         assert bool(torch.isnan(ref.dlogits[case.row]).all())
 
 
+def check_refusals(device):
+    """What the five bo_train_* entry points refuse, and in which words (the texts are written out here, not taken from the library's
+    source: "<entry>: bad arguments" and "<entry>: unsupported dtype").  With n = 2, W = 2 and float32 buffers that a call could run on:
+    every pointer that must not be null, null in turn; n = 0, W = 0, W = BO_RES_CAP + 1 and, for the metrics, n_buckets = 0 give
+    -1 (BO_E_ARG) and "<entry>: bad arguments"; the dtype code 7 for the logits or for the value gives -3 (BO_E_CONFIG) and
+    "<entry>: unsupported dtype"; a null pointer together with the code 7 gives -1.  q and bucket of bo_train_metrics and every stream
+    may be null (no root values, one bucket, the default stream): they are no refusals.  The unchanged arguments are accepted first
+    (0), so each refusal is the changed argument's.  Returns the number of refusals seen."""
+    from betaone_amd import engine as E
+
+    lib = E.load_hip_library()
+    n = W = 2
+
+    def buf(*shape, dtype=torch.float32):
+        return torch.zeros(shape, dtype=dtype, device=device)
+
+    logits, value, idx, val, z = buf(n, A), buf(n), buf(n, W, dtype=torch.int32), buf(n, W), buf(n)
+    q, mix, g3, stats, loss, dlogits, dvalue = buf(n), buf(1), buf(3), buf(n, 6), buf(5), buf(n, A), buf(n)
+    rows, accum, bucket = buf(n, E.METRIC_ROW_COLS), buf(1, E.METRIC_COLS, dtype=torch.float64), buf(n, dtype=torch.int32)
+    p = torch.Tensor.data_ptr
+    batch = [n, W, p(logits), 0, p(value), 0, p(idx), p(val), p(z)]   # arguments 0..8 of every entry point; 2, 4, 6, 7, 8 are pointers
+    entries = {   # the arguments from 9 on, and which of them are pointers that must not be null
+        "bo_train_loss_forward": ([p(stats), p(loss), None], (9, 10)),
+        "bo_train_loss_backward": ([p(stats), p(g3), p(dlogits), p(dvalue), None], (9, 10, 11, 12)),
+        "bo_train_loss_forward_mix": ([p(q), p(mix), p(stats), p(loss), None], (9, 10, 11, 12)),
+        "bo_train_loss_backward_mix": ([p(q), p(mix), p(stats), p(g3), p(dlogits), p(dvalue), None], (9, 10, 11, 12, 13, 14)),
+        "bo_train_metrics": ([p(q), p(bucket), 1, p(rows), p(accum), None], (12, 13)),
+    }
+    seen = 0
+    for entry, (rest, own) in entries.items():
+        fn, good = getattr(lib, entry), batch + rest
+
+        def refused(code, text, **changed):
+            args = list(good)
+            for k, v in changed.items():
+                args[int(k[1:])] = v
+            rc = fn(*args)
+            assert rc == code and lib.bo_last_error().decode() == f"{entry}: {text}", (entry, changed, rc, lib.bo_last_error())
+            return 1
+
+        assert fn(*good) == 0, (entry, lib.bo_last_error())
+        if torch.device(device).type == "cuda":
+            torch.cuda.synchronize()
+        for k in (2, 4, 6, 7, 8) + own:
+            seen += refused(-1, "bad arguments", **{f"a{k}": None})
+            seen += refused(-1, "bad arguments", **{f"a{k}": None}, a3=7)
+        seen += refused(-1, "bad arguments", a0=0) + refused(-1, "bad arguments", a1=0) + refused(-1, "bad arguments", a1=res_cap() + 1)
+        if entry == "bo_train_metrics":
+            seen += refused(-1, "bad arguments", a11=0) + refused(-1, "bad arguments", a11=0, a5=7)
+        seen += refused(-3, "unsupported dtype", a3=7) + refused(-3, "unsupported dtype", a5=7)
+        seen += refused(-1, "bad arguments", a0=0, a3=7, a5=7)
+    return seen
+
+
 # ---- the replay samplers at wide rows ------------------------------------------------------------------------------------------
 
 def res_cap() -> int:

@@ -215,6 +215,11 @@ def test_guard_rows_and_row_independence_under_the_emulator():
                 LC.check_row_independence(_by_name(name), pair, "cpu")
 
 
+def test_the_entry_points_refuse_bad_arguments_in_their_words_under_the_emulator():
+    with H.emulator_backend():
+        assert LC.check_refusals("cpu") > 0
+
+
 @pytest.fixture(scope="module")
 def fake_games():
     """Finished self-play games of FakeNet on the emulator, as in tests/test_train_emu.py."""

@@ -157,6 +157,10 @@ def test_loss_kernels_write_no_row_past_the_batch(name):
         LC.check_guard_rows(case, pair, DEV)
 
 
+def test_the_entry_points_refuse_bad_arguments_in_their_words():
+    assert LC.check_refusals(DEV) > 0
+
+
 @pytest.fixture(scope="module")
 def games():
     """Self-play games of a 10x128 net (CohortRollout, two cohorts), as FinishedGame objects."""

@@ -60,6 +60,14 @@ def test_invalid_mixes_give_nan_losses():
             VM.check_invalid_mix(_by_name("B63_W32_dom90_edges"), pair, "cpu")
 
 
+@pytest.mark.parametrize("name,mixes", VM.GUARD_CASES, ids=[c[0] for c in VM.GUARD_CASES])
+def test_mix_kernels_write_no_row_past_the_batch(name, mixes):
+    with H.emulator_backend():
+        for pair in ((F32, F32), (BF16, F32)):
+            for mix in mixes:
+                VM.check_guard_rows_mix(_by_name(name), pair, "cpu", mix)
+
+
 def test_bad_arguments_are_refused():
     from betaone_amd.train import sparse_policy_value_loss_mix
 

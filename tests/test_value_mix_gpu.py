@@ -52,6 +52,13 @@ def test_invalid_mixes_give_nan_losses(name):
         VM.check_invalid_mix(_by_name(name), pair, DEV)
 
 
+@pytest.mark.parametrize("name,mixes", VM.GUARD_CASES, ids=[c[0] for c in VM.GUARD_CASES])
+def test_mix_kernels_write_no_row_past_the_batch(name, mixes):
+    for pair in LC.PAIRS if len(mixes) > 1 else ((F16, F16),):   # (every dtype pair on the case that also runs mix 0)
+        for mix in mixes:
+            VM.check_guard_rows_mix(_by_name(name), pair, DEV, mix)
+
+
 def test_the_mix_is_read_on_the_device_when_the_kernels_run():
     """One device tensor, changed in place between calls (what a schedule does under a captured step): each call sees its value."""
     case = _by_name("B65_W2_dom60_first_full")

@@ -305,6 +305,72 @@ def check_loss_case(case, pair, device, mixes=MIXES, again=False):
         assert near_x + near_v < LC.NEAR_SHARE * (ref.dlogits.numel() + ref.dvalue.numel()), f"{what}: elements at the overflow threshold"
 
 
+# ---- the raw calls on guarded buffers ------------------------------------------------------------------------------------------------
+
+ROW_STATS_MIX = 6
+GUARD_CASES = (("B1_W1_randn3_prefix", (0.5,)), ("B65_W2_dom60_first_full", (0.5, 0.0)), ("B65_W63_dom90_last_empty_rows", (0.5,)))
+
+
+def raw_forward_backward_mix(logits, value, idx, val, z, q, mix, w3, guard=64):
+    """bo_train_loss_forward_mix / bo_train_loss_backward_mix called directly, with row_stats [n + guard, 6], dlogits and dvalue
+    allocated `guard` rows longer than the batch and pre-filled with the NaN payload (LC.raw_forward_backward for the mix entry
+    points).  Returns (row_stats, loss5, dlogits, dvalue), the three with their guard rows."""
+    from betaone_amd import engine as E
+    from betaone_amd.train import DTYPE_CODES
+
+    lib = E.load_hip_library()
+    dev = logits.device
+    stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+    n, W = idx.shape
+    logits, value, z, q = logits.contiguous(), value.contiguous().reshape(-1), z.contiguous().reshape(-1), q.contiguous().reshape(-1)
+    row_stats = LC.guarded(n, ROW_STATS_MIX, F32, dev, guard)
+    dlogits, dvalue = LC.guarded(n, LC.A, logits.dtype, dev, guard), LC.guarded(n, 1, value.dtype, dev, guard)
+    loss5 = torch.empty(5, dtype=F32, device=dev)
+    g3, m = torch.tensor(w3, dtype=F32, device=dev), torch.tensor([mix], dtype=F32, device=dev)
+    args = (n, W, logits.data_ptr(), DTYPE_CODES[logits.dtype], value.data_ptr(), DTYPE_CODES[value.dtype], idx.data_ptr(), val.data_ptr(),
+            z.data_ptr(), q.data_ptr(), m.data_ptr(), row_stats.data_ptr())
+    rc = lib.bo_train_loss_forward_mix(*args, loss5.data_ptr(), stream)
+    assert rc == 0, lib.bo_last_error().decode()
+    rc = lib.bo_train_loss_backward_mix(*args, g3.data_ptr(), dlogits.data_ptr(), dvalue.data_ptr(), stream)
+    assert rc == 0, lib.bo_last_error().decode()
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+    return row_stats, loss5, dlogits, dvalue
+
+
+def check_guard_rows_mix(case, pair, device, mix):
+    """LC.check_guard_rows for the mix entry points: the guard rows keep their pattern, no payload is left below row B in any of the
+    six columns of row_stats (a stride of 4 leaves some and runs short; a stride of 6 in the plain kernels would write past them) nor in
+    dlogits and dvalue, and the results are reference64_mix's.  The row terms: the policy term within LC's envelope; the three value
+    terms d^2 with d = v - t, v - z, v - q within FACTOR allowances of eps (4 d^2 + 4 |d| T) + 2^-126 -- 4 eps d^2 is LC's allowance for
+    (v - z)^2, and the target's own error of 2 eps T (dvalue_envelope, module docstring; T = 0 for a target that is given) reaches d^2
+    times 2 |d|.  The losses and the gradients by the conditions of check_loss_case; the three cases' w3 have no scale."""
+    t = LC.cast(case, pair, device)
+    q = root_values_for(case).to(device)
+    assert weights_for(case, pair) == case.w3
+    row_stats, loss5, dlogits, dvalue = raw_forward_backward_mix(*t, q, mix, case.w3)
+    B = case.B
+    what = f"{case.name} {LC.short(pair[0])}/{LC.short(pair[1])} mix {mix} guard rows"
+    assert tuple(row_stats.shape) == (B + 64, ROW_STATS_MIX)
+    for name, buf in (("row_stats", row_stats), ("dlogits", dlogits), ("dvalue", dvalue)):
+        assert LC.guard_intact(buf, B), f"{what}: {name} written past row {B}"
+        bits = buf[:B].view(torch.int32) if buf.dtype == F32 else buf[:B].view(torch.int16)
+        left = bits == (LC.NAN32 if buf.dtype == F32 else LC.NAN16)
+        assert not bool(left.any()), f"{what}: {name} has unwritten elements in columns {sorted(set(torch.nonzero(left)[:, 1].tolist()))[:8]}"
+    base = LC.reference64(*t, case.w3)
+    env = LC.envelope(base)
+    ref = reference64_mix(base, t[1], t[4], q, mix)
+    LC.check_output(row_stats[:B, 2], base.row_policy, env.row_policy, what + " row policy terms")
+    v, zz, qq = (x.detach().cpu().double().reshape(-1) for x in (t[1], t[4], q))
+    for col, target, T in ((3, ref.t, ref.T), (4, zz, 0.0), (5, qq, 0.0)):
+        d = v - target
+        LC.check_output(row_stats[:B, col], d * d, LC.EPS * (4.0 * d * d + 4.0 * d.abs() * T) + LC.TINY, f"{what} row value terms, column {col}")
+    check_losses(loss5, ref.loss5, what)
+    near = (check_gradient(dlogits[:B], ref.dlogits, env.dlogits, what + " dlogits")
+            + check_gradient(dvalue[:B].reshape(-1), ref.dvalue, None, what + " dvalue"))
+    assert near < LC.NEAR_SHARE * (ref.dlogits.numel() + ref.dvalue.numel()), f"{what}: {near} elements at the overflow threshold"
+
+
 # ---- mix 0, invalid mixes, the point of view ---------------------------------------------------------------------------------------
 
 def hard_inputs(case, device, pair):
