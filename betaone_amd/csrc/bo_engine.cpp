@@ -16,6 +16,7 @@
 #include "bo_analyse.h"
 #include "bo_reanalyse.h"
 #include "bo_perft.h"
+#include "bo_mate.h"
 #include "bo_book.h"
 #include "bo_merge.h"
 #include "bo_tb.h"
@@ -3263,6 +3264,339 @@ extern "C" int bo_perft(int device, int32_t n_roots, const char *const *fens, in
             }
         }
     }
+    if (n_splits) *n_splits = R.splits;
+    return BO_OK;
+}
+
+// ---- forced mates on the device (bo_mate.h) ----------------------------------------------------------------------------------------
+// The walk is perft's: a frontier per level, PerftRun's buffers, scan and split.  Each level also keeps one value byte per entry, an
+// attacker level (even) the live masks of its entries; after a chunk of level l + 1 has been taken to the bottom, its values are backed
+// up into the parents of level l that the chunk was expanded from.
+namespace {
+struct MateRoot {
+    int32_t dtm = 0, searched = 0, n_moves = 0, n_keys = 0, key = -1, chk = 0;
+    uint64_t mask[4] = {0, 0, 0, 0};
+};
+struct MateRun : PerftRun {
+    std::vector<uint8_t *> val;    // per level [have_val]
+    std::vector<uint64_t *> live;  // per attacker level [have_val][4]
+    std::vector<int64_t> have_val;
+    // per root of the current solve [have_roots]: the roots, check bits, active -> root, key mask [4], keys, lowest key
+    DPos *d_roots = nullptr;
+    int32_t *root_chk = nullptr, *act = nullptr, *n_keys = nullptr, *key = nullptr;
+    uint64_t *keymask = nullptr;
+    int64_t have_roots = 0;
+    uint64_t visited = 0;  // frontier entries of every level of every walk (include/betaone_engine.h: nodes)
+    ~MateRun() {
+        (void)rt_sync(stream);
+        for (uint8_t *p : val) rt_free(p);
+        for (uint64_t *p : live) rt_free(p);
+        rt_free(d_roots); rt_free(root_chk); rt_free(act); rt_free(n_keys); rt_free(key); rt_free(keymask);
+    }
+    void levels(size_t k) {
+        if (lv.size() >= k) return;
+        lv.resize(k); val.resize(k, nullptr); live.resize(k, nullptr); have_val.resize(k, 0);
+    }
+    int room_mate(int l, int64_t n) {
+        int rc = room(l, n);
+        if (!rc) rc = room_scan(l, n);
+        const int64_t m = lv[l].have;
+        if (rc || have_val[l] >= m) return rc;
+        rt_free(val[l]); rt_free(live[l]);
+        val[l] = nullptr; live[l] = nullptr; have_val[l] = 0;
+        rc = rt_malloc((void **)&val[l], (size_t)m);
+        if (!rc && !(l & 1)) rc = rt_malloc((void **)&live[l], (size_t)m * 32);
+        if (!rc) have_val[l] = m;
+        return rc;
+    }
+    int room_roots(int64_t n) {
+        if (have_roots >= n) return 0;
+        rt_free(d_roots); rt_free(root_moves); rt_free(root_n); rt_free(root_chk); rt_free(act); rt_free(n_keys); rt_free(key); rt_free(keymask);
+        d_roots = nullptr; root_moves = root_n = root_chk = act = n_keys = key = nullptr; keymask = nullptr; have_roots = 0;
+        const size_t N = (size_t)n;
+        int rc = rt_malloc((void **)&d_roots, N * sizeof(DPos));
+        if (!rc) rc = rt_malloc((void **)&root_moves, N * BO_MAX_MOVES * 4);
+        if (!rc) rc = rt_malloc((void **)&root_n, N * 4);
+        if (!rc) rc = rt_malloc((void **)&root_chk, N * 4);
+        if (!rc) rc = rt_malloc((void **)&act, N * 4);
+        if (!rc) rc = rt_malloc((void **)&n_keys, N * 4);
+        if (!rc) rc = rt_malloc((void **)&key, N * 4);
+        if (!rc) rc = rt_malloc((void **)&keymask, N * 32);
+        if (!rc) have_roots = n;
+        return rc;
+    }
+    int scan(int l, int64_t n) {  // cnt -> off of level l, the total into h_word[0]
+        PerftLevel &L = lv[l];
+        const int nt = (int)((n + BO_PERFT_TILE - 1) / BO_PERFT_TILE);
+        RT(RT_LAUNCH(bo_k_perft_tile_sums, nt, stream, (const int32_t *)L.cnt, n, tsum));
+        RT(RT_LAUNCH(bo_k_perft_tile_scan, 1, stream, (const int32_t *)tsum, nt, tbase, L.off, n));
+        RT(RT_LAUNCH(bo_k_perft_offsets, nt, stream, (const int32_t *)L.cnt, n, (const uint64_t *)tbase, L.off));
+        RT(rt_d2h(h_word, L.off + n, 8, stream));
+        RT(rt_sync(stream));
+        return BO_OK;
+    }
+};
+
+int mate_backup(MateRun &R, int l, int64_t a, int64_t e) {
+    PerftLevel &L = R.lv[l];
+    const uint8_t *below = l + 1 < (int)R.lv.size() ? R.val[l + 1] : nullptr;  // (read only by parents that have children)
+    if (l == 0)
+        RT(RT_LAUNCH(bo_k_mate_backup_root, e - a, R.stream, (const int32_t *)L.cnt, (const uint64_t *)L.off, a, below, R.val[0],
+                     (const uint64_t *)R.live[0], R.keymask, (const int32_t *)R.act, (const int32_t *)R.root_moves, R.n_keys, R.key));
+    else
+        RT(RT_LAUNCH(bo_k_mate_backup, e - a, R.stream, (const int32_t *)L.cnt, (const uint64_t *)L.off, a, below, R.val[l], (uint32_t)!(l & 1)));
+    return BO_OK;
+}
+
+// the values of entries [0, n) of level l (R.room_mate(l, n) has been called)
+int mate_level(MateRun &R, int l, int64_t n) {
+    PerftLevel &L = R.lv[l];
+    const bool attacker = !(l & 1), last = l == R.depth - 1;
+    R.visited += (uint64_t)n;
+    if (attacker)
+        RT(RT_LAUNCH(bo_k_mate_attack, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], R.live[l], l == 0 ? R.keymask : (uint64_t *)nullptr,
+                     (last ? MT_LAST : 0u) | (l == 0 ? MT_ROOT : 0u)));
+    else
+        RT(RT_LAUNCH(bo_k_perft_count, n, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (int64_t)0, L.cnt, (uint64_t *)nullptr,
+                     (uint64_t *)nullptr, 0u));
+    if (last) return l == 0 ? mate_backup(R, 0, 0, n) : BO_OK;  // (every count is 0: no offsets are read)
+    int rc = R.scan(l, n);
+    if (rc) return rc;
+    int64_t left = R.h_word[0], a = 0;
+    while (a < n && left > 0) {
+        int64_t e = n, c = left;
+        if (left > R.cap) {
+            RT(RT_LAUNCH(bo_k_perft_split, 1, R.stream, (const uint64_t *)L.off, a, n, R.cap, R.d_word));
+            RT(rt_d2h(R.h_word, R.d_word, 16, R.stream));
+            RT(rt_sync(R.stream));
+            e = R.h_word[0];
+            c = R.h_word[1];
+            if (e <= a || e > n || c < 1 || c > R.cap) return fail(BO_E_STATE, "bo_mate: the level split is inconsistent");
+            if (c < left) R.splits++;
+        }
+        RT(R.room_mate(l + 1, c));
+        PerftLevel &C = R.lv[l + 1];
+        if (attacker)
+            RT(RT_LAUNCH(bo_k_mate_expand, e - a, R.stream, (const DPos *)L.pos, (const uint64_t *)L.off, (const uint64_t *)R.live[l], a, C.pos, C.tag,
+                         C.have));
+        else
+            RT(RT_LAUNCH(bo_k_perft_expand, e - a, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (const uint64_t *)L.off, a, C.pos, C.tag,
+                         C.have, 0u));
+        rc = mate_level(R, l + 1, c);
+        if (!rc) rc = mate_backup(R, l, a, e);
+        if (rc) return rc;
+        left -= c;
+        a = e;
+    }
+    if (l == 0 && a < n) return mate_backup(R, 0, a, n);  // roots behind the last child: mates in 1 and roots without a live move
+    return BO_OK;
+}
+
+// Iterative deepening over `roots` (finished in place: key fields as bo_k_perft_roots leaves them): n = 1 .. N over the roots still
+// unresolved.  moves [n][256] = the roots' move lists.
+int mate_solve(MateRun &R, std::vector<DPos> &roots, int N, uint64_t max_nodes, std::vector<MateRoot> &out, std::vector<int32_t> &moves) {
+    const size_t n = roots.size();
+    out.assign(n, MateRoot());
+    moves.assign(n * BO_MAX_MOVES, -1);
+    if (!n) return BO_OK;
+    RT(R.room_roots((int64_t)n));
+    std::vector<int32_t> rn(n), chk(n);
+    RT(rt_h2d(R.d_roots, roots.data(), n * sizeof(DPos), R.stream));
+    RT(RT_LAUNCH(bo_k_mate_roots, n, R.stream, R.d_roots, R.root_moves, R.root_n, R.root_chk));
+    RT(rt_d2h(roots.data(), R.d_roots, n * sizeof(DPos), R.stream));
+    RT(rt_d2h(moves.data(), R.root_moves, moves.size() * 4, R.stream));
+    RT(rt_d2h(rn.data(), R.root_n, n * 4, R.stream));
+    RT(rt_d2h(chk.data(), R.root_chk, n * 4, R.stream));
+    RT(rt_sync(R.stream));
+    std::vector<int32_t> active;
+    for (size_t r = 0; r < n; r++) {
+        out[r].n_moves = rn[r];
+        out[r].chk = chk[r];
+        if (!(chk[r] & 2) && rn[r] > 0) active.push_back((int32_t)r);
+    }
+    std::vector<DPos> sub;
+    std::vector<uint8_t> v;
+    std::vector<int32_t> nk, ky;
+    std::vector<uint64_t> km;
+    for (int it = 1; it <= N && !active.empty(); it++) {
+        if (max_nodes && R.visited > max_nodes) break;
+        const size_t na = active.size();
+        R.depth = 2 * it - 1;
+        R.levels((size_t)R.depth);
+        RT(R.room_mate(0, (int64_t)na));
+        sub.resize(na);
+        for (size_t i = 0; i < na; i++) sub[i] = roots[(size_t)active[i]];
+        RT(rt_h2d(R.lv[0].pos, sub.data(), na * sizeof(DPos), R.stream));
+        RT(rt_h2d(R.act, active.data(), na * 4, R.stream));
+        RT(rt_sync(R.stream));
+        const int rc = mate_level(R, 0, (int64_t)na);
+        if (rc) return rc;
+        v.resize(na); nk.resize(na); ky.resize(na); km.resize(na * 4);
+        RT(rt_d2h(v.data(), R.val[0], na, R.stream));
+        RT(rt_d2h(nk.data(), R.n_keys, na * 4, R.stream));
+        RT(rt_d2h(ky.data(), R.key, na * 4, R.stream));
+        RT(rt_d2h(km.data(), R.keymask, na * 32, R.stream));
+        RT(rt_sync(R.stream));
+        std::vector<int32_t> next;
+        for (size_t i = 0; i < na; i++) {
+            MateRoot &o = out[(size_t)active[i]];
+            o.searched = it;
+            if (!v[i]) { next.push_back(active[i]); continue; }
+            if (v[i] != 2 * it - 1) return fail(BO_E_STATE, "bo_mate: a root resolved at another depth than the iteration's");
+            o.dtm = v[i]; o.n_keys = nk[i]; o.key = ky[i];
+            for (int w = 0; w < 4; w++) o.mask[w] = km[i * 4 + w];
+        }
+        active.swap(next);
+    }
+    return BO_OK;
+}
+
+// The principal variation of every solved root: pv [n][W].  Along the line the attacker's move is known (the lowest-index key); the
+// defender's replies of all unfinished lines become one batch of roots, solved at the remaining distance.
+int mate_pv(MateRun &R, const std::vector<DPos> &roots, const std::vector<MateRoot> &out, const std::vector<int32_t> &index, int W, int32_t *pv) {
+    struct Line { size_t row; DPos A; int32_t key; int d, ply; };
+    std::vector<Line> lines;
+    for (size_t r = 0; r < roots.size(); r++)
+        if (out[r].dtm > 0) {
+            lines.push_back(Line{(size_t)index[r], roots[r], out[r].key, out[r].dtm, 0});
+            pv[(size_t)index[r] * W] = out[r].key;
+        }
+    for (;;) {
+        std::vector<size_t> S;
+        for (size_t i = 0; i < lines.size(); i++)
+            if (lines[i].d > 1) S.push_back(i);
+        if (S.empty()) return BO_OK;
+        const size_t ns = S.size();
+        std::vector<DPos> A(ns);
+        std::vector<int32_t> keys(ns);
+        int nsub = 1;
+        for (size_t j = 0; j < ns; j++) { A[j] = lines[S[j]].A; keys[j] = lines[S[j]].key; nsub = std::max(nsub, (lines[S[j]].d - 1) / 2); }
+        R.levels(2);
+        RT(R.room_roots((int64_t)ns));
+        RT(R.room_mate(0, (int64_t)ns));
+        PerftLevel &L = R.lv[0];
+        RT(rt_h2d(L.pos, A.data(), ns * sizeof(DPos), R.stream));
+        RT(rt_h2d(R.key, keys.data(), ns * 4, R.stream));
+        RT(RT_LAUNCH(bo_k_mate_play, (ns + 63) / 64, R.stream, (const DPos *)L.pos, (const int32_t *)R.key, (int64_t)ns, L.pos, L.tag));
+        RT(RT_LAUNCH(bo_k_mate_roots, ns, R.stream, L.pos, R.root_moves, R.root_n, R.root_chk));  // the replies' words
+        RT(RT_LAUNCH(bo_k_perft_count, ns, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (int64_t)0, L.cnt, (uint64_t *)nullptr,
+                     (uint64_t *)nullptr, 0u));
+        int rc = R.scan(0, (int64_t)ns);
+        if (rc) return rc;
+        const int64_t T = R.h_word[0];
+        if (T < (int64_t)ns) return fail(BO_E_STATE, "bo_mate: a defender on a mating line has no reply");
+        RT(R.room(1, T));
+        RT(RT_LAUNCH(bo_k_perft_expand, ns, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (const uint64_t *)L.off, (int64_t)0, R.lv[1].pos,
+                     R.lv[1].tag, R.lv[1].have, 0u));
+        std::vector<DPos> B((size_t)T);
+        std::vector<uint64_t> off(ns + 1);
+        std::vector<int32_t> words(ns * BO_MAX_MOVES);
+        RT(rt_d2h(B.data(), R.lv[1].pos, (size_t)T * sizeof(DPos), R.stream));
+        RT(rt_d2h(off.data(), L.off, (ns + 1) * 8, R.stream));
+        RT(rt_d2h(words.data(), R.root_moves, words.size() * 4, R.stream));
+        RT(rt_sync(R.stream));
+        std::vector<MateRoot> ob;
+        std::vector<int32_t> mb;
+        rc = mate_solve(R, B, nsub, 0, ob, mb);
+        if (rc) return rc;
+        for (size_t j = 0; j < ns; j++) {
+            Line &ln = lines[S[j]];
+            int64_t best = -1;
+            bool open = false;  // a reply that is not mated within the distance
+            for (int64_t k = (int64_t)off[j]; k < (int64_t)off[j + 1]; k++) {
+                open = open || ob[(size_t)k].dtm == 0;
+                if (best < 0 || ob[(size_t)k].dtm > ob[(size_t)best].dtm) best = k;
+            }
+            if (best < 0 || open || ob[(size_t)best].dtm != ln.d - 2) return fail(BO_E_STATE, "bo_mate: the line's replies do not add up to the root's distance");
+            int32_t *row = pv + ln.row * (size_t)W + ln.ply;
+            row[1] = words[j * BO_MAX_MOVES + (size_t)(best - (int64_t)off[j])];
+            row[2] = ob[(size_t)best].key;
+            ln.A = B[(size_t)best]; ln.key = ob[(size_t)best].key; ln.d -= 2; ln.ply += 2;
+        }
+    }
+}
+
+// what the generator's 256-move lists and its king lookups need of a position (include/betaone_engine.h: "not a position")
+bool mate_position_ok(const DPos &p) {
+    uint64_t all = 0;
+    for (int i = 0; i < 6; i++) {
+        if (all & p.bb[i]) return false;
+        all |= p.bb[i];
+    }
+    if ((p.bb[BB_WHITE] & p.bb[BB_BLACK]) || (p.bb[BB_WHITE] | p.bb[BB_BLACK]) != all) return false;
+    if (p.bb[BB_P] & (RANK_1 | RANK_8)) return false;
+    for (int c = 0; c < 2; c++) {
+        const uint64_t own = p.bb[c ? BB_BLACK : BB_WHITE];
+        auto cnt = [&](int t) { return __builtin_popcountll(p.bb[t] & own); };
+        if (cnt(BB_K) != 1 || __builtin_popcountll(own) > 16 || cnt(BB_P) > 8) return false;
+        const int extra = std::max(0, cnt(BB_N) - 2) + std::max(0, cnt(BB_B) - 2) + std::max(0, cnt(BB_R) - 2) + std::max(0, cnt(BB_Q) - 1);
+        if (extra > 8 - cnt(BB_P)) return false;
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int bo_mate(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t max_moves, int64_t capacity,
+                       uint64_t max_nodes, uint32_t flags, bo_mate_result *results, int32_t *key_moves, int32_t *pv, int64_t *n_splits, void *stream) {
+    if (n_splits) *n_splits = 0;
+    if (n_roots < 0 || n_roots > (1 << 20) || (fens != nullptr) == (positions != nullptr))
+        return fail(BO_E_ARG, "bo_mate: exactly one of fens and positions, n_roots <= 2^20");
+    if (max_moves < 1 || max_moves > BO_MATE_MAX_MOVES) return fail(BO_E_ARG, "bo_mate: max_moves must be 1 .. 16");
+    if (capacity < BO_MAX_MOVES || capacity > ((int64_t)1 << 26))
+        return fail(BO_E_CONFIG, "bo_mate: capacity must be 256 (the children of one position) .. 2^26 positions per level");
+    if (flags & ~(uint32_t)BO_MATE_PV) return fail(BO_E_ARG, "bo_mate: unknown flag bits");
+    if (n_roots && (!results || ((flags & BO_MATE_PV) && !pv))) return fail(BO_E_ARG, "bo_mate: results (and pv with BO_MATE_PV) must be given");
+    if (n_roots == 0) return BO_OK;
+    const size_t N = (size_t)n_roots;
+    const int W = 2 * max_moves - 1;
+    std::vector<DPos> roots;       // the roots that are positions
+    std::vector<int32_t> index;    // their rows in the caller's arrays
+    roots.reserve(N); index.reserve(N);
+    memset(results, 0, N * sizeof(bo_mate_result));
+    for (size_t i = 0; i < N; i++) {
+        DPos p;
+        results[i].key = -1;
+        if (fens) {
+            if (!pgn_fen_root(fens[i] ? fens[i] : "", &p) || !mate_position_ok(p)) return fail(BO_E_FEN, "bo_mate: bad FEN (root " + std::to_string(i) + ")");
+        } else {
+            const bo_position &q = positions[i];
+            const bool fields = (q.turn == 0 || q.turn == 1) && q.castling <= 0xFu && q.ep_square >= -1 && q.ep_square <= 63 && q.ep_key >= -2 && q.ep_key <= 63;
+            if (fields) p = from_abi(q);
+            if (!fields || !mate_position_ok(p)) { results[i].status = BO_MATE_NOT_A_POSITION; continue; }
+        }
+        roots.push_back(p);
+        index.push_back((int32_t)i);
+    }
+    if (key_moves)
+        for (size_t i = 0; i < N * BO_MAX_MOVES; i++) key_moves[i] = -1;
+    if (flags & BO_MATE_PV)
+        for (size_t i = 0; i < N * (size_t)W; i++) pv[i] = -1;
+    if (roots.empty()) return BO_OK;
+    RT(rt_set_device(device));
+    MateRun R;
+    R.stream = stream; R.cap = capacity;
+    RT(rt_malloc((void **)&R.d_word, 16));
+    RT(rt_host_alloc((void **)&R.h_word, 16));
+    std::vector<MateRoot> out;
+    std::vector<int32_t> moves;
+    int rc = mate_solve(R, roots, max_moves, max_nodes, out, moves);
+    if (!rc && (flags & BO_MATE_PV)) rc = mate_pv(R, roots, out, index, W, pv);
+    if (rc) return rc;
+    for (size_t r = 0; r < roots.size(); r++) {
+        const size_t i = (size_t)index[r];
+        bo_mate_result &o = results[i];
+        const MateRoot &m = out[r];
+        o.n_moves = m.n_moves;
+        if (m.chk & 2) { o.status = BO_MATE_NOT_A_POSITION; o.n_moves = 0; continue; }
+        if (m.n_moves == 0) { o.status = (m.chk & 1) ? BO_MATE_CHECKMATED : BO_MATE_STALEMATED; continue; }
+        o.dtm = m.dtm; o.searched = m.searched; o.n_keys = m.n_keys; o.key = m.key;
+        if (key_moves && m.dtm) {
+            int k = 0;
+            for (int j = 0; j < BO_MAX_MOVES; j++)
+                if (m.mask[j >> 6] >> (j & 63) & 1) key_moves[i * BO_MAX_MOVES + (size_t)k++] = moves[r * BO_MAX_MOVES + (size_t)j];
+        }
+    }
+    for (size_t i = 0; i < N; i++) results[i].nodes = R.visited;
     if (n_splits) *n_splits = R.splits;
     return BO_OK;
 }

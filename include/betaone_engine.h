@@ -37,10 +37,11 @@ extern "C" {
  * 14: endgame tablebases inside the search and at the root -- bo_engine_tablebases, bo_engine_tb_stats, bo_debug_tree's terminal codes
  * 3 / 4 / 5, bo_root_info's terminal code 3 -- additions only; 15: reanalysis of self-play records -- bo_records_ring,
  * bo_reanalysis_result, status bit BO_ST_PI_OVERFLOW -- additions only; 16: opening books -- bo_book_insert -- addition only;
- * 18: board symmetries in the replay samplers -- bo_replay_sample_sym, _sparse_sym, _sparse_q_sym, _merged_sym -- additions only).
+ * 18: board symmetries in the replay samplers -- bo_replay_sample_sym, _sparse_sym, _sparse_q_sym, _merged_sym -- additions only;
+ * 19: forced mates on the device -- bo_mate, bo_mate_result -- additions only).
  * A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 18
+#define BO_ABI_VERSION 19
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -970,6 +971,49 @@ void bo_tb_destroy(bo_tb *tb);
  *   set-up, and 1 where the game's CURRENT root was adjudicated (terminal 2 or 3 from the tables, not from the rules).  Synchronises. */
 int bo_engine_tablebases(bo_engine *e, bo_tb *const *tbs, int32_t n_tb, int32_t flags);
 int bo_engine_tb_stats(bo_engine *e, int32_t *tb_nodes, int32_t *tb_sims, int32_t *adjudicated, void *stream);
+
+/* ---- (ABI 19, additions) forced mates on the device: csrc/bo_mate.h, betaone_amd/mate.py ---------------------------------------------
+ * Is there a forced mate in at most max_moves moves for the root's side to move (the attacker), in how many plies, and by which first
+ * moves?  dtm = plies to mate with best play by both sides (odd for the attacker; mate in m moves = dtm 2 m - 1), 0 = none within the
+ * budget.  Draw rules are IGNORED, as in perft and the tablebases: only a position without legal moves ends a line.  A search for mate
+ * in at most n moves is a full-width walk to depth 2 n - 1 over perft's frontier with an AND/OR backup.  Engine-less; SYNCHRONISES
+ * `stream` and allocates and frees its own device memory, as bo_perft does.
+ *
+ * Roots: EITHER fens [n_roots] (NULL entries = the start position; a FEN that does not parse or is not a position: BO_E_FEN, as for
+ * bo_perft) OR positions [n_roots] (HOST memory, as bo_tb_probe takes them; a record that is not a position gets status
+ * BO_MATE_NOT_A_POSITION and is not searched).  Not a position: not exactly one king per side, overlapping or inconsistent bitboards,
+ * pawns on the first or last rank, more than 16 men or more promoted pieces than missing pawns on a side (the move list has room for
+ * 256 moves), and -- seen by the device -- the side NOT to move in check.  n_roots <= 2^20; n_roots == 0 does nothing.
+ * max_moves N: 1 .. 16.  capacity: as for bo_perft (256 .. 2^26 positions per level buffer, BO_E_CONFIG otherwise; the results do not
+ * depend on it, *n_splits counts the extra chunks).
+ * The driver deepens iteratively: n = 1, 2, ..., N over the roots still unresolved; a root resolved at iteration n has dtm = 2 n - 1
+ * exactly and drops out.  max_nodes (0 = unlimited): before an iteration starts, if the nodes counted so far exceed it, the call stops;
+ * results[r].searched = the largest n completed for that root.
+ * nodes: the positions the walks of this call visited -- the frontier entries of every level of every iteration, the roots included,
+ * each of which had its move list generated by the level's count kernel; the passes of BO_MATE_PV count too (and are not bounded by
+ * max_nodes).  It is the number of the WHOLE call, the same in every result.  (Not counted: the child lists an attacker entry generates
+ * to classify its moves, and the regeneration in the expand kernels.)
+ * key_moves (may be NULL) [n_roots][BO_MAX_LEGAL]: the root moves that begin a shortest mate, in generated order, -1 beyond n_keys.
+ * flags: BO_MATE_PV fills pv [n_roots][2 N - 1] (needed then), -1 beyond dtm: the attacker plays the lowest-index key move, the
+ * defender the reply of longest resistance (lowest index on ties).  It is computed by solving again along the line -- the defender's
+ * replies of all solved roots become one batch of roots at n - 1, N - 1 further passes -- and MAY COST AS MUCH AS THE SOLVE.
+ * Arguments are checked in this order, before any device call: n_roots out of range or both / neither of fens and positions
+ * (BO_E_ARG); max_moves out of range (BO_E_ARG); capacity (BO_E_CONFIG); unknown flag bits (BO_E_ARG); results NULL with n_roots > 0,
+ * or BO_MATE_PV without pv (BO_E_ARG). */
+enum { BO_MATE_PV = 1 };
+enum { BO_MATE_OK = 0, BO_MATE_CHECKMATED = 1, BO_MATE_STALEMATED = 2, BO_MATE_NOT_A_POSITION = 3 };
+#define BO_MATE_MAX_MOVES 16
+typedef struct bo_mate_result {
+    int32_t status;               /* BO_MATE_*: ok; the root's side to move is checkmated / stalemated; not a position */
+    int32_t dtm;                  /* plies to mate, 0 = none found within `searched` moves */
+    int32_t searched;             /* the largest n completed for this root (a resolved root: its mate distance in moves) */
+    int32_t n_moves;              /* legal moves of the root */
+    int32_t n_keys;               /* root moves that begin a shortest mate */
+    int32_t key;                  /* the lowest-index one (from | to << 6 | promo << 12), -1 none */
+    uint64_t nodes;               /* of the whole call, see above */
+} bo_mate_result;
+int bo_mate(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t max_moves, int64_t capacity,
+            uint64_t max_nodes, uint32_t flags, bo_mate_result *results, int32_t *key_moves, int32_t *pv, int64_t *n_splits, void *stream);
 
 #ifdef __cplusplus
 }
