@@ -32,6 +32,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -95,11 +96,13 @@ F16_TILE_DEFAULT = {128: "16", 256: "32"}
 
 
 def split_scale(w: torch.Tensor) -> float:
-    """The power of two s that puts the largest |s*w| in [2^14, 2^15) (BO_TOWER_SPLIT_F16: fp16 pairs of s*w)."""
+    """The power of two s that puts the largest |s*w| in [2^14, 2^15) (BO_TOWER_SPLIT_F16: fp16 pairs of s*w).  s <= 2^126: the
+    kernels multiply by 1 / s in float32, which has to be a normal number there (a layer whose largest |w| is below 2^-112 -- a
+    float32 denormal, say -- got s up to 2^163 and an inverse of 0; it now keeps s = 2^126 and fewer bits in its lo halves)."""
     m = float(w.abs().max())
     if m == 0.0 or not np.isfinite(m):
         return 1.0
-    return float(2.0 ** (14 - int(np.floor(np.log2(m)))))
+    return float(2.0 ** min(126, 15 - math.frexp(m)[1]))  # frexp: m = f * 2^e with 0.5 <= f < 1, so floor(log2 m) = e - 1, exactly
 
 
 def split_f16(w: torch.Tensor):
@@ -117,6 +120,15 @@ def pack_conv_weight_split(w: torch.Tensor, scale: float) -> torch.Tensor:
     hi, lo = split_f16(w.double() * scale)
     u = torch.stack([hi, lo], 0).reshape(2, co // 32, 32, ci // 16, 2, 8, 9)  # [hl][mt][o][cg][kg][i][tap]
     return u.permute(6, 3, 1, 0, 4, 2, 5).contiguous()  # [tap][cg][mt][hl][kg][o][i]
+
+
+def pack_head_weight_split(wh: torch.Tensor, scale: float) -> torch.Tensor:
+    """[32*mt_n, c] float32 (the joint 1x1 head convolution, rows padded with zeros to whole 32-channel tiles) -> fp16
+    [mt_n][c/16][2 = hi, lo][64][8] of scale*wh (bo_k_tower_s / bo_k_tower_s16, the head loop): element (mt, st, hl, lane, i) =
+    split(scale * Wh[32*mt + (lane & 31)][16*st + 8*(lane >> 5) + i])."""
+    mt, c = wh.shape[0] // 32, wh.shape[1]
+    hi, lo = split_f16(wh.double() * scale)
+    return torch.stack([hi, lo], 0).reshape(2, mt, 32, c // 16, 2, 8).permute(1, 3, 0, 4, 2, 5).contiguous()  # [mt][st][hl][kg][o][i]
 
 
 SPLIT_TILE_DEFAULT = "16"  # which MFMA tile conv='tower_split' multiplies with at 128 filters ("16": csrc/bo_tower_s16.h); BETAONE_SPLIT_TILE overrides
@@ -385,8 +397,7 @@ class FusedPolicyValueNet(nn.Module):
         wh = torch.zeros((mt * 32, c))
         wh[:self._head_ch] = self.w_head.detach().float().cpu().reshape(self._head_ch, c)
         hs = split_scale(wh)
-        hi, lo = split_f16(wh.double() * hs)
-        whp = torch.stack([hi, lo], 0).reshape(2, mt, 32, c // 16, 2, 8).permute(1, 3, 0, 4, 2, 5).contiguous()  # [mt][st][hl][kg][o][i]
+        whp = pack_head_weight_split(wh, hs)
         head = np.array([self._head_ch, self._head_split, add_w(whp),
                          add_p(torch.cat([self.b_head.detach().float().cpu().reshape(-1), torch.tensor([1.0 / hs])]))], dtype=np.int32)
         wts = np.ascontiguousarray(np.concatenate(wts), dtype=np.float16)
