@@ -31,7 +31,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import copy
 import ctypes as C
+import dataclasses
 import math
 import os
 
@@ -161,14 +163,199 @@ def pack_conv_weight_small_split(w: torch.Tensor, scale: float) -> torch.Tensor:
     return u.permute(1, 6, 3, 4, 2, 0, 5).contiguous()  # [ot][tap][g][kq][n][hl][j]
 
 
+def pack_head_weight_winograd(wh: torch.Tensor) -> torch.Tensor:
+    """[16*mb, c] float32 (the joint 1x1 head convolution, rows padded with zeros to whole 16-channel tiles) -> [mb][c/16][4][16][4]
+    (bo_k_tower_wg, the head loop): element (mb, g, k, o, e) = Wh[16*mb + o][16*g + 4*e + k]."""
+    mb, c = wh.shape[0] // 16, wh.shape[1]
+    return wh.reshape(mb, 16, c // 16, 4, 4).permute(0, 2, 4, 1, 3).contiguous()
+
+
+def pack_head_weight_f16(wh: torch.Tensor) -> torch.Tensor:
+    """[32*mt, c] float32 (rows padded with zeros to whole 32-channel tiles) -> fp16 [mt][c/16][2][32][8] (bo_k_tower_h / bo_k_tower_h16,
+    the head loop): element (mt, st, kg, o, i) = Wh[32*mt + o][16*st + 8*kg + i]."""
+    mt, c = wh.shape[0] // 32, wh.shape[1]
+    return wh.reshape(mt, 32, c // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous().half()
+
+
+def _pad_input_weight(w_in: torch.Tensor) -> torch.Tensor:
+    """The input convolution's [c, 120, 3, 3] weight with zero planes up to 128 (a whole number of K-steps in every layout)."""
+    w0 = torch.zeros((w_in.shape[0], 128, 3, 3), device=w_in.device)
+    w0[:, :120] = w_in
+    return w0
+
+
+def _split_tile(c, asked):
+    # 128 filters: the products as 16x16x32 tiles (csrc/bo_tower_s16.h) or 32x32x16 (bo_tower_s.h); BETAONE_SPLIT_TILE=16 / 32 for A/B runs
+    return 16 if (c == 128 and str(os.environ.get("BETAONE_SPLIT_TILE", SPLIT_TILE_DEFAULT) if asked is None else asked) == "16") else 32
+
+
+def _f16_tile(c, asked):
+    return 16 if str(os.environ.get("BETAONE_F16_TILE", F16_TILE_DEFAULT.get(c, "32")) if asked is None else asked) == "16" else 32
+
+
+@dataclasses.dataclass(frozen=True)
+class _TowerLayout:
+    """What one kind x tile of bo_nn_tower_create reads differently from the others (include/betaone_engine.h, BO_TOWER_*)."""
+    algo: int
+    pack: object  # conv weight [c_out, c_in, 3, 3] float32 (scaled: and its scale) -> the packed tensor, float32 or fp16
+    ksteps: object  # c_in -> K-steps of a layer (column 1 of the layer table)
+    unit: int = 4  # a weight offset counts 16 bytes: 4 floats, or 8 halves (then wts is fp16)
+    wts_multiple: int = 1  # wts gets zeros up to a multiple of this many elements
+    scaled: bool = False  # (hi, lo) routes: pack(w, split_scale(w)), (1 / scale, 0, 0, 0) behind every bias (1 / scale behind the head's),
+    #                       and the parameters behind an SE block padded to a multiple of 4 floats
+    head_rows: int = 0  # the joint head convolution's rows, padded to whole tiles of this many, packed by head_pack; 0: no head descriptor
+    head_pack: object = None
+    head_in_params: bool = False  # the head weights go into params (at a multiple of 4 floats) instead of wts
+
+
+@dataclasses.dataclass(frozen=True)
+class _TowerKind:
+    name: str  # in the messages
+    filters: tuple
+    se_text: str
+    se_limit: object  # filters -> the largest SE hidden width
+    layouts: dict  # tile (None: the kind has one) -> _TowerLayout
+    tile: object = None  # (filters, tile asked for or None: the environment) -> tile
+    tile_first: bool = False  # the tile is chosen in front of the shape check
+
+
+_K16 = lambda c_in: 9 * c_in // 16
+_HEAD_F16 = dict(head_rows=32, head_pack=pack_head_weight_f16)
+_HEAD_SPLIT = dict(head_rows=32, head_pack=pack_head_weight_split)
+TOWER_KINDS = {
+    "tower": _TowerKind("tower", (64, 128), "16", lambda c: 16, {None: _TowerLayout(0, pack_conv_weight, lambda c_in: c_in // 8)}),
+    # (the two 1x1 head convolutions run behind the tower on the LDS-resident output)
+    "tower_wg": _TowerKind("tower", (64, 128), "16", lambda c: 16, {None: _TowerLayout(
+        1, pack_conv_weight_winograd, lambda c_in: c_in // 4, head_rows=16, head_pack=pack_head_weight_winograd, head_in_params=True)}),
+    "tower_f16": _TowerKind("tower_f16", (128, 256), "16", lambda c: 16, {
+        32: _TowerLayout(2, pack_conv_weight_f16, _K16, unit=8, wts_multiple=2, **_HEAD_F16),
+        16: _TowerLayout(5, pack_conv_weight_f16_t16, _K16, unit=8, wts_multiple=2, **_HEAD_F16)}, tile=_f16_tile, tile_first=True),
+    "tower_split": _TowerKind("tower_split", (128, 256), "min(16, filters/16)", lambda c: min(16, c // 16), {
+        32: _TowerLayout(3, pack_conv_weight_split, _K16, unit=8, wts_multiple=8, scaled=True, **_HEAD_SPLIT),
+        16: _TowerLayout(4, pack_conv_weight_split16, _K16, unit=8, wts_multiple=8, scaled=True, **_HEAD_SPLIT)}, tile=_split_tile),
+}
+
+
+@dataclasses.dataclass
+class TowerTables:
+    """The host arrays of bo_nn_tower_create."""
+    table: np.ndarray  # int32 [L, 8]
+    wts: np.ndarray
+    params: np.ndarray  # float32
+    head: object  # int32 [4] (head channels, policy channels, weights offset, bias offset) or None
+    algo: int
+    n_weights: int  # wts in floats
+    c: int
+    tile: object  # 16 / 32, None for the kinds that have one layout
+
+
+def flatten_tower(kind, w_in, b_in, blocks, w_head, b_head, n_policy_ch, tile=None) -> TowerTables:
+    """Flatten the trunk (BatchNorm-folded float32 weights: blocks = [(w1, b1, w2, b2, (se_w1, se_w2) or None)], w_head / b_head the
+    joint 1x1 head convolution) into the host arrays of bo_nn_tower_create for conv=kind.  tile (16 / 32; tower_f16 and tower_split):
+    None reads BETAONE_F16_TILE / BETAONE_SPLIT_TILE.  Pure: no library call, nothing on the GPU."""
+    k = TOWER_KINDS[kind]
+    c = w_in.shape[0]
+    if k.tile_first:
+        tile = k.tile(c, tile)
+    if c not in k.filters or w_in.shape[1] != 120:
+        raise E.EngineError(f"conv='{k.name}' supports 120 input planes and {k.filters[0]} or {k.filters[1]} filters")
+    if not k.tile_first:
+        tile = k.tile(c, tile) if k.tile else None
+    lay = k.layouts[tile]
+    wts, params, layers = [], [], []
+
+    def add_w(t):  # -> offset in units of 16 bytes
+        off = sum(a.size for a in wts) // lay.unit
+        wts.append(t.reshape(-1).numpy())
+        return off
+
+    def add_p(t):  # -> offset in floats
+        off = sum(a.size for a in params)
+        params.append(t.detach().float().cpu().contiguous().reshape(-1).numpy())
+        return off
+
+    def pad_p():
+        n = sum(a.size for a in params)
+        if n % 4:
+            add_p(torch.zeros(4 - n % 4))
+
+    def f32(t):
+        return t.detach().float().cpu()
+
+    convs = [(_pad_input_weight(f32(w_in)), b_in, 0, None)]
+    for w1, b1, w2, b2, se in blocks:
+        convs += [(f32(w1), b1, 1, None), (f32(w2), b2, 2 if se is None else 3, se)]
+    for w, bias, mode, se in convs:
+        if se is not None and se[0].shape[0] > k.se_limit(c):
+            raise E.EngineError(f"conv='{k.name}' supports SE hidden widths up to {k.se_text}")
+        if lay.scaled:
+            s = split_scale(w)
+            row = [add_w(lay.pack(w, s)), lay.ksteps(w.shape[1]), add_p(torch.cat([f32(bias).reshape(-1), torch.tensor([1.0 / s, 0.0, 0.0, 0.0])]))]
+        else:
+            row = [add_w(lay.pack(w)), lay.ksteps(w.shape[1]), add_p(bias)]
+        if se is not None:
+            row += [mode, add_p(se[0]), add_p(se[1]), se[0].shape[0], 0]
+            if lay.scaled:
+                pad_p()
+        else:
+            row += [mode, 0, 0, 0, 0]
+        layers.append(row)
+    layers[-1][7] = 1
+    head = None
+    if lay.head_pack is not None:
+        ch = w_head.shape[0]
+        wh = torch.zeros((-(-ch // lay.head_rows) * lay.head_rows, c))
+        wh[:ch] = f32(w_head).reshape(ch, c)
+        hs = split_scale(wh) if lay.scaled else None
+        whp = lay.head_pack(wh, hs) if lay.scaled else lay.head_pack(wh)
+        if lay.head_in_params:
+            pad_p()
+        w_off = add_p(whp) if lay.head_in_params else add_w(whp)
+        head = np.array([ch, n_policy_ch, w_off, add_p(torch.cat([f32(b_head).reshape(-1), torch.tensor([1.0 / hs] if lay.scaled else [])]))],
+                        dtype=np.int32)
+    wts = np.ascontiguousarray(np.concatenate(wts), dtype=np.float16 if lay.unit == 8 else np.float32)
+    if wts.size % lay.wts_multiple:
+        wts = np.concatenate([wts, np.zeros(lay.wts_multiple - wts.size % lay.wts_multiple, wts.dtype)])
+    params = np.ascontiguousarray(np.concatenate(params), dtype=np.float32)
+    return TowerTables(np.ascontiguousarray(np.array(layers, dtype=np.int32)), wts, params, head, lay.algo, wts.nbytes // 4, c, tile)
+
+
+def _check(lib, rc):
+    if rc:
+        raise E.EngineError(lib.bo_last_error().decode())
+
+
+def _planes(x, dev, message):
+    """x as the contiguous float32 [B, 120, 8, 8] tensor on `dev` that the tower launches read, or EngineError(message)."""
+    if x.device != dev or x.dtype != torch.float32 or x.shape[1:] != (120, 8, 8):
+        raise E.EngineError(message)
+    return x.contiguous()
+
+
+def _dev_index(dev) -> int:
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def _launch_heads(lib, dev, B, launch, n_scratch=4096, tail=False):
+    """The buffers of one head launch (bo_nn_heads, bo_nn_heads_f16, bo_nn_heads_pair) and the launch itself:
+    launch(out ptr, value ptr or None, scratch ptr) -> rc.  -> (out [B, 4672], value [B, 1]), with tail (out, the scratch as
+    value_fc1's partial sums [16, B, 256])."""
+    # the scratch (value_fc1 partial sums / softmax statistics) is allocated per call -- under graph capture it then comes from the
+    # graph's own pool (a module-wide scratch that grew with a later, larger batch left earlier captured graphs writing into freed
+    # memory, and was shared by concurrent streams); the caching allocator makes the eager cost a free-list lookup
+    scr = torch.empty(n_scratch * B, dtype=torch.float32, device=dev)
+    out = torch.empty((B, 4672), dtype=torch.float32, device=dev)
+    value = None if tail else torch.empty((B, 1), dtype=torch.float32, device=dev)
+    _check(lib, launch(out.data_ptr(), None if tail else value.data_ptr(), scr.data_ptr()))
+    return (out, scr.view(16, B, 256)) if tail else (out, value)
+
+
 def conv3x3_small(lib, x, wpacked, bias, c_in, c_out, mode=0, residual=None):
     """y = epilogue(conv3x3(x)) through bo_nn_conv3x3_small; x NCHW float32 [B, c_in_x <= c_in, 8, 8], contiguous."""
     B = x.shape[0]
     y = torch.empty((B, c_out, 8, 8), dtype=torch.float32, device=x.device)
-    rc = lib.bo_nn_conv3x3_small(x.data_ptr(), wpacked.data_ptr(), bias.data_ptr(), residual.data_ptr() if residual is not None else None,
-                                 y.data_ptr(), B, c_in, x.shape[1], c_out, mode, torch.cuda.current_stream(x.device).cuda_stream)
-    if rc:
-        raise E.EngineError(lib.bo_last_error().decode())
+    _check(lib, lib.bo_nn_conv3x3_small(x.data_ptr(), wpacked.data_ptr(), bias.data_ptr(), residual.data_ptr() if residual is not None else None,
+                                        y.data_ptr(), B, c_in, x.shape[1], c_out, mode, torch.cuda.current_stream(x.device).cuda_stream))
     return y
 
 
@@ -179,10 +366,8 @@ def conv3x3_mfma(lib, x, wpacked, bias, c_out, mode=0, residual=None, out=None):
         raise E.EngineError("conv3x3_mfma: x must be a contiguous float32 [B, C, 8, 8] tensor")
     y = out if out is not None else torch.empty((B, c_out, 8, 8), dtype=torch.float32, device=x.device)
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    rc = lib.bo_nn_conv3x3(x.data_ptr(), wpacked.data_ptr(), bias.data_ptr(), residual.data_ptr() if residual is not None else None,
-                           y.data_ptr(), B, c_in, c_out, mode, stream)
-    if rc:
-        raise E.EngineError(lib.bo_last_error().decode())
+    _check(lib, lib.bo_nn_conv3x3(x.data_ptr(), wpacked.data_ptr(), bias.data_ptr(), residual.data_ptr() if residual is not None else None,
+                                  y.data_ptr(), B, c_in, c_out, mode, stream))
     return y
 
 
@@ -227,52 +412,39 @@ class FusedPolicyValueNet(nn.Module):
         self.b_head = nn.Parameter(torch.cat([f.policy_conv.bias, f.value_conv.bias], 0).detach().contiguous(), requires_grad=False)
         self.n_policy_ch = f.policy_conv.out_channels
         self.policy_fc, self.value_fc1, self.value_fc2 = f.policy_fc, f.value_fc1, f.value_fc2
+        # what the hand-written head kernels are written for: 2 policy + 32 value planes into the reference's three Linear layers
+        self._reference_heads = (self.n_policy_ch == 2 and self.w_head.shape[0] == 34 and self.policy_fc.weight.shape == (4672, 128)
+                                 and self.value_fc1.weight.shape == (256, 2048) and self.value_fc2.weight.shape == (1, 256))
         self.layout = "nchw+fused"
-        if conv == "mfma":
-            shapes = {(self.w_in.shape[1], self.w_in.shape[0])} | {(b[0].shape[1], b[0].shape[0]) for b in self.blocks}
-            if not shapes <= MFMA_CONV_SHAPES:
-                raise E.EngineError(f"conv='mfma' supports (c_in, c_out) in {sorted(MFMA_CONV_SHAPES)}, got {sorted(shapes)}")
-            self.c = self.w_in.shape[0]
-            self.p_in = nn.Parameter(pack_conv_weight(self.w_in), requires_grad=False)
-            self.packed = []
-            for i, (w1, _, w2, _, _) in enumerate(self.blocks):
-                p1 = nn.Parameter(pack_conv_weight(w1), requires_grad=False)
-                p2 = nn.Parameter(pack_conv_weight(w2), requires_grad=False)
-                self.register_parameter(f"blk{i}_p1", p1)
-                self.register_parameter(f"blk{i}_p2", p2)
-                self.packed.append((p1, p2))
-            self.zero_bias = nn.Parameter(torch.zeros(self.c, device=dev), requires_grad=False)
-            self.layout = "nchw+mfma"
-        elif conv in ("mfma_small", "tower_b1"):
+        if conv in ("mfma", "mfma_small", "tower_b1"):  # one launch per layer: the packed weights stay torch tensors
             c = self.w_in.shape[0]
-            if c not in (64, 128, 256) or self.w_in.shape[1] != 120:
-                raise E.EngineError(f"conv='{conv}' supports 120 input planes and 64, 128 or 256 filters")
+            if conv == "mfma":
+                shapes = {(self.w_in.shape[1], c)} | {(b[0].shape[1], b[0].shape[0]) for b in self.blocks}
+                if not shapes <= MFMA_CONV_SHAPES:
+                    raise E.EngineError(f"conv='mfma' supports (c_in, c_out) in {sorted(MFMA_CONV_SHAPES)}, got {sorted(shapes)}")
+                pack, w0 = pack_conv_weight, self.w_in
+            else:
+                if c not in (64, 128, 256) or self.w_in.shape[1] != 120:
+                    raise E.EngineError(f"conv='{conv}' supports 120 input planes and 64, 128 or 256 filters")
+                pack, w0 = pack_conv_weight_small, _pad_input_weight(self.w_in)
             self.c = c
-            w0 = torch.zeros((c, 128, 3, 3), device=dev)
-            w0[:, :120] = self.w_in
-            self.p_in = nn.Parameter(pack_conv_weight_small(w0), requires_grad=False)
+            self.p_in = nn.Parameter(pack(w0), requires_grad=False)
             self.packed = []
             for i, (w1, _, w2, _, _) in enumerate(self.blocks):
-                p1 = nn.Parameter(pack_conv_weight_small(w1), requires_grad=False)
-                p2 = nn.Parameter(pack_conv_weight_small(w2), requires_grad=False)
+                p1 = nn.Parameter(pack(w1), requires_grad=False)
+                p2 = nn.Parameter(pack(w2), requires_grad=False)
                 self.register_parameter(f"blk{i}_p1", p1)
                 self.register_parameter(f"blk{i}_p2", p2)
                 self.packed.append((p1, p2))
             self.zero_bias = nn.Parameter(torch.zeros(c, device=dev), requires_grad=False)
-            self.layout = "nchw+" + conv
             if conv == "tower_b1":
                 self._build_b1(dev)
-        elif conv in ("tower", "tower_wg"):
-            self._build_tower(dev, winograd=conv == "tower_wg")
-            self.layout = "nchw+" + conv
-        elif conv == "tower_f16":
-            self._build_tower_f16(dev)
-            self.layout = "nchw+tower_f16"
-        elif conv == "tower_split":
-            self._build_tower_split(dev)
-            self.layout = "nchw+tower_split"
+        elif conv in TOWER_KINDS:
+            self._build_tower(dev, conv)
         elif conv != "miopen":
             raise ValueError("conv must be 'miopen', 'mfma', 'mfma_small', 'tower_b1', 'tower', 'tower_wg', 'tower_split' or 'tower_f16'")
+        if conv != "miopen":
+            self.layout = "nchw+" + conv
 
     def _build_b1(self, dev):
         """bo_nn_b1_create over the SAME device tensors the per-layer route uses (pack_conv_weight_small layout): the handle keeps
@@ -297,9 +469,7 @@ class FusedPolicyValueNet(nn.Module):
                                 c_in, c_in_x, mode, se[0].shape[0] if se else 0, ws.data_ptr() if ws is not None else None, inv, 0)
             descs.append(d)
 
-        w0 = torch.zeros((c, 128, 3, 3))
-        w0[:, :120] = self.w_in.detach().float().cpu()
-        desc(w0, self.p_in, self.b_in, 128, 120, 0)
+        desc(_pad_input_weight(self.w_in.detach().float().cpu()), self.p_in, self.b_in, 128, 120, 0)
         for (w1, b1, w2, b2, se), (p1, p2) in zip(self.blocks, self.packed):
             if se is not None and se[0].shape[0] > 16:
                 raise E.EngineError("conv='tower_b1' supports SE hidden widths up to 16")
@@ -308,9 +478,7 @@ class FusedPolicyValueNet(nn.Module):
         arr = (E.BoB1LayerDesc * len(descs))(*descs)
         self._b1_max = 256 // ((c // 16) * 4)
         handle = C.c_void_p()
-        rc = self.lib.bo_nn_b1_create(arr, len(descs), c, self._b1_max, dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(handle))
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
+        _check(self.lib, self.lib.bo_nn_b1_create(arr, len(descs), c, self._b1_max, _dev_index(dev), C.byref(handle)))
         self._b1, self._b1_dev = handle, dev
 
     def _tower_b1(self, x):
@@ -318,13 +486,9 @@ class FusedPolicyValueNet(nn.Module):
         B = x.shape[0]
         if B > self._b1_max:
             return self._tower_small(x)
-        if x.device != self._b1_dev or x.dtype != torch.float32 or x.shape[1:] != (120, 8, 8):
-            raise E.EngineError("tower_b1: x must be float32 [B, 120, 8, 8] on the net's device")
-        x = x.contiguous()
+        x = _planes(x, self._b1_dev, "tower_b1: x must be float32 [B, 120, 8, 8] on the net's device")
         y = torch.empty((B, self.c, 8, 8), dtype=torch.float32, device=x.device)
-        rc = self.lib.bo_nn_b1_forward(self._b1, x.data_ptr(), y.data_ptr(), B, torch.cuda.current_stream(x.device).cuda_stream)
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
+        _check(self.lib, self.lib.bo_nn_b1_forward(self._b1, x.data_ptr(), y.data_ptr(), B, torch.cuda.current_stream(x.device).cuda_stream))
         return y
 
     def check_b1(self):
@@ -334,218 +498,42 @@ class FusedPolicyValueNet(nn.Module):
         if not t:
             return
         code = C.c_int32(0)
-        if self.lib.bo_nn_b1_status(t, C.byref(code), torch.cuda.current_stream(self._b1_dev).cuda_stream):
-            raise E.EngineError(self.lib.bo_last_error().decode())
+        _check(self.lib, self.lib.bo_nn_b1_status(t, C.byref(code), torch.cuda.current_stream(self._b1_dev).cuda_stream))
         if code.value < 0:
             raise E.EngineError("tower_b1: an activation left the fp16 range (|v| > 65504) and was saturated -- the evaluation is wrong on the fp16 "
                                 "matrix pipe; run this net with BETAONE_F32_TOWER=fp32 (FusedPolicyValueNet(..., f32_pipe=True))")
         if code.value:
             raise E.EngineError(f"tower_b1: a hand-off inside the launch timed out (phase {code.value - 1}); the evaluation is invalid")
 
-    def _build_tower_split(self, dev):
-        """float32 tower on the fp16 matrix pipe (bo_nn_tower_create, BO_TOWER_SPLIT_F16): (hi, lo) fp16 pairs of the scaled weights,
-        the inverse scale behind every bias."""
-        c = self.w_in.shape[0]
-        if c not in (128, 256) or self.w_in.shape[1] != 120:
-            raise E.EngineError("conv='tower_split' supports 120 input planes and 128 or 256 filters")
-        # 128 filters: the products as 16x16x32 tiles (csrc/bo_tower_s16.h) or 32x32x16 (bo_tower_s.h); BETAONE_SPLIT_TILE=16 / 32 for A/B runs
-        self.split_tile = 16 if (c == 128 and os.environ.get("BETAONE_SPLIT_TILE", SPLIT_TILE_DEFAULT) == "16") else 32
-        pack = pack_conv_weight_split16 if self.split_tile == 16 else pack_conv_weight_split
-        wts, params, layers = [], [], []
-        n_h = n_p = 0  # halves in wts, floats in params
-
-        def add_w(t16):
-            nonlocal n_h
-            off = n_h // 8
-            flat = t16.reshape(-1).numpy()
-            wts.append(flat)
-            n_h += flat.size
-            return off
-
-        def add_p(t):
-            nonlocal n_p
-            off = n_p
-            flat = t.detach().float().cpu().contiguous().reshape(-1).numpy()
-            params.append(flat)
-            n_p += flat.size
-            return off
-
-        def add_conv(w, bias):  # -> (weights offset, bias offset); params: bias [c], 1 / scale, padding to a multiple of 4 floats
-            w = w.detach().float().cpu()
-            s = split_scale(w)
-            return add_w(pack(w, s)), add_p(torch.cat([bias.detach().float().cpu().reshape(-1), torch.tensor([1.0 / s, 0.0, 0.0, 0.0])]))
-
-        w0 = torch.zeros((c, 128, 3, 3))
-        w0[:, :120] = self.w_in.detach().float().cpu()
-        wo, bo = add_conv(w0, self.b_in)
-        layers.append([wo, 9 * 128 // 16, bo, 0, 0, 0, 0, 0])
-        for w1, b1, w2, b2, se in self.blocks:
-            wo, bo = add_conv(w1, b1)
-            layers.append([wo, 9 * c // 16, bo, 1, 0, 0, 0, 0])
-            wo, bo = add_conv(w2, b2)
-            if se is not None:
-                if se[0].shape[0] > 16 or se[0].shape[0] > c // 16:
-                    raise E.EngineError("conv='tower_split' supports SE hidden widths up to min(16, filters/16)")
-                layers.append([wo, 9 * c // 16, bo, 3, add_p(se[0]), add_p(se[1]), se[0].shape[0], 0])
-                if n_p % 4:
-                    add_p(torch.zeros(4 - n_p % 4))
-            else:
-                layers.append([wo, 9 * c // 16, bo, 2, 0, 0, 0, 0])
-        layers[-1][7] = 1
-        self._head_ch, self._head_split = self.w_head.shape[0], self.n_policy_ch
-        mt = (self._head_ch + 31) // 32
-        wh = torch.zeros((mt * 32, c))
-        wh[:self._head_ch] = self.w_head.detach().float().cpu().reshape(self._head_ch, c)
-        hs = split_scale(wh)
-        whp = pack_head_weight_split(wh, hs)
-        head = np.array([self._head_ch, self._head_split, add_w(whp),
-                         add_p(torch.cat([self.b_head.detach().float().cpu().reshape(-1), torch.tensor([1.0 / hs])]))], dtype=np.int32)
-        wts = np.ascontiguousarray(np.concatenate(wts), dtype=np.float16)
-        if wts.size % 8:
-            wts = np.concatenate([wts, np.zeros(8 - wts.size % 8, np.float16)])
-        params = np.ascontiguousarray(np.concatenate(params), dtype=np.float32)
-        table = np.ascontiguousarray(np.array(layers, dtype=np.int32))
+    def _build_tower(self, dev, kind):
+        """The persistent tower of conv=kind (bo_nn_tower_create over flatten_tower's arrays); the fp16 tower also gets half copies
+        of the three head Linear layers."""
+        t = flatten_tower(kind, self.w_in, self.b_in, self.blocks, self.w_head, self.b_head, self.n_policy_ch)
         handle = C.c_void_p()
-        rc = self.lib.bo_nn_tower_create(table.ctypes.data, len(layers), wts.ctypes.data, wts.size // 2, params.ctypes.data, params.size, c,
-                                         4 if self.split_tile == 16 else 3, head.ctypes.data, dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(handle))
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
-        self.c, self._tower, self._tower_dev = c, handle, dev
-
-    def _build_tower_f16(self, dev):
-        """fp16 tower (bo_nn_tower_create, BO_TOWER_DIRECT_F16) + half copies of the three head Linear layers."""
-        self.f16_tile = 16 if os.environ.get("BETAONE_F16_TILE", F16_TILE_DEFAULT.get(self.w_in.shape[0], "32")) == "16" else 32
-        pack16 = pack_conv_weight_f16_t16 if self.f16_tile == 16 else pack_conv_weight_f16
-        c = self.w_in.shape[0]
-        if c not in (128, 256) or self.w_in.shape[1] != 120:
-            raise E.EngineError("conv='tower_f16' supports 120 input planes and 128 or 256 filters")
-        wts, params, layers = [], [], []
-        n_h = n_p = 0  # halves in wts, floats in params
-
-        def add_w(t16):
-            nonlocal n_h
-            off = n_h // 8
-            flat = t16.reshape(-1).numpy()
-            wts.append(flat)
-            n_h += flat.size
-            return off
-
-        def add_p(t):
-            nonlocal n_p
-            off = n_p
-            flat = t.detach().float().cpu().contiguous().reshape(-1).numpy()
-            params.append(flat)
-            n_p += flat.size
-            return off
-
-        w0 = torch.zeros((c, 128, 3, 3))
-        w0[:, :120] = self.w_in.detach().float().cpu()
-        layers.append([add_w(pack16(w0)), 9 * 128 // 16, add_p(self.b_in), 0, 0, 0, 0, 0])
-        for w1, b1, w2, b2, se in self.blocks:
-            layers.append([add_w(pack16(w1.detach().float().cpu())), 9 * c // 16, add_p(b1), 1, 0, 0, 0, 0])
-            p2 = add_w(pack16(w2.detach().float().cpu()))
-            if se is not None:
-                if se[0].shape[0] > 16:
-                    raise E.EngineError("conv='tower_f16' supports SE hidden widths up to 16")
-                layers.append([p2, 9 * c // 16, add_p(b2), 3, add_p(se[0]), add_p(se[1]), se[0].shape[0], 0])
-            else:
-                layers.append([p2, 9 * c // 16, add_p(b2), 2, 0, 0, 0, 0])
-        layers[-1][7] = 1
+        _check(self.lib, self.lib.bo_nn_tower_create(t.table.ctypes.data, len(t.table), t.wts.ctypes.data, t.n_weights, t.params.ctypes.data,
+                                                t.params.size, t.c, t.algo, t.head.ctypes.data if t.head is not None else None,
+                                                _dev_index(dev), C.byref(handle)))
+        self.c, self._tower, self._tower_dev = t.c, handle, dev
         self._head_ch, self._head_split = self.w_head.shape[0], self.n_policy_ch
-        mt = (self._head_ch + 31) // 32
-        wh = torch.zeros((mt * 32, c))
-        wh[:self._head_ch] = self.w_head.detach().float().cpu().reshape(self._head_ch, c)
-        whp = wh.reshape(mt, 32, c // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous().half()  # [mt][st][kg][o][i]
-        head = np.array([self._head_ch, self._head_split, add_w(whp), add_p(self.b_head)], dtype=np.int32)
-        wts = np.ascontiguousarray(np.concatenate(wts), dtype=np.float16)
-        if wts.size % 2:
-            wts = np.concatenate([wts, np.zeros(1, np.float16)])
-        params = np.ascontiguousarray(np.concatenate(params), dtype=np.float32)
-        table = np.ascontiguousarray(np.array(layers, dtype=np.int32))
-        handle = C.c_void_p()
-        rc = self.lib.bo_nn_tower_create(table.ctypes.data, len(layers), wts.ctypes.data, wts.size // 2, params.ctypes.data, params.size, c,
-                                         (5 if self.f16_tile == 16 else 2), head.ctypes.data, dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(handle))
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
-        self.c, self._tower, self._tower_dev = c, handle, dev
-        import copy
-
-        self.policy_fc_h = copy.deepcopy(self.policy_fc).half()
-        self.value_fc1_h = copy.deepcopy(self.value_fc1).half()
-        self.value_fc2_h = copy.deepcopy(self.value_fc2).half()
-        self.wants_float32_input = True
+        if kind == "tower_split":
+            self.split_tile = t.tile
+        elif kind == "tower_f16":
+            self.f16_tile = t.tile
+            self.policy_fc_h = copy.deepcopy(self.policy_fc).half()
+            self.value_fc1_h = copy.deepcopy(self.value_fc1).half()
+            self.value_fc2_h = copy.deepcopy(self.value_fc2).half()
+            self.wants_float32_input = True
 
     def _tower_f16_forward(self, x):
         if x.dtype != torch.float32:
             x = x.float()
-        if x.device != self._tower_dev or x.shape[1:] != (120, 8, 8):
-            raise E.EngineError("tower_f16: x must be [B, 120, 8, 8] on the tower's device")
-        x = x.contiguous()
+        x = _planes(x, self._tower_dev, "tower_f16: x must be [B, 120, 8, 8] on the tower's device")
         B = x.shape[0]
         pa = torch.empty((B, self._head_split * 64), dtype=torch.float16, device=x.device)
         pb = torch.empty((B, (self._head_ch - self._head_split) * 64), dtype=torch.float16, device=x.device)
-        rc = self.lib.bo_nn_tower_forward(self._tower, x.data_ptr(), None, pa.data_ptr(), pb.data_ptr(), B,
-                                          torch.cuda.current_stream(x.device).cuda_stream)
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
+        _check(self.lib, self.lib.bo_nn_tower_forward(self._tower, x.data_ptr(), None, pa.data_ptr(), pb.data_ptr(), B,
+                                                 torch.cuda.current_stream(x.device).cuda_stream))
         return pa, pb
-
-    def _build_tower(self, dev, winograd=False):
-        """Flatten the trunk into the three host arrays of bo_nn_tower_create (include/betaone_engine.h)."""
-        c = self.w_in.shape[0]
-        if c not in (64, 128) or self.w_in.shape[1] != 120:
-            raise E.EngineError("conv='tower' supports 120 input planes and 64 or 128 filters")
-        wts, params, layers = [], [], []
-        n_w = n_p = 0
-
-        def add_w(w):
-            nonlocal n_w
-            off = n_w // 4
-            flat = (pack_conv_weight_winograd if winograd else pack_conv_weight)(w.detach().float().cpu()).reshape(-1).numpy()
-            wts.append(flat)
-            n_w += flat.size
-            return off
-
-        def add_p(t):
-            nonlocal n_p
-            off = n_p
-            flat = t.detach().float().cpu().contiguous().reshape(-1).numpy()
-            params.append(flat)
-            n_p += flat.size
-            return off
-
-        w0 = torch.zeros((c, 128, 3, 3))
-        w0[:, :120] = self.w_in.detach().float().cpu()
-        ksteps = (lambda cin: cin // 4) if winograd else (lambda cin: cin // 8)
-        layers.append([add_w(w0), ksteps(128), add_p(self.b_in), 0, 0, 0, 0, 0])
-        for w1, b1, w2, b2, se in self.blocks:
-            layers.append([add_w(w1), ksteps(c), add_p(b1), 1, 0, 0, 0, 0])
-            if se is not None:
-                if se[0].shape[0] > 16:
-                    raise E.EngineError("conv='tower' supports SE hidden widths up to 16")
-                layers.append([add_w(w2), ksteps(c), add_p(b2), 3, add_p(se[0]), add_p(se[1]), se[0].shape[0], 0])
-            else:
-                layers.append([add_w(w2), ksteps(c), add_p(b2), 2, 0, 0, 0, 0])
-        layers[-1][7] = 1
-        head = None
-        if winograd:  # the two 1x1 head convolutions run behind the tower on the LDS-resident output
-            self._head_ch, self._head_split = self.w_head.shape[0], self.n_policy_ch
-            mb = (self._head_ch + 15) // 16
-            wh = torch.zeros((mb * 16, c))
-            wh[:self._head_ch] = self.w_head.detach().float().cpu().reshape(self._head_ch, c)
-            whp = wh.reshape(mb, 16, c // 16, 4, 4).permute(0, 2, 4, 1, 3).contiguous()  # [mb][g][k][o16][e], ic = 16g + 4e + k
-            if n_p % 4:
-                add_p(torch.zeros(4 - n_p % 4))
-            head = np.array([self._head_ch, self._head_split, add_p(whp), add_p(self.b_head)], dtype=np.int32)
-        wts = np.ascontiguousarray(np.concatenate(wts), dtype=np.float32)
-        params = np.ascontiguousarray(np.concatenate(params), dtype=np.float32)
-        table = np.ascontiguousarray(np.array(layers, dtype=np.int32))
-        handle = C.c_void_p()
-        rc = self.lib.bo_nn_tower_create(table.ctypes.data, len(layers), wts.ctypes.data, wts.size, params.ctypes.data, params.size, c,
-                                         1 if winograd else 0, head.ctypes.data if head is not None else None, dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(handle))
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
-        self.c, self._tower, self._tower_dev = c, handle, dev
 
     def __del__(self):
         try:
@@ -571,9 +559,7 @@ class FusedPolicyValueNet(nn.Module):
         if not t or self.conv != "tower_split":
             return
         flag = C.c_int32(0)
-        rc = self.lib.bo_nn_tower_status(t, C.byref(flag), torch.cuda.current_stream(self._tower_dev).cuda_stream)
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
+        _check(self.lib, self.lib.bo_nn_tower_status(t, C.byref(flag), torch.cuda.current_stream(self._tower_dev).cuda_stream))
         if flag.value:
             raise E.EngineError(self.OVERFLOW_MESSAGE)
 
@@ -587,8 +573,7 @@ class FusedPolicyValueNet(nn.Module):
         block brings them along and an invalid evaluation stops the run where it happened."""
         if self.conv == "tower_b1" and self.__dict__.get("_b1"):
             p = C.c_void_p()
-            if self.lib.bo_nn_b1_word(self._b1, C.byref(p)):
-                raise E.EngineError(self.lib.bo_last_error().decode())
+            _check(self.lib, self.lib.bo_nn_b1_word(self._b1, C.byref(p)))
             return (p.value or 0), 2
         return self.overflow_word_ptr(), 1
 
@@ -598,15 +583,12 @@ class FusedPolicyValueNet(nn.Module):
         if not t or self.conv != "tower_split":
             return 0
         p = C.c_void_p()
-        if self.lib.bo_nn_tower_word(t, C.byref(p)):
-            raise E.EngineError(self.lib.bo_last_error().decode())
+        _check(self.lib, self.lib.bo_nn_tower_word(t, C.byref(p)))
         return p.value or 0
 
     def _tower_forward(self, x, heads=False):
         """Tower output [B, C, 8, 8]; with heads=True (conv='tower_wg') the ReLU'd policy / value planes, flattened."""
-        if x.device != self._tower_dev or x.dtype != torch.float32 or x.shape[1:] != (120, 8, 8):
-            raise E.EngineError("tower: x must be float32 [B, 120, 8, 8] on the tower's device")
-        x = x.contiguous()
+        x = _planes(x, self._tower_dev, "tower: x must be float32 [B, 120, 8, 8] on the tower's device")
         B = x.shape[0]
         stream = torch.cuda.current_stream(x.device).cuda_stream
         if heads:
@@ -631,35 +613,72 @@ class FusedPolicyValueNet(nn.Module):
             rc = self.lib.bo_nn_tower_forward(self._tower, x.data_ptr(), y.data_ptr(), dummy[0].data_ptr() if wg else None,
                                               dummy[1].data_ptr() if wg else None, B, stream)
             out = y
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
+        _check(self.lib, rc)
         return out
 
     def _heads(self, p, v, probs, tail=False):
         """tail=True: stop behind the first launch -> (logits, value_fc1's partial sums [16, B, 256]); Engine.step_heads finishes the
         row (softmax, value) in the step kernel that consumes it (bo_nn_heads flags 4)."""
-        B = p.shape[0]
-        dev = p.device
-        # value_fc1 partial sums: allocated per call -- under graph capture it then comes from the graph's own pool (a module-wide
-        # scratch that grew with a later, larger batch left earlier captured graphs writing into freed memory, and was shared
-        # by concurrent streams); the caching allocator makes the eager cost a free-list lookup
-        scr = torch.empty(4096 * B, dtype=torch.float32, device=dev)
-        out = torch.empty((B, 4672), dtype=torch.float32, device=dev)
-        value = None if tail else torch.empty((B, 1), dtype=torch.float32, device=dev)
-        rc = self.lib.bo_nn_heads(p.data_ptr(), v.data_ptr(), self.policy_fc.weight.data_ptr(), self.policy_fc.bias.data_ptr(),
-                                  self.value_fc1.weight.data_ptr(), self.value_fc1.bias.data_ptr(), self.value_fc2.weight.data_ptr(),
-                                  self.value_fc2.bias.data_ptr(), out.data_ptr(), None if tail else value.data_ptr(), scr.data_ptr(), B,
-                                  (4 if tail else 1 if probs else 0) | (2 if p.dtype == torch.float16 else 0),
-                                  torch.cuda.current_stream(dev).cuda_stream)
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
-        return (out, scr.view(16, B, 256)) if tail else (out, value)
+        B, dev = p.shape[0], p.device
+        flags = (4 if tail else 1 if probs else 0) | (2 if p.dtype == torch.float16 else 0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        return _launch_heads(self.lib, dev, B, lambda out, value, scr: self.lib.bo_nn_heads(
+            p.data_ptr(), v.data_ptr(), self.policy_fc.weight.data_ptr(), self.policy_fc.bias.data_ptr(), self.value_fc1.weight.data_ptr(),
+            self.value_fc1.bias.data_ptr(), self.value_fc2.weight.data_ptr(), self.value_fc2.bias.data_ptr(), out, value, scr, B, flags, stream),
+            tail=tail)
+
+    def _heads_f16(self, p, v, probs):
+        """fp16 planes and fp16 head weights on the fp16 pipe (bo_nn_heads_f16); its scratch: (max, sum of exp) per board and output range."""
+        B, dev = p.shape[0], p.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        return _launch_heads(self.lib, dev, B, lambda out, value, scr: self.lib.bo_nn_heads_f16(
+            p.data_ptr(), v.data_ptr(), self.policy_fc_h.weight.data_ptr(), self.policy_fc.bias.data_ptr(), self.value_fc1_h.weight.data_ptr(),
+            self.value_fc1.bias.data_ptr(), self.value_fc2.weight.data_ptr(), self.value_fc2.bias.data_ptr(), out, value, scr, B,
+            1 if probs else 0, stream), n_scratch=20)
+
+    def _library_heads(self, p, v, probs, half=False, forked=False):
+        """The heads as library calls: policy_fc (-> softmax) and tanh(value_fc2(relu(value_fc1))).  half: the fp16 tower's half
+        copies of the three layers.  forked: the value head (2 small kernels) runs beside the policy GEMM -- a fork / join of
+        streams, also inside a captured graph."""
+        fc, fc1, fc2 = (self.policy_fc_h, self.value_fc1_h, self.value_fc2_h) if half else (self.policy_fc, self.value_fc1, self.value_fc2)
+        if not forked:
+            logits = fc(p)
+            return (torch.softmax(logits.float(), dim=1) if probs else logits), torch.tanh(fc2(F.relu(fc1(v))))
+        cur = torch.cuda.current_stream(p.device)
+        side = self.__dict__.get("_side")
+        if side is None or side.device != p.device:
+            side = self.__dict__["_side"] = torch.cuda.Stream(p.device)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            h = torch._addmm_activation(fc1.bias, v, fc1.weight.t())  # relu(fc1)
+            value = torch.empty((h.shape[0], 1), dtype=torch.float32, device=h.device)
+            _check(self.lib, self.lib.bo_nn_value_tail(h.data_ptr(), fc2.weight.data_ptr(), fc2.bias.data_ptr(), value.data_ptr(), h.shape[0],
+                                                       h.shape[1], torch.cuda.current_stream(h.device).cuda_stream))
+        logits = fc(p)
+        if probs:  # before the join: the softmax runs beside the value head instead of behind the streams' rendezvous
+            logits = torch.softmax(logits.float(), dim=1)
+        cur.wait_stream(side)
+        return logits, value
+
+    def head_stage(self, batch: int) -> str:
+        """What runs behind the trunk's head planes at this batch:
+          "heads":     bo_nn_heads -- float32 head weights, accumulation, softmax and value on the fp32 matrix pipe (behind the fp16 tower
+                       up to 1024 boards -- configs[4]: 512 -- with the fp16 planes widened on load: closer to the float32 net than the
+                       half-precision GEMMs; tile-parallel, so a few hundred rows still fill the chip);
+          "heads_f16": the fp16 tower beyond that (fast mode: 4 096 .. 131 072 rows): fp16 weights on the fp16 pipe, the policy FC and its
+                       softmax fused per 32-board wave, the value head in one kernel (bo_heads.h) -- no library launch;
+                       BETAONE_HEADS_F16=0 takes "library" instead (A/B runs);
+          "library" / "library_forked" (behind tower_wg / tower_split): a net without the reference's head shapes, and conv='miopen'."""
+        if self.fused_heads and self._reference_heads:
+            if self.conv != "tower_f16" or batch <= 1024:
+                return "heads"
+            if os.environ.get("BETAONE_HEADS_F16", "1") != "0":
+                return "heads_f16"
+        return "library_forked" if self.conv in ("tower_wg", "tower_split") else "library"
 
     def tail_supported(self, batch: int) -> bool:
-        """forward_tail exists for this net at this batch: the evaluate stage ends in bo_nn_heads (the reference's head shapes,
-        float32 head weights; behind the fp16 tower up to 1024 boards)."""
-        ok = self.fused_heads and self.policy_fc.weight.shape == (4672, 128) and self.value_fc1.weight.shape == (256, 2048)
-        return bool(ok and (self.conv != "tower_f16" or batch <= 1024))
+        """forward_tail exists for this net at this batch: the evaluate stage ends in bo_nn_heads."""
+        return self.head_stage(batch) == "heads"
 
     def tail_params(self):
         """(value_fc1.bias, value_fc2.weight, value_fc2.bias) device pointers for Engine.step_heads (a captured graph holds copies of
@@ -669,53 +688,21 @@ class FusedPolicyValueNet(nn.Module):
     @torch.no_grad()
     def forward_tail(self, x):
         """(logits [B, 4672], partial sums of value_fc1 [16, B, 256]): the evaluate stage without its last launch."""
-        if not self.tail_supported(x.shape[0]):
-            raise E.EngineError(f"forward_tail: not available for conv={self.conv!r} at batch {x.shape[0]}")
         return self.forward(x, tail=True)
-
-    def _heads_f16(self, p, v, probs):
-        B, dev = p.shape[0], p.device
-        out = torch.empty((B, 4672), dtype=torch.float32, device=dev)
-        value = torch.empty((B, 1), dtype=torch.float32, device=dev)
-        scr = torch.empty(20 * B, dtype=torch.float32, device=dev)  # (max, sum of exp) per board and output range (per call: see _heads)
-        rc = self.lib.bo_nn_heads_f16(p.data_ptr(), v.data_ptr(), self.policy_fc_h.weight.data_ptr(), self.policy_fc.bias.data_ptr(),
-                                      self.value_fc1_h.weight.data_ptr(), self.value_fc1.bias.data_ptr(), self.value_fc2.weight.data_ptr(),
-                                      self.value_fc2.bias.data_ptr(), out.data_ptr(), value.data_ptr(), scr.data_ptr(), B, 1 if probs else 0,
-                                      torch.cuda.current_stream(dev).cuda_stream)
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
-        return out, value
-
-    def _value_tail(self, h):
-        out = torch.empty((h.shape[0], 1), dtype=torch.float32, device=h.device)
-        rc = self.lib.bo_nn_value_tail(h.data_ptr(), self.value_fc2.weight.data_ptr(), self.value_fc2.bias.data_ptr(), out.data_ptr(), h.shape[0],
-                                       h.shape[1], torch.cuda.current_stream(h.device).cuda_stream)
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
-        return out
 
     def _epi(self, x, bias, res=None):
         B, C = x.shape[0], x.shape[1]
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = self.lib.bo_nn_bias_act(x.data_ptr(), bias.data_ptr(), res.data_ptr() if res is not None else None, B, C, stream)
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
+        _check(self.lib, self.lib.bo_nn_bias_act(x.data_ptr(), bias.data_ptr(), res.data_ptr() if res is not None else None, B, C, stream))
         return x
 
     def _se(self, x, bias, se, res):
         B, C = x.shape[0], x.shape[1]
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        if self.conv in ("mfma_small", "tower_b1") and C % 16 == 0 and se[0].shape[0] <= 16:  # few boards: C/16 workgroups per board, result into `res`
-            rc = self.lib.bo_nn_se_residual_small(x.data_ptr(), bias.data_ptr(), se[0].data_ptr(), se[1].data_ptr(), res.data_ptr(), B, C,
-                                                  se[0].shape[0], stream)
-            if rc:
-                raise E.EngineError(self.lib.bo_last_error().decode())
-            return res
-        rc = self.lib.bo_nn_se_residual(x.data_ptr(), bias.data_ptr(), se[0].data_ptr(), se[1].data_ptr(), res.data_ptr(), B, C,
-                                        se[0].shape[0], stream)
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
-        return x
+        small = self.conv in ("mfma_small", "tower_b1") and C % 16 == 0 and se[0].shape[0] <= 16  # few boards: C/16 workgroups per board, result into `res`
+        _check(self.lib, (self.lib.bo_nn_se_residual_small if small else self.lib.bo_nn_se_residual)(
+            x.data_ptr(), bias.data_ptr(), se[0].data_ptr(), se[1].data_ptr(), res.data_ptr(), B, C, se[0].shape[0], stream))
+        return res if small else x
 
     def _tower_mfma(self, x):
         L, C = self.lib, self.c
@@ -739,6 +726,27 @@ class FusedPolicyValueNet(nn.Module):
                 x = conv3x3_small(L, y, p2, b2, C, C, 2, residual=x)
         return x
 
+    def _tower_miopen(self, x):
+        x = self._epi(F.conv2d(x, self.w_in, None, padding=1), self.b_in)
+        for w1, b1, w2, b2, se in self.blocks:
+            y = self._epi(F.conv2d(x, w1, None, padding=1), b1)
+            y = F.conv2d(y, w2, None, padding=1)
+            x = self._se(y, b2, se, x) if se is not None else self._epi(y, b2, x)
+        return x
+
+    def _trunk(self, x):
+        """The ReLU'd (policy planes [B, 64 * policy channels], value planes) behind the joint head convolution: from the tower kernel
+        itself (tower_f16 in fp16, tower_wg, tower_split), otherwise a 1x1 convolution and its epilogue behind the tower output."""
+        conv = self.conv
+        if conv == "tower_f16":
+            return self._tower_f16_forward(x)
+        if conv in ("tower_wg", "tower_split"):
+            return self._tower_forward(x, heads=True)
+        x = (self._tower_mfma(x) if conv == "mfma" else self._tower_small(x) if conv == "mfma_small" else self._tower_b1(x) if conv == "tower_b1"
+             else self._tower_forward(x) if conv == "tower" else self._tower_miopen(x))
+        h = self._epi(F.conv2d(x, self.w_head, None), self.b_head)
+        return h[:, :self.n_policy_ch].flatten(1), h[:, self.n_policy_ch:].flatten(1)
+
     @torch.no_grad()
     def forward_probs(self, x):
         """(softmax(logits, dim=1) in float32, value): the policy softmax of mcts.py:185,287 issued where it costs least."""
@@ -746,58 +754,15 @@ class FusedPolicyValueNet(nn.Module):
 
     @torch.no_grad()
     def forward(self, x, probs: bool = False, tail: bool = False):
-        if self.conv == "tower_f16":
-            p, v = self._tower_f16_forward(x)
-            if self.fused_heads and p.shape[1] == 128 and v.shape[1] == 2048:
-                # Up to 1024 boards (configs[4]: 512): fp16 head planes widened on load; float32 head weights, accumulation, softmax and
-                # value on the fp32 matrix pipe (closer to the float32 net than the half-precision GEMMs; tile-parallel, so a few
-                # hundred rows still fill the chip).  Beyond (fast mode: 4 096 .. 131 072 rows): fp16 weights on the fp16 pipe, the
-                # policy FC and its softmax fused per 32-board wave, the value head in one kernel (bo_heads.h) -- no library launch.
-                if p.shape[0] <= 1024:
-                    return self._heads(p, v, probs, tail)
-                if os.environ.get("BETAONE_HEADS_F16", "1") != "0":  # (0: the library path below, for A/B runs)
-                    return self._heads_f16(p, v, probs)
-            logits = self.policy_fc_h(p)
-            return (torch.softmax(logits.float(), dim=1) if probs else logits), torch.tanh(self.value_fc2_h(F.relu(self.value_fc1_h(v))))
-        if self.conv in ("tower_wg", "tower_split"):  # tower + head convolutions in one kernel, then the heads
-            p, v = self._tower_forward(x, heads=True)
-            if self.fused_heads and p.shape[1] == 128 and v.shape[1] == 2048:
-                return self._heads(p, v, probs, tail)  # policy FC + softmax + value head: two launches (csrc/bo_heads.h)
-            # the value head (2 small kernels) runs beside the policy GEMM: a fork/join of streams, also inside a captured graph
-            cur = torch.cuda.current_stream(x.device)
-            side = self.__dict__.get("_side")
-            if side is None or side.device != x.device:
-                side = self.__dict__["_side"] = torch.cuda.Stream(x.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                h = torch._addmm_activation(self.value_fc1.bias, v, self.value_fc1.weight.t())  # relu(fc1)
-                value = self._value_tail(h)
-            logits = self.policy_fc(p)
-            if probs:  # before the join: the softmax runs beside the value head instead of behind the streams' rendezvous
-                logits = torch.softmax(logits.float(), dim=1)
-            cur.wait_stream(side)
-            return logits, value
-        if self.conv in ("mfma", "tower", "mfma_small", "tower_b1"):
-            x = (self._tower_mfma(x) if self.conv == "mfma" else self._tower_small(x) if self.conv == "mfma_small"
-                 else self._tower_b1(x) if self.conv == "tower_b1" else self._tower_forward(x))
-            h = self._epi(F.conv2d(x, self.w_head, None), self.b_head)
-            p = h[:, :self.n_policy_ch].flatten(1)
-            v = h[:, self.n_policy_ch:].flatten(1)
-            if self.fused_heads and h.dtype == torch.float32 and p.shape[1] == 128 and v.shape[1] == 2048:
-                # (batch 1 -- uci.py's analysis -- : the slices are contiguous already; this replaces nine small launches)
-                return self._heads(p.contiguous(), v.contiguous(), probs, tail)
-            logits = self.policy_fc(p)
-            return (torch.softmax(logits.float(), dim=1) if probs else logits), torch.tanh(self.value_fc2(F.relu(self.value_fc1(v))))
-        x = self._epi(F.conv2d(x, self.w_in, None, padding=1), self.b_in)
-        for w1, b1, w2, b2, se in self.blocks:
-            y = self._epi(F.conv2d(x, w1, None, padding=1), b1)
-            y = F.conv2d(y, w2, None, padding=1)
-            x = self._se(y, b2, se, x) if se is not None else self._epi(y, b2, x)
-        h = self._epi(F.conv2d(x, self.w_head, None), self.b_head)
-        p = h[:, :self.n_policy_ch].flatten(1)
-        v = h[:, self.n_policy_ch:].flatten(1)
-        logits = self.policy_fc(p)
-        return (torch.softmax(logits.float(), dim=1) if probs else logits), torch.tanh(self.value_fc2(F.relu(self.value_fc1(v))))
+        stage = self.head_stage(x.shape[0])
+        if tail and stage != "heads":  # (every other stage returns the value [B, 1], not value_fc1's partial sums)
+            raise E.EngineError(f"forward_tail: not available for conv={self.conv!r} at batch {x.shape[0]}")
+        p, v = self._trunk(x)
+        if stage == "heads":  # (batch 1 -- uci.py's analysis -- : the slices of the head convolution's output are contiguous already)
+            return self._heads(p.contiguous(), v.contiguous(), probs, tail)
+        if stage == "heads_f16":
+            return self._heads_f16(p, v, probs)
+        return self._library_heads(p, v, probs, half=self.conv == "tower_f16", forked=stage == "library_forked")
 
 
 class PairedNet(nn.Module):
@@ -845,8 +810,7 @@ class PairedNet(nn.Module):
         a, b = self.nets
         if not all(isinstance(n, FusedPolicyValueNet) and n.conv == "tower_split" and n.__dict__.get("_tower") for n in (a, b)):
             return False
-        heads_ok = all(n.fused_heads and n.policy_fc.weight.shape == (4672, 128) and n.value_fc1.weight.shape == (256, 2048)
-                       and n._head_ch == 34 and n._head_split == 2 for n in (a, b))
+        heads_ok = all(n.fused_heads and n._reference_heads for n in (a, b))
         if not heads_ok or a.split_tile != b.split_tile or a._tower_dev != b._tower_dev:
             return False
         return self.lib.bo_nn_tower_pair_check(a._tower, b._tower) == 0
@@ -883,22 +847,12 @@ class PairedNet(nn.Module):
         stream = torch.cuda.current_stream(x.device).cuda_stream
         if self.route == "pair:tower_split":
             a, b = self.nets
-            if x.device != a._tower_dev or x.dtype != torch.float32 or x.shape[1:] != (120, 8, 8):
-                raise E.EngineError("PairedNet: x must be float32 [B, 120, 8, 8] on the nets' device")
-            x = x.contiguous()
+            x = _planes(x, a._tower_dev, "PairedNet: x must be float32 [B, 120, 8, 8] on the nets' device")
             pa = torch.empty((B, 2 * 64), dtype=torch.float32, device=x.device)
             pv = torch.empty((B, 32 * 64), dtype=torch.float32, device=x.device)
-            rc = self.lib.bo_nn_tower_forward_pair(a._tower, b._tower, sel.data_ptr(), x.data_ptr(), pa.data_ptr(), pv.data_ptr(), B, stream)
-            if rc:
-                raise E.EngineError(self.lib.bo_last_error().decode())
-            scr = torch.empty(4096 * B, dtype=torch.float32, device=x.device)  # (per call, as FusedPolicyValueNet._heads: graph-pool safe)
-            out = torch.empty((B, 4672), dtype=torch.float32, device=x.device)
-            value = torch.empty((B, 1), dtype=torch.float32, device=x.device)
-            rc = self.lib.bo_nn_heads_pair(pa.data_ptr(), pv.data_ptr(), C.byref(self._hw[0]), C.byref(self._hw[1]), sel.data_ptr(),
-                                           out.data_ptr(), value.data_ptr(), scr.data_ptr(), B, 1 if probs else 0, stream)
-            if rc:
-                raise E.EngineError(self.lib.bo_last_error().decode())
-            return out, value
+            _check(self.lib, self.lib.bo_nn_tower_forward_pair(a._tower, b._tower, sel.data_ptr(), x.data_ptr(), pa.data_ptr(), pv.data_ptr(), B, stream))
+            return _launch_heads(self.lib, x.device, B, lambda out, value, scr: self.lib.bo_nn_heads_pair(
+                pa.data_ptr(), pv.data_ptr(), C.byref(self._hw[0]), C.byref(self._hw[1]), sel.data_ptr(), out, value, scr, B, 1 if probs else 0, stream))
         # merge: both nets over the whole batch (twice the evaluate time), then each row from its own net
         outs = []
         for n in self.nets:
@@ -913,8 +867,6 @@ class PairedNet(nn.Module):
             raise E.EngineError(f"PairedNet: the two nets' policy widths differ ({tuple(l0.shape)} vs {tuple(l1.shape)})")
         out = torch.empty_like(l0)
         value = torch.empty_like(v0)
-        rc = self.lib.bo_nn_merge_rows(sel.data_ptr(), l0.data_ptr(), v0.data_ptr(), l1.data_ptr(), v1.data_ptr(), out.data_ptr(),
-                                       value.data_ptr(), B, l0.shape[1], stream)
-        if rc:
-            raise E.EngineError(self.lib.bo_last_error().decode())
+        _check(self.lib, self.lib.bo_nn_merge_rows(sel.data_ptr(), l0.data_ptr(), v0.data_ptr(), l1.data_ptr(), v1.data_ptr(), out.data_ptr(),
+                                                   value.data_ptr(), B, l0.shape[1], stream))
         return out, value

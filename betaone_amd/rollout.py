@@ -296,6 +296,8 @@ class Rollout:
     def _step_after(self, first, second):
         """The tree step behind an evaluation: (logits or probabilities, value) -> bo_step; (logits, partial sums) -> bo_step_heads."""
         if self.step_tail:
+            if second.shape != (16, self.G, 256):  # (a value [G, 1] here would be read as partial sums, past its end)
+                raise E.EngineError(f"step tail: value_fc1's partial sums must be [16, {self.G}, 256], got {tuple(second.shape)}")
             self.eng.step_heads(first.data_ptr(), second.data_ptr(), *self._tail_params, second.shape[1], self.nn_in.data_ptr(), self._stream())
         else:
             self.eng.step(first.data_ptr(), second.data_ptr(), self.policy_kind, self.nn_in.data_ptr(), self._stream())

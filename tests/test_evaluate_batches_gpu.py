@@ -177,6 +177,57 @@ def test_later_pass_rows_match_the_float64_net(n_cu, bases, rid, conv, size, env
     fused.check_overflow()
 
 
+# (conv, the smallest net of the suite that the route takes, [(batch, BETAONE_HEADS_F16 or None, the stages allowed)])
+STAGE_CASES = [(conv, (2, 1, 64), [(3, None, ("heads",))]) for conv in ("mfma", "mfma_small", "tower_b1", "tower", "tower_wg")]
+STAGE_CASES += [("miopen", (2, 1, 64), [(3, None, ("library",))]), ("tower_split", (2, 1, 128), [(3, None, ("heads",))]),
+                ("tower_f16", (2, 1, 128), [(3, None, ("heads",)), (1024, None, ("heads",)), (1024, "0", ("heads",)),
+                                            (1025, None, ("heads_f16",)), (1025, "0", ("library",))])]
+
+
+@pytest.mark.parametrize("conv,size,runs", STAGE_CASES, ids=[c[0] for c in STAGE_CASES])
+def test_head_stage_agrees_with_forward(bases, conv, size, runs, monkeypatch):
+    """head_stage(B) names what forward runs: forward(x, tail=True) returns value_fc1's partial sums [16, B, 256] exactly when
+    tail_supported(B), and raises EngineError otherwise (never the value [B, 1] in their place); forward and forward_probs stay,
+    at every stage, within the bound this file uses for the route (_err_bound; for the probabilities against the float64 softmax of
+    the float64 logits: |d softmax| <= max |d logits| / 2, so the logits' bound holds for them)."""
+    from betaone_amd import engine as E
+    from betaone_amd.fused_net import FusedPolicyValueNet
+
+    net = _plain_net(size)
+    fused = FusedPolicyValueNet(net, conv=conv).to(DEV)
+    for B, heads_f16, stages in runs:
+        if heads_f16 is None:
+            monkeypatch.delenv("BETAONE_HEADS_F16", raising=False)
+        else:
+            monkeypatch.setenv("BETAONE_HEADS_F16", heads_f16)
+        what = (conv, B, heads_f16)
+        x = EB.make_rows(bases, B, seed=B + 3)
+        stage = fused.head_stage(B)
+        assert stage in stages and fused.tail_supported(B) == (stage == "heads"), (what, stage)
+        with torch.no_grad():
+            logits, value = fused(x)
+            probs, value_p = fused.forward_probs(x)
+            if fused.tail_supported(B):
+                l_tail, part = fused.forward(x, tail=True)
+                assert part.shape == (16, B, 256) and part.dtype == torch.float32 and torch.equal(l_tail, logits), what
+                l_tail, part = fused.forward_tail(x)
+                assert part.shape == (16, B, 256), what
+            else:
+                for call in (lambda: fused.forward(x, tail=True), lambda: fused.forward_tail(x)):
+                    with pytest.raises(E.EngineError):
+                        call()
+        assert logits.shape == probs.shape == (B, 4672) and value.reshape(-1).shape == value_p.reshape(-1).shape == (B,), what
+        idx = torch.tensor(sorted({0, 1, B // 2, B - 2, B - 1}), device=DEV)
+        l64, v64 = EB.reference64(net, x[idx])
+        bound, e_torch = _err_bound(conv, net, x[idx], l64, v64)
+        e_logits = EB.row_errors(logits[idx].float(), value.float().reshape(-1, 1)[idx], l64, v64).max()
+        e_probs = EB.row_errors(probs[idx], value_p.float().reshape(-1, 1)[idx], torch.softmax(l64, dim=1), v64).max()
+        print(f"[head stage] {conv} B={B} BETAONE_HEADS_F16={heads_f16}: {stage}; errors {e_logits:.3g} / {e_probs:.3g}, bound {bound:.3g} (torch {e_torch:.3g})")
+        assert e_logits <= bound and e_probs <= bound, (what, stage, float(e_logits), float(e_probs), bound)
+    torch.cuda.synchronize()
+    fused.check_overflow()
+
+
 def test_fast_mode_evaluate_stage_at_32768_rows(n_cu, bases):
     """The evaluate stage of bench.py --fast at a quarter of the bench's batch: the 10x128 net (torch.manual_seed(0), default
     initialisation) in fp16 as bench.make_net builds it -- best_inference_copy(..., torch.float16) -> conv='tower_f16'.  The bench sizes
