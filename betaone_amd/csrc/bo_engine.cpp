@@ -326,6 +326,7 @@ extern "C" int bo_engine_create(const bo_config *cfg, int device, bo_engine **ou
         rc |= e->alloc(&f.played_now, G); rc |= e->alloc(&f.row_pos, G * L);
         rc |= e->alloc(&f.row_moves, G * L * BO_MAX_MOVES);
         rc |= e->alloc(&f.sim_path, G * L * BO_FW_PATH_CAP);
+        rc |= e->alloc(&f.row_val, G * L);
         float *st = nullptr, *rt = nullptr;
         rc |= e->alloc(&st, (size_t)BO_FW_SQRT_TAB); rc |= e->alloc(&rt, (size_t)BO_FW_RCP_TAB);
         if (!rc) {
@@ -338,6 +339,7 @@ extern "C" int bo_engine_create(const bo_config *cfg, int device, bo_engine **ou
             f.sqrt_tab = st; f.rcp_tab = rt;
             rt_memset(f.ctl, 0, G * (size_t)f.CS * 4, nullptr);
             rt_memset(f.played_now, 0, G * 4, nullptr);
+            rt_memset(f.row_val, 0, G * L * 4, nullptr);
             d.played_now = f.played_now;
         }
     }
@@ -576,7 +578,7 @@ static int step_launch(bo_engine *e, const float *policy_dev, const float *value
     e->prefetch_valid = false;  // (a prefetched result block is older than this step; replays of a captured step are the caller's to track)
     if (e->fast) {  // apply (one wave per row) -> backup + select (half a wave per game) -> leaf positions and planes (one wave per row)
         const int rows = e->d.c.G * e->f.L;
-        if (policy_kind != BO_POLICY_NONE) RT(RT_LAUNCH(bo_k_fw_apply, rows, stream, e->d, e->f, policy_dev, policy_kind));
+        if (policy_kind != BO_POLICY_NONE) RT(RT_LAUNCH(bo_k_fw_apply, rows, stream, e->d, e->f, policy_dev, value_dev, policy_kind));
 #if !defined(BO_WAVE_EMU)
         if (e->sel_profile) {  // eager launches only (events recorded during a graph capture would become graph nodes)
             if (!e->sel_ev0) { RT((int)hipEventCreate(&e->sel_ev0)); RT((int)hipEventCreate(&e->sel_ev1)); }
@@ -589,7 +591,7 @@ static int step_launch(bo_engine *e, const float *policy_dev, const float *value
             RT((int)hipEventRecord(e->sel_ev0, (hipStream_t)stream));
         }
 #endif
-        RT(launch_fw_select(e, value_dev, policy_kind, stream));
+        RT(launch_fw_select(e, policy_kind != BO_POLICY_NONE ? e->f.row_val : value_dev, policy_kind, stream));  // (values as bo_k_fw_apply left them: finite)
 #if !defined(BO_WAVE_EMU)
         if (e->sel_profile) { RT((int)hipEventRecord(e->sel_ev1, (hipStream_t)stream)); e->sel_pending = 1; }
 #endif

@@ -111,6 +111,7 @@ struct FastW {
     bo_mv *row_moves;          // [G][L][256] its legal moves (python-chess order)
     int *sim_path;             // [G][PATH_CAP][L] record ids root..leaf, DEPTH-major (record id = granule * GR + index): FW_PIDX
     int *played_now;           // [G] move played by the last bo_k_play (0: none); the same array as Eng::played_now
+    float *row_val;            // [G][L] value of row r as the select + backup kernel reads it: the caller's, or 0 where that one is not finite
 };
 
 BO_DEV int *fw_ctl(const FastW &f, int g) { return f.ctl + (size_t)g * f.CS; }
@@ -176,7 +177,11 @@ struct FwShared {
 BO_DEV int fw_row_need(int term, int nlegal) { return term == 0 ? BO_FW_HG + fw_gran_for(nlegal) : 0; }
 
 // ---- apply: the evaluated leaf of row r gets its children ------------------------------------------------------------
-BO_KERNEL void bo_k_fw_apply(Eng e, FastW f, const float *policy, int kind) {
+// Non-finite rows (the contract of ST_NAN_SCORE, bo_tree.h): a sum over the legal moves that is NaN or +-inf -- one such entry is enough --
+// is treated like a sum of 0 (uniform priors), a prior that still is not finite becomes 0, a value that is not finite is backed up as 0;
+// each of them flags the game here, in the launch that consumes the row.  The select + backup kernels read the row's value from
+// f.row_val, which this kernel writes: they are launched with that pointer instead of the caller's.
+BO_KERNEL void bo_k_fw_apply(Eng e, FastW f, const float *policy, const float *value, int kind) {
     BO_SHARED float pv[BO_MAX_MOVES];
     const int L = f.L, g = bo_block() / L, r = bo_block() % L, lane = bo_lane();
     const int *ctl = fw_ctl(f, g);
@@ -201,7 +206,10 @@ BO_KERNEL void bo_k_fw_apply(Eng e, FastW f, const float *policy, int kind) {
     }
     bo_sync();
     const float sum = fw_sum(pv, n);
-    for (int j = lane; j < n; j += 64) pv[j] = sum > 0.0f ? pv[j] / sum : 1.0f / (float)n;
+    bool bad = !bo_finite(sum);
+    for (int j = lane; j < n; j += 64) pv[j] = (sum > 0.0f && !bad) ? finite_or_zero(pv[j] / sum, &bad) : 1.0f / (float)n;
+    const float v = slot == 0 ? 0.0f : finite_or_zero(value[ro], &bad);  // (the root's own evaluation is not backed up: no simulation ends in it)
+    if (lane == 0) f.row_val[ro] = v;
     bo_sync();
     if (slot == 0 && e.c.use_noise) {  // Dirichlet noise on every root prior
         const double *nz = e.noise + (size_t)g * BO_MAX_MOVES;
@@ -211,6 +219,7 @@ BO_KERNEL void bo_k_fw_apply(Eng e, FastW f, const float *policy, int kind) {
         }
         bo_sync();
     }
+    if (bo_ballot(bad) != 0 && lane == 0) bo_atomic_or(&e.status[g], ST_NAN_SCORE);
     // this row's run starts behind the runs of the rows before it (rows of one game are applied by different waves)
     int first = ctl[FWC_TOP];
     for (int q = 0; q < r; q++) {

@@ -776,6 +776,18 @@ BO_DEV int stable_rank(const float *p, int n, int j) {
     return r;
 }
 
+// The contract of ST_NAN_SCORE (BO_ST_NAN_SCORE, include/betaone_engine.h): a prior the engine would store, or a value it would back up,
+// that is NaN or +-inf is replaced by 0 and the game is flagged -- by the step that consumes the row, not by a later select that happens to
+// see NaN scores.  Over finite numbers stable_rank is a permutation of 0 .. n-1, so every rank_of[] entry below the child count is
+// written and every child comes from its own parent's move list (with NaN priors every move ranked 0: the other ranks kept their -1, or
+// the moves an earlier leaf had left in the slot).  -inf LOGITS are legitimate (a masked move: probability 0).
+BO_DEV bool bo_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }
+BO_DEV float finite_or_zero(float x, bool *bad) {
+    if (bo_finite(x)) return x;
+    *bad = true;
+    return 0.0f;
+}
+
 struct StepShared {
     bo_mv moves[BO_MAX_MOVES];
     bo_mv moves2[BO_MAX_MOVES];
@@ -818,7 +830,8 @@ BO_DEV void apply_root(const Eng &e, int g, const float *row, int kind, StepShar
     load_probs(row, kind, sh.probs);
     int m = e.c.root_m < n ? e.c.root_m : n;
     if (m > BO_CH_CAP) m = BO_CH_CAP;
-    for (int j = lane; j < n; j += 64) sh.pv[j] = sh.probs[move_to_index(mv[j])];
+    bool bad = false;
+    for (int j = lane; j < n; j += 64) sh.pv[j] = finite_or_zero(sh.probs[move_to_index(mv[j])], &bad);
     if (lane < 2 * BO_CH_CAP) sh.rank_of[lane] = -1;
     bo_sync();
     for (int j = lane; j < n; j += 64) {  // first expand: top-m raw priors
@@ -845,9 +858,10 @@ BO_DEV void apply_root(const Eng &e, int g, const float *row, int kind, StepShar
         bo_sync();
         const float sum = np_sum_4672(sh.probs);
         const float denom = sum + 1e-12f;
-        for (int j = lane; j < n; j += 64) sh.pv[j] = sh.probs[move_to_index(mv[j])] / denom;
+        for (int j = lane; j < n; j += 64) sh.pv[j] = finite_or_zero(sh.probs[move_to_index(mv[j])] / denom, &bad);
         bo_sync();
     }
+    if (bo_ballot(bad) != 0) *flags |= ST_NAN_SCORE;
     // second expand (mcts.py:203): top-m of the (noised) priors, children not yet present are appended
     for (int j = lane; j < n; j += 64) {
         int r = stable_rank(sh.pv, n, j);
@@ -916,9 +930,10 @@ BO_DEV void apply_leaf(const Eng &e, int g, int leaf, const float *row, int kind
     if (slot >= e.c.UL_MAX) { *flags |= ST_UL_OVERFLOW; slot = e.c.UL_MAX - 1; }
     const size_t uo = (size_t)g * e.c.UL_MAX + slot;
     float value;
+    bool bad = false;
     if (kind == POLICY_PROBS) {
         value = value_of[g];
-        for (int j = lane; j < n; j += 64) sh.pv[j] = row[move_to_index(mv[j])];
+        for (int j = lane; j < n; j += 64) sh.pv[j] = finite_or_zero(row[move_to_index(mv[j])], &bad);
     } else {  // softmax restricted to what is needed: max and sum over the row, exp at the legal indices
         float mx, sum;
         if (vt.vpart) {  // bo_step_heads: the value's operands are requested in front of the row (one round trip for both)
@@ -930,9 +945,11 @@ BO_DEV void apply_leaf(const Eng &e, int g, int leaf, const float *row, int kind
             value = value_of[g];
             row_max_sum(row, &mx, &sum);
         }
-        for (int j = lane; j < n; j += 64) sh.pv[j] = bo_exp_row(row[move_to_index(mv[j])] - mx) / sum;
+        for (int j = lane; j < n; j += 64) sh.pv[j] = finite_or_zero(bo_exp_row(row[move_to_index(mv[j])] - mx) / sum, &bad);
     }
     bo_sync();
+    value = finite_or_zero(value, &bad);  // (the same value in every lane)
+    if (bo_ballot(bad) != 0) *flags |= ST_NAN_SCORE;
     const int M = n < e.c.CH_MAX ? n : e.c.CH_MAX;
     for (int j = lane; j < n; j += 64) {
         int r = stable_rank(sh.pv, n, j);

@@ -24,7 +24,7 @@ MAX_LEGAL = 256
 RES_CAP = 256
 POLICY_NONE, POLICY_LOGITS, POLICY_PROBS = 0, 1, 2
 
-STATUS_BITS = {1: "node overflow", 2: "depth overflow", 4: "NaN PUCT score", 8: "ply overflow",
+STATUS_BITS = {1: "node overflow", 2: "depth overflow", 4: "NaN or infinite evaluation (prior or value)", 8: "ply overflow",
                16: "illegal action", 32: "leaf cache overflow", 64: "tracker overflow", 128: "position range outside the array",
                256: "pi wider than the record's rows"}
 ST_PLY_OVERFLOW, ST_ILLEGAL_ACTION = 8, 16   # per-GAME conditions (the reference aborts that game only); the rest are engine faults
@@ -32,6 +32,11 @@ ST_PI_OVERFLOW = 256  # bo_reanalysis_result: a condition of one record (its sta
 ST_NODE_OVERFLOW = 1  # reference mode: a fault (the node arrays are sized for the search).  Fast mode: the game's arena was full at an
 #                       expansion or a re-root -- the leaf stayed unexpanded (its value was still backed up) / the subtree that did not
 #                       fit was dropped; the search is valid, only narrower.  Sticky per slot until the slot is reset.
+ST_NAN_SCORE = 4      # the net's row for this game held a NaN or an infinity where the engine would store a prior or back up a value
+#                       (-inf LOGITS are fine: a masked move).  Set by the step that consumed the row; the offending prior or value
+#                       counts as 0 (fast mode: a row whose legal mass is not finite gets uniform priors), so every stored prior is
+#                       finite, the tree stays well-formed and the search runs to its end -- but it searched something the net never
+#                       said: a fault of the evaluator, not of the engine's arithmetic.  Other slots are untouched.
 
 
 LAZY_BEGIN = "lazy-begin"  # selfplay_turn(lazy_begin=True): the begun searches' root info comes from selfplay_begun()
@@ -740,6 +745,8 @@ class Engine:
 
     @staticmethod
     def describe_status(bits: int) -> str:
+        """The names of the status bits set in `bits` (STATUS_BITS).  Bit 4 (ST_NAN_SCORE) means the evaluator gave this game a NaN or
+        an infinity as a prior or as a value: flagged by the step that consumed the row, searched with 0 in its place."""
         return ", ".join(v for b, v in STATUS_BITS.items() if bits & b)
 
     def soft_status_bits(self) -> int:

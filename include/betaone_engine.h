@@ -60,6 +60,14 @@ enum {
 /* per-game status bits reported by bo_engine_status() */
 enum {
     BO_ST_NODE_OVERFLOW = 1, BO_ST_DEPTH_OVERFLOW = 2, BO_ST_NAN_SCORE = 4, BO_ST_PLY_OVERFLOW = 8,
+    /* BO_ST_NAN_SCORE -- non-finite evaluations.  A game is flagged when a prior the engine would store, or a value it would back up, is
+     * NaN or +-inf: a probability at a legal move of the row (BO_POLICY_PROBS; entries at other actions of a leaf's row are never
+     * read), a softmax term whose row maximum or sum is not finite (BO_POLICY_LOGITS: one NaN or +inf logit, a row of -inf only; single
+     * -inf logits are legitimate and give probability 0), a root prior after the noise renormalisation, a leaf's value.  The bit is set
+     * by the bo_step / bo_step_heads call that consumes the row, not by a later selection.  The offender counts as 0.0f (fast mode: a
+     * legal mass that is not finite gives uniform priors, like a mass of 0), so every stored prior is finite, every node's move comes
+     * from its own parent's legal moves without duplicates among siblings, the search runs to its end, and other slots are untouched.
+     * Finite rows are never flagged.  (A selection that meets NaN scores all the same still sets the bit, as before.) */
     BO_ST_ILLEGAL_ACTION = 16, BO_ST_UL_OVERFLOW = 32, BO_ST_TRK_OVERFLOW = 64,
     BO_ST_BAD_RANGE = 128,  /* (ABI 8) bo_games_reset_dev: the slot's positions are not inside the array */
     BO_ST_PI_OVERFLOW = 256 /* (ABI 15) bo_reanalysis_result: the search's pi has more entries than the rows hold.  A condition of one

@@ -136,8 +136,8 @@ def Kcopy(k: O.Key) -> O.Key:
     return c
 
 
-def check_golden_search(backend, name):
-    entry = SEARCHES[name]
+def check_golden_search(backend, name, table=None):
+    entry = (table or SEARCHES)[name]
     case, exp = entry["case"], entry["expect"]
     eng = make_engine(backend, 1, case["config"])
     moves = " ".join(case["moves"]) or None
@@ -148,7 +148,7 @@ def check_golden_search(backend, name):
         eng.reset([0], [case["fen"]], [moves])
     s = Searcher(backend, eng)
     rng = np.random.RandomState(case["seed"])
-    res = s.search([1], [seam().eval_fn(case["scale"], case["salt"])], [rng], case["config"].get("dirichlet_alpha", 0.1))
+    res = s.search([1], [seam().eval_fn(case.get("family") or case["scale"], case["salt"])], [rng], case["config"].get("dirichlet_alpha", 0.1))
     if exp.get("raises"):
         assert res["best_idx"][0] == -1
         return
@@ -225,11 +225,12 @@ def check_golden_game(backend, name):
 
 
 # ---- many games in lock step vs the oracle (fresh inputs, not fixtures) ----------------------------------------
-def check_multi_game_vs_oracle(backend, n_games=5, plies=6, sims=60, batch=16, scale=6.0, **search_cfg):
-    """search_cfg: cpuct / widen_coeff / dirichlet_alpha / dirichlet_eps overrides (engine and oracle get the same)."""
+def check_multi_game_vs_oracle(backend, n_games=5, plies=6, sims=60, batch=16, scale=6.0, eval_fn_for=None, **search_cfg):
+    """search_cfg: cpuct / widen_coeff / dirichlet_alpha / dirichlet_eps overrides (engine and oracle get the same);
+    eval_fn_for(salt): another evaluator than the hash net's float64 softmax at `scale`."""
     from fake_model import fake_logits_values
 
-    def eval_fn_for(salt):
+    def plain_eval_fn_for(salt):
         def fn(planes):
             logits, v = fake_logits_values(planes, scale, salt)
             x = logits.astype(np.float64)
@@ -237,6 +238,7 @@ def check_multi_game_vs_oracle(backend, n_games=5, plies=6, sims=60, batch=16, s
             return (e / e.sum(axis=1, keepdims=True)).astype(np.float32), v
         return fn
 
+    eval_fn_for = eval_fn_for or plain_eval_fn_for
     cfg = dict(num_simulations=sims, batch_size=batch, max_game_moves=plies, **search_cfg)
     eng = make_engine(backend, n_games, cfg)
     eng.reset(list(range(n_games)))

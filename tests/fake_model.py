@@ -43,8 +43,22 @@ def planes_hash(planes: np.ndarray) -> np.ndarray:
         return (xi * _W[None, :]).sum(axis=1, dtype=np.uint64)
 
 
-def fake_logits_values(planes: np.ndarray, scale: float = 6.0, salt: int = 0):
+# Evaluation families of the degenerate-row tests (tests/degenerate_eval_cases.py): what a trained net hands the tree step and the
+# plain hash net never does.  `family=None` leaves the bits of every earlier caller unchanged.
+#   peak          logits spread over 400: a float32 softmax gives exact zeros and denormals at legal moves
+#   illegal_mass  scale 6 with +300 on eight actions that leave the board (from a1 southwards, from h8 northwards: legal in no
+#                 position at all), so every legal prior is exactly 0
+#   v_pm1         value = sign(v): evaluations of exactly +-1
+#   v_zero        value = +0.0 where v > 0, otherwise -0.0
+FAMILIES = ("peak", "illegal_mass", "v_pm1", "v_zero")
+ILLEGAL_MASS_ACTIONS = (28, 29, 30, 31, 63 * 73, 63 * 73 + 1, 63 * 73 + 2, 63 * 73 + 3)
+
+
+def fake_logits_values(planes: np.ndarray, scale: float = 6.0, salt: int = 0, family=None):
     """planes[B,120,8,8] -> (logits f32[B,4672], values f32[B])."""
+    if family is not None:
+        assert family in FAMILIES, family
+        scale = 400.0 if family == "peak" else 6.0
     h = planes_hash(planes) ^ np.uint64(salt)
     a = np.arange(NUM_ACTIONS, dtype=np.uint64)
     with np.errstate(over="ignore"):
@@ -53,7 +67,26 @@ def fake_logits_values(planes: np.ndarray, scale: float = 6.0, salt: int = 0):
     logits = ((u - 0.5) * scale).astype(np.float32)
     zv = _splitmix64(h ^ np.uint64(0xABCDEF0123456789))
     v = ((zv >> np.uint64(40)).astype(np.float64) / float(1 << 24) * 2.0 - 1.0) * 0.9
-    return logits, v.astype(np.float32)
+    v = v.astype(np.float32)
+    if family == "illegal_mass":
+        logits[:, list(ILLEGAL_MASS_ACTIONS)] += np.float32(300.0)
+    elif family == "v_pm1":
+        v = np.sign(v).astype(np.float32)
+    elif family == "v_zero":
+        v = np.where(v > 0, np.float32(0.0), np.float32(-0.0)).astype(np.float32)
+    return logits, v
+
+
+def family_eval(family, salt: int):
+    """planes -> (torch.softmax of the family's logits in float32, values): the evaluator the degenerate-row tests hand to the
+    engine and to the oracle alike."""
+    import torch
+
+    def fn(planes):
+        logits, v = fake_logits_values(planes, salt=salt, family=family)
+        return torch.softmax(torch.from_numpy(logits), dim=1).numpy(), v
+
+    return fn
 
 
 def planes_key(planes_row: np.ndarray) -> str:
@@ -64,15 +97,17 @@ def planes_key(planes_row: np.ndarray) -> str:
 class FakeNet:
     """torch-module-like callable: model(x) -> (logits[B,4672], value[B,1]) as torch tensors."""
 
-    def __init__(self, scale: float = 6.0, salt: int = 0):
-        self.scale, self.salt = scale, salt
+    def __init__(self, scale: float = 6.0, salt: int = 0, family=None):
+        self.scale, self.salt, self.family = scale, salt, family
+        # the model's part of a seam key: a family's name where a plain net has its scale, so the two cannot collide
+        self.model_id = f"{scale}:{salt}" if family is None else f"{family}:{salt}"
         self.calls = []
 
     def __call__(self, x):
         import torch
 
         planes = x.detach().cpu().numpy()
-        logits, v = fake_logits_values(planes, self.scale, self.salt)
+        logits, v = fake_logits_values(planes, self.scale, self.salt, self.family)
         self.calls.append(planes.shape[0])
         return torch.from_numpy(logits), torch.from_numpy(v).unsqueeze(1)
 

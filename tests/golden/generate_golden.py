@@ -18,6 +18,8 @@ Outputs (tests/golden/):
   g4_codec.json     utils.test_move_indexing error counts + legal move -> index tables
   g5_long_games.json / g5_long_evals.npz   two full-length games of the reference (120 plies from the start position; fullmove 28 to the
                     end by rule) with their seam -- `--long` regenerates only these
+  g8_degenerate_searches.json / g8_degenerate_evals.npz   four searches on the rows a trained net produces (fake_model.FAMILIES: exact-zero
+                    and denormal priors, no legal mass, values of exactly +-1 and +-0) with their seam -- `--degenerate` regenerates only these
 
 Nothing here travels to the GPU box except the outputs; tests never read /root/reference.
 """
@@ -84,7 +86,7 @@ _real_softmax = torch.softmax
 class RecordingModel:
     def __init__(self, inner):
         self.inner = inner
-        _last_input["model"] = f"{inner.scale}:{inner.salt}"
+        _last_input["model"] = inner.model_id
 
     def __call__(self, x):
         _last_input["planes"] = x.detach().cpu().numpy().copy()
@@ -196,7 +198,7 @@ def build_context(fen, moves, uci_style=False):
 
 def run_search_case(case):
     set_config(case["config"])
-    model = RecordingModel(FakeNet(scale=case["scale"], salt=case["salt"]))
+    model = RecordingModel(FakeNet(scale=case["scale"], salt=case["salt"], family=case.get("family")))
     board, history, tracker = build_context(case["fen"], case["moves"], case.get("uci_style", False))
     np.random.seed(case["seed"])
     random.seed(case["seed"])
@@ -423,14 +425,8 @@ LONG_GAME_CASES = [
 ]
 
 
-def gen_g5():
-    EVALS.clear()
-    PROB_HASH.clear()
-    games = []
-    for case in LONG_GAME_CASES:
-        exp = run_game_case(case)
-        games.append(dict(case=case, expect=exp))
-        print(f"[g5] {case['name']}: records={exp.get('n_records')} last z={exp.get('z', [])[-2:]} moves={' '.join(exp.get('moves', [])[-6:])}")
+def write_seam(name):
+    """EVALS -> one compressed seam table: root rows whole, leaf rows at the indices the reference read."""
     full = sorted(k for k in EVALS if EVALS[k][2])
     sparse = sorted(k for k in EVALS if not EVALS[k][2])
     ptr, idx, val = [0], [], []
@@ -439,17 +435,61 @@ def gen_g5():
         idx.append(ii)
         val.append(EVALS[k][0][ii])
         ptr.append(ptr[-1] + len(ii))
-    np.savez_compressed(os.path.join(OUT, "g5_long_evals.npz"),
+    np.savez_compressed(os.path.join(OUT, name),
                         full_keys=np.array(full), full_probs=np.stack([EVALS[k][0] for k in full]),
                         full_values=np.array([EVALS[k][1] for k in full], np.float32),
                         sparse_keys=np.array(sparse), sparse_ptr=np.array(ptr, np.int64),
                         sparse_idx=np.concatenate(idx), sparse_val=np.concatenate(val),
                         sparse_values=np.array([EVALS[k][1] for k in sparse], np.float32))
+    return len(full) + len(sparse)
+
+
+def gen_g5():
+    EVALS.clear()
+    PROB_HASH.clear()
+    games = []
+    for case in LONG_GAME_CASES:
+        exp = run_game_case(case)
+        games.append(dict(case=case, expect=exp))
+        print(f"[g5] {case['name']}: records={exp.get('n_records')} last z={exp.get('z', [])[-2:]} moves={' '.join(exp.get('moves', [])[-6:])}")
+    n_evals = write_seam("g5_long_evals.npz")
     json.dump(games, open(os.path.join(OUT, "g5_long_games.json"), "w"), indent=0)
-    print(f"[g5] {len(full) + len(sparse)} evals, {len(games)} games")
+    print(f"[g5] {n_evals} evals, {len(games)} games")
+
+
+# Degenerate rows (fake_model.FAMILIES): what the hash net never gives the tree and a trained net does.  One search per family, the
+# unmodified reference on each; widen 4.0 without noise keeps the raw zero and denormal priors in the tree, alpha 0.1 takes the root's
+# renormalisation over no legal mass (sum + 1e-12).  Their own files: the earlier fixtures stay byte-identical.
+KIWIPETE = "r3k2r/p1ppqpb1/bn2pnp1/3PN3/1p2P3/2N2Q1p/PPPBBPPP/R3K2R w KQkq - 0 1"
+DEGENERATE_SEARCH_CASES = [
+    dict(name="degenerate_peak_kiwipete", fen=KIWIPETE, moves=[], seed=40, scale=400.0, salt=32, family="peak",
+         config=dict(num_simulations=120, batch_size=8, widen_coeff=4.0, dirichlet_alpha=0.0)),
+    dict(name="degenerate_illegal_mass_startpos", fen=chess.STARTING_FEN, moves=[], seed=41, scale=6.0, salt=31, family="illegal_mass",
+         config=dict(num_simulations=120, batch_size=8, widen_coeff=1.5, dirichlet_alpha=0.1)),
+    dict(name="degenerate_v_pm1_startpos", fen=chess.STARTING_FEN, moves=[], seed=42, scale=6.0, salt=31, family="v_pm1",
+         config=dict(num_simulations=120, batch_size=8, widen_coeff=4.0, dirichlet_alpha=0.1)),
+    dict(name="degenerate_v_zero_kiwipete", fen=KIWIPETE, moves=[], seed=43, scale=6.0, salt=32, family="v_zero",
+         config=dict(num_simulations=120, batch_size=8, widen_coeff=1.5, dirichlet_alpha=0.1)),
+]
+
+
+def gen_g8():
+    EVALS.clear()
+    PROB_HASH.clear()
+    searches = []
+    for case in DEGENERATE_SEARCH_CASES:
+        exp = run_search_case(case)
+        searches.append(dict(case=case, expect=exp))
+        print(f"[g8] {case['name']}: nodes={exp.get('n_nodes')} batches={len(exp.get('batches', []))} best={exp.get('best')}")
+    n_evals = write_seam("g8_degenerate_evals.npz")
+    json.dump(searches, open(os.path.join(OUT, "g8_degenerate_searches.json"), "w"), indent=0)
+    print(f"[g8] {n_evals} evals, {len(searches)} searches")
 
 
 if __name__ == "__main__":
+    if "--degenerate" in sys.argv:  # only the degenerate-row searches (the other fixtures are left as they are)
+        gen_g8()
+        sys.exit(0)
     if "--long" in sys.argv:  # only the full-length games (the other fixtures are left as they are)
         gen_g5()
         sys.exit(0)
@@ -457,3 +497,4 @@ if __name__ == "__main__":
     gen_g2()
     gen_g1()
     gen_g5()
+    gen_g8()

@@ -18,8 +18,9 @@ class SeamTable:
     them when the fixtures were generated (tests/golden/generate_golden.py)."""
 
     def __init__(self):
-        # g2: the round-1 searches and short games; g5: the two full-length games (generate_golden.py --long)
-        zs = [np.load(os.path.join(GOLD, f)) for f in ("g2_evals.npz", "g5_long_evals.npz")]
+        # g2: the round-1 searches and short games; g5: the two full-length games (generate_golden.py --long); g8: the searches on
+        # degenerate rows (--degenerate), whose keys carry a family name where the others carry a scale
+        zs = [np.load(os.path.join(GOLD, f)) for f in ("g2_evals.npz", "g5_long_evals.npz", "g8_degenerate_evals.npz")]
         cat = lambda key: np.concatenate([z[key] for z in zs])
         self.full = {k: i for i, k in enumerate(cat("full_keys").tolist())}
         self.full_probs, self.full_values = cat("full_probs"), cat("full_values")
@@ -34,7 +35,8 @@ class SeamTable:
         self.ptr = np.concatenate(ptrs + [np.array([base], np.int64)])
         self.misses = []
 
-    def lookup(self, planes_row: np.ndarray, scale: float, salt: int):
+    def lookup(self, planes_row: np.ndarray, scale, salt: int):
+        """scale: the fake net's scale, or the name of its family (fake_model.FAMILIES)"""
         k = f"{planes_key(planes_row)}:{scale}:{salt}"
         if k in self.full:
             i = self.full[k]
@@ -48,7 +50,7 @@ class SeamTable:
         self.misses.append(k)
         raise KeyError(f"position not in the golden seam table (encoding differs from the reference?): {k}")
 
-    def eval_fn(self, scale: float, salt: int):
+    def eval_fn(self, scale, salt: int):
         def fn(planes: np.ndarray):
             n = planes.shape[0]
             probs = np.zeros((n, NUM_ACTIONS), dtype=np.float32)
@@ -62,6 +64,10 @@ class SeamTable:
 
 def load_searches():
     return json.load(open(os.path.join(GOLD, "g2_searches.json")))
+
+
+def load_degenerate_searches():
+    return json.load(open(os.path.join(GOLD, "g8_degenerate_searches.json")))
 
 
 def load_games():

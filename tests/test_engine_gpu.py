@@ -62,14 +62,20 @@ def test_select_wide_matches_numpy_reference(backend):
         assert (leaf[t], levels[t]) == (el, ev), t
 
 
-def test_in_kernel_softmax_close_to_torch(backend):
-    """policy_kind LOGITS: the engine's own softmax (hardware exp, the seam is NOT shared here) -- priors within
-    1e-5 relative of torch.softmax (north-star tolerance: 1e-4), visit counts identical for well-separated logits."""
+def in_kernel_softmax_vs_torch(masked):
+    """policy_kind LOGITS against torch.softmax of the same logits; masked: -inf at every odd action (half of the legal moves of any
+    position: a masked move has probability 0 and is no fault -- the status stays 0)."""
     import torch
     from betaone_amd import engine as E
     from engine_harness import Buf, make_engine, canonical_tree
     from fake_model import fake_logits_values
     from oracle import oracle as O
+
+    def net_logits(planes):
+        logits, v = fake_logits_values(planes, 6.0, 77)
+        if masked:
+            logits[:, 1::2] = -np.inf
+        return logits, v
 
     cfg = dict(num_simulations=200, batch_size=32, dirichlet_alpha=0.0)
     eng = make_engine("hip", 1, cfg)
@@ -82,14 +88,15 @@ def test_in_kernel_softmax_close_to_torch(backend):
         running, _, _ = eng.poll()
         if not running:
             break
-        logits, v = fake_logits_values(nn_in.numpy(), 6.0, 77)
+        logits, v = net_logits(nn_in.numpy())
         pol.set(logits); val.set(v)
         kind = E.POLICY_LOGITS
     eng.check_status()
+    assert not eng.status_bits().any()
     got = canonical_tree(eng.debug_tree(0))
 
     def eval_fn(planes):
-        logits, v = fake_logits_values(planes, 6.0, 77)
+        logits, v = net_logits(planes)
         return torch.softmax(torch.from_numpy(logits), dim=1).numpy(), v
 
     b = O.Board(); trk = O.PyTracker(); trk.add_board(b)
@@ -101,6 +108,13 @@ def test_in_kernel_softmax_close_to_torch(backend):
         pg = np.array([got[k][2]], dtype=np.uint32).view(np.float32)[0]
         pe = np.array([exp[k][2]], dtype=np.uint32).view(np.float32)[0]
         assert abs(pg - pe) <= 1e-5 * abs(pe) + 1e-12
+    return exp
+
+
+def test_in_kernel_softmax_close_to_torch(backend):
+    """policy_kind LOGITS: the engine's own softmax (hardware exp, the seam is NOT shared here) -- priors within
+    1e-5 relative of torch.softmax (north-star tolerance: 1e-4), visit counts identical for well-separated logits."""
+    in_kernel_softmax_vs_torch(masked=False)
 
 
 def test_rollout_with_torch_net_graph_equals_eager(backend):
@@ -841,24 +855,20 @@ def test_masked_stream_runs_kernels_and_refuses_an_empty_mask(backend):
     assert ms.lib.bo_stream_create_cu_mask(0, zero, len(masks[0]), ctypes.byref(h)) != 0 and not h.value
 
 
-def test_step_heads_sees_the_bits_of_the_rows_kernel(backend):
-    """bo_step_heads (ABI 6): the evaluate stage stops behind bo_k_heads_tiles and the step kernel finishes the row it consumes.
-    Three engines search the same positions from the same head planes, one launch form each:
-      A  bo_nn_heads(softmax) -> probabilities, value -> bo_step(PROBS)      (the seam the oracle replays are recorded at)
-      B  bo_nn_heads(logits)  -> logits, value        -> bo_step(LOGITS)     (the step kernel's own softmax)
-      C  bo_nn_heads(flags 4) -> logits, partial sums -> bo_step_heads       (softmax AND value in the step kernel)
-    The three trees are the same bit for bit (visit counts, q, priors) after every search of a short game: the step kernel's softmax
-    and value are bo_k_heads_rows' operations in bo_k_heads_rows' order."""
+def step_heads_three_launch_forms(sims, plies, wp_scale, min_nodes, min_spread=None):
+    """The body of test_step_heads_sees_the_bits_of_the_rows_kernel (its docstring): three engines, one launch form each, trees compared bit
+    for bit after every search.  wp_scale: standard deviation of the policy head's weights (the spread of the logits grows with it);
+    min_spread: every row of logits must spread over more than this.  Returns form A's trees of every ply."""
     import torch
     from betaone_amd import engine as E
     from engine_harness import canonical_tree
 
     lib = E.load_hip_library()
     dev = torch.device("cuda:0")
-    G, SIMS = 8, 300
+    G, SIMS = 8, sims
     gen = torch.Generator(device="cpu").manual_seed(11)
     rnd = lambda *s, k=1.0: (torch.randn(*s, generator=gen) * k).to(dev).contiguous()
-    wp, bp = rnd(4672, 128, k=0.35), rnd(4672, k=0.5)
+    wp, bp = rnd(4672, 128, k=wp_scale), rnd(4672, k=0.5)
     w1, b1, w2, b2 = rnd(256, 2048, k=0.03), rnd(256, k=0.1), rnd(256, k=0.2), rnd(1, k=0.1)
     mix_p, mix_v = rnd(120 * 64, 128, k=0.08), rnd(120 * 64, 2048, k=0.08)
     fens = [None, "6k1/5ppp/8/8/8/8/5PPP/3R2K1 w - - 0 40", None, "r1bq1rk1/pp2bppp/2n1pn2/3p4/3P1B2/2PBPN2/PP1N1PPP/R2QK2R w KQ - 4 29",
@@ -877,6 +887,8 @@ def test_step_heads_sees_the_bits_of_the_rows_kernel(backend):
         rc = lib.bo_nn_heads(p.data_ptr(), v.data_ptr(), wp.data_ptr(), bp.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
                              out.data_ptr(), None if k == 2 else val.data_ptr(), scr.data_ptr(), G, flags, st)
         assert rc == 0, lib.bo_last_error().decode()
+        if k == 1 and min_spread is not None:  # (form B's `out` holds the logits)
+            assert float((out.max(dim=1).values - out.min(dim=1).values).min()) > min_spread
         if k == 2:
             engs[k].step_heads(out.data_ptr(), scr.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), G, nn_in[k].data_ptr(), st)
         else:
@@ -889,7 +901,8 @@ def test_step_heads_sees_the_bits_of_the_rows_kernel(backend):
     for e in engs:
         e.reset(list(range(G)), fens)
     rng = [np.random.RandomState(5) for _ in range(3)]
-    for ply in range(5):
+    all_trees = []
+    for ply in range(plies):
         trees = []
         for k, e in enumerate(engs):
             nl, term, _ = e.root_info()
@@ -909,7 +922,8 @@ def test_step_heads_sees_the_bits_of_the_rows_kernel(backend):
             acts = np.where(go != 0, res["best_idx"], -1).astype(np.int32)
             e.play(acts, st)
         (ta, ra), (tb, rb), (tc, rc_) = trees
-        assert max(len(t) for t in ta) > 40
+        assert max(len(t) for t in ta) > min_nodes
+        all_trees.append(ta)
         for g in range(G):
             assert ta[g] == tb[g], (ply, g, "the step kernel's softmax differs from bo_k_heads_rows'")
             assert tb[g] == tc[g], (ply, g, "the step kernel's value differs from bo_k_heads_rows'")
@@ -918,3 +932,15 @@ def test_step_heads_sees_the_bits_of_the_rows_kernel(backend):
         assert ra["val"].view(np.uint32).tolist() == rb["val"].view(np.uint32).tolist() == rc_["val"].view(np.uint32).tolist()
     for e in engs:
         e.close()
+    return all_trees
+
+
+def test_step_heads_sees_the_bits_of_the_rows_kernel(backend):
+    """bo_step_heads (ABI 6): the evaluate stage stops behind bo_k_heads_tiles and the step kernel finishes the row it consumes.
+    Three engines search the same positions from the same head planes, one launch form each:
+      A  bo_nn_heads(softmax) -> probabilities, value -> bo_step(PROBS)      (the seam the oracle replays are recorded at)
+      B  bo_nn_heads(logits)  -> logits, value        -> bo_step(LOGITS)     (the step kernel's own softmax)
+      C  bo_nn_heads(flags 4) -> logits, partial sums -> bo_step_heads       (softmax AND value in the step kernel)
+    The three trees are the same bit for bit (visit counts, q, priors) after every search of a short game: the step kernel's softmax
+    and value are bo_k_heads_rows' operations in bo_k_heads_rows' order."""
+    step_heads_three_launch_forms(sims=300, plies=5, wp_scale=0.35, min_nodes=40)
