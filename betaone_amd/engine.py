@@ -32,6 +32,10 @@ ST_PI_OVERFLOW = 256  # bo_reanalysis_result: a condition of one record (its sta
 ST_NODE_OVERFLOW = 1  # reference mode: a fault (the node arrays are sized for the search).  Fast mode: the game's arena was full at an
 #                       expansion or a re-root -- the leaf stayed unexpanded (its value was still backed up) / the subtree that did not
 #                       fit was dropped; the search is valid, only narrower.  Sticky per slot until the slot is reset.
+ST_DEPTH_OVERFLOW = 2  # fast mode, the path cap: a descent whose path already held 64 nodes (the root included) ended at the child it chose,
+#                       expanded or not; the visit was backed up as a draw (0.0) over those 64 nodes and counted as a terminal simulation,
+#                       the child's state did not change.  The search delivers all its simulations and pi sums to 1.  Sticky per slot
+#                       until the slot is reset.  Unlike a full arena this is NOT among soft_status_bits(): check_status() raises on it.
 ST_NAN_SCORE = 4      # the net's row for this game held a NaN or an infinity where the engine would store a prior or back up a value
 #                       (-inf LOGITS are fine: a masked move).  Set by the step that consumed the row; the offending prior or value
 #                       counts as 0 (fast mode: a row whose legal mass is not finite gets uniform priors), so every stored prior is

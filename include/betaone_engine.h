@@ -68,6 +68,13 @@ enum {
      * legal mass that is not finite gives uniform priors, like a mass of 0), so every stored prior is finite, every node's move comes
      * from its own parent's legal moves without duplicates among siblings, the search runs to its end, and other slots are untouched.
      * Finite rows are never flagged.  (A selection that meets NaN scores all the same still sets the bit, as before.) */
+    /* BO_ST_DEPTH_OVERFLOW in FAST mode -- the path cap.  A descent's path holds at most 64 nodes, the root included.  A descent whose
+     * path already holds 64 nodes ends at the child it chose last, even though that child is expanded: the visit is backed up as a
+     * draw (0.0) over those 64 nodes, with the step's other simulations and in their order, and is counted among the terminal
+     * simulations; the child's state does not change, so later descents may go on ending there.  The search delivers all its
+     * simulations and pi is a distribution over the legal moves.  The bit is set in the step that cut the descent short and stays set
+     * until the slot is reset.  Callers that check the status words (Engine.check_status) treat it as a fault today -- unlike a
+     * full arena (BO_ST_NODE_OVERFLOW), which they count as a condition of one search. */
     BO_ST_ILLEGAL_ACTION = 16, BO_ST_UL_OVERFLOW = 32, BO_ST_TRK_OVERFLOW = 64,
     BO_ST_BAD_RANGE = 128,  /* (ABI 8) bo_games_reset_dev: the slot's positions are not inside the array */
     BO_ST_PI_OVERFLOW = 256 /* (ABI 15) bo_reanalysis_result: the search's pi has more entries than the rows hold.  A condition of one

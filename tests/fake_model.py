@@ -50,15 +50,21 @@ def planes_hash(planes: np.ndarray) -> np.ndarray:
 #                 position at all), so every legal prior is exactly 0
 #   v_pm1         value = sign(v): evaluations of exactly +-1
 #   v_zero        value = +0.0 where v > 0, otherwise -0.0
+# A policy family combines with a value family through `value=` (tests/fast_degenerate_cases.py): "v_pm1", "v_zero", or
+#   v_m1          value = -1 at every row: whoever moved into a leaf sees +1, so a step's descents all follow one line
+# and `peak_scale` sharpens the peak family further (one legal move holds all the mass: a search that runs down a single line).
 FAMILIES = ("peak", "illegal_mass", "v_pm1", "v_zero")
+POLICY_FAMILIES, VALUE_FAMILIES = ("peak", "illegal_mass"), ("v_pm1", "v_zero", "v_m1")
 ILLEGAL_MASS_ACTIONS = (28, 29, 30, 31, 63 * 73, 63 * 73 + 1, 63 * 73 + 2, 63 * 73 + 3)
 
 
-def fake_logits_values(planes: np.ndarray, scale: float = 6.0, salt: int = 0, family=None):
+def fake_logits_values(planes: np.ndarray, scale: float = 6.0, salt: int = 0, family=None, value=None, peak_scale: float = 400.0):
     """planes[B,120,8,8] -> (logits f32[B,4672], values f32[B])."""
     if family is not None:
         assert family in FAMILIES, family
-        scale = 400.0 if family == "peak" else 6.0
+        scale = peak_scale if family == "peak" else 6.0
+    if value is not None:
+        assert family in (None,) + POLICY_FAMILIES and value in VALUE_FAMILIES, (family, value)
     h = planes_hash(planes) ^ np.uint64(salt)
     a = np.arange(NUM_ACTIONS, dtype=np.uint64)
     with np.errstate(over="ignore"):
@@ -70,20 +76,23 @@ def fake_logits_values(planes: np.ndarray, scale: float = 6.0, salt: int = 0, fa
     v = v.astype(np.float32)
     if family == "illegal_mass":
         logits[:, list(ILLEGAL_MASS_ACTIONS)] += np.float32(300.0)
-    elif family == "v_pm1":
+    value = family if value is None else value
+    if value == "v_pm1":
         v = np.sign(v).astype(np.float32)
-    elif family == "v_zero":
+    elif value == "v_zero":
         v = np.where(v > 0, np.float32(0.0), np.float32(-0.0)).astype(np.float32)
+    elif value == "v_m1":
+        v = np.full_like(v, -1.0)
     return logits, v
 
 
-def family_eval(family, salt: int):
+def family_eval(family, salt: int, value=None, peak_scale: float = 400.0):
     """planes -> (torch.softmax of the family's logits in float32, values): the evaluator the degenerate-row tests hand to the
     engine and to the oracle alike."""
     import torch
 
     def fn(planes):
-        logits, v = fake_logits_values(planes, salt=salt, family=family)
+        logits, v = fake_logits_values(planes, salt=salt, family=family, value=value, peak_scale=peak_scale)
         return torch.softmax(torch.from_numpy(logits), dim=1).numpy(), v
 
     return fn

@@ -14,6 +14,7 @@ from oracle import oracle as O
 
 F = np.float32
 PATH_CAP = 64
+RCP_TAB = 256  # the kernel's reciprocal table holds RN(1 / k) for k < 256: a child with n_eff > 254 needs an entry it does not have
 UNVISITED, MATE, DRAW, EXPANDED = "unvisited", "mate", "draw", "expanded"
 
 
@@ -45,6 +46,17 @@ class FastSearcher:
         self.cp, self.keep, self.eps, self.use_noise, self.reuse = F(cpuct), F(1.0 - eps), eps, use_noise, reuse
         self.root = Node(1.0, None)
         self.n_evals = self.n_term_sims = 0
+        # the path cap (include/betaone_engine.h, BO_ST_DEPTH_OVERFLOW): set once a descent was cut short, and how many were
+        self.depth_overflow, self.n_depth_overflows = False, 0
+        # what the searches so far exercised; the tests assert their preconditions on these:
+        #   levels / tie_levels  scored levels, and those whose best score was held by more than one child
+        #   max_n_eff            largest n + in-flight count of a scored child (255 and more: beyond the reciprocal table)
+        #   max_sharing          most earlier descents of a step in flight through one scored child
+        #   max_parent_visits    largest n + in-flight count of a node whose children were scored (4096 and more: beyond the sqrt table)
+        #   max_path             longest path, in nodes, the root included
+        #   rcp_clamp_flips      levels with a child beyond the reciprocal table at which the table's last entries, used in place of
+        #                        the exact reciprocals, would have chosen another child (what a kernel without its side path does)
+        self.stats = dict(levels=0, tie_levels=0, max_n_eff=0, max_sharing=0, max_parent_visits=0, max_path=0, rcp_clamp_flips=0)
 
     # -- helpers ------------------------------------------------------------------------------------------------------
     def _hist(self):
@@ -73,6 +85,18 @@ class FastSearcher:
             pv = [F(np.float64(F(self.keep * p)) + self.eps * noise[j]) for j, p in enumerate(pv)]
         node.children = [Node(p, m) for m, p in zip(moves, pv)]
         node.state = EXPANDED
+
+    def _clamped_choice(self, cur, sq):
+        """The child a level would choose if counts beyond the reciprocal table took its last entries (for the counters only)."""
+        best, bi = -np.inf, None
+        for ch in cur.children:
+            ne = ch.n + ch.fl
+            t = min(ne, RCP_TAB - 2)
+            u = F(F(F(self.cp * ch.prior) * sq) * F(F(1.0) / F(1 + t)))
+            qv = F(F(ch.w - F(ch.fl)) * F(F(1.0) / F(t))) if ne > 0 else F(0.0)
+            if F(qv + u) > best:
+                best, bi = F(qv + u), ch
+        return bi
 
     @staticmethod
     def _backup(path, v):
@@ -108,7 +132,8 @@ class FastSearcher:
                 path, cur = [root], root
                 while cur.state == EXPANDED and len(path) < PATH_CAP:
                     sq = np.sqrt(F(cur.n + cur.fl))  # visits of the node being expanded, this simulation included
-                    best, bi = -np.inf, None
+                    best, bi, holders = -np.inf, None, 0
+                    st = self.stats
                     for ch in cur.children:
                         ne = ch.n + ch.fl
                         we = F(ch.w - F(ch.fl))
@@ -116,13 +141,32 @@ class FastSearcher:
                         u = F(t2 * F(F(1.0) / F(1 + ne)))
                         qv = F(we * F(F(1.0) / F(ne))) if ne > 0 else F(0.0)
                         sc = F(qv + u)
-                        if sc > best:
-                            best, bi = sc, ch
+                        if sc > best:  # first maximum in child order
+                            best, bi, holders = sc, ch, 1
+                        elif sc == best:
+                            holders += 1
+                        if ne > st["max_n_eff"]:
+                            st["max_n_eff"] = ne
+                        if ch.fl > st["max_sharing"]:
+                            st["max_sharing"] = ch.fl
+                    st["levels"] += 1
+                    st["tie_levels"] += holders > 1
+                    if any(ch.n + ch.fl > RCP_TAB - 2 for ch in cur.children):
+                        st["rcp_clamp_flips"] += self._clamped_choice(cur, sq) is not bi
+                    st["max_parent_visits"] = max(st["max_parent_visits"], cur.n + cur.fl)
                     cur = bi
                     cur.fl += 1
                     path.append(cur)
-                assert cur.state != EXPANDED, "path cap not expected in tests"
-                if cur.state in (MATE, DRAW):  # known terminal: needs no row; backed up with the step's other simulations
+                self.stats["max_path"] = max(self.stats["max_path"], len(path))
+                if cur.state == EXPANDED:
+                    # The path cap: a descent whose path holds PATH_CAP nodes, the root included, ends at the child it chose.  The
+                    # visit is backed up as a draw over those PATH_CAP nodes, with the step's other simulations and in their order,
+                    # it counts as a terminal simulation, the child stays expanded, and the game is flagged.
+                    assert len(path) == PATH_CAP
+                    self.depth_overflow = True
+                    self.n_depth_overflows += 1
+                    sims_l.append((path, DRAW))
+                elif cur.state in (MATE, DRAW):  # known terminal: needs no row; backed up with the step's other simulations
                     sims_l.append((path, cur.state))
                 elif cur.row >= 0:  # already selected in this step: shares the row
                     sims_l.append((path, cur.row))
@@ -159,6 +203,24 @@ class FastSearcher:
 
     def visits(self):
         return [(ch.move, ch.n) for ch in self.root.children]
+
+    def nodes(self):
+        out, todo = [], [self.root]
+        while todo:
+            nd = todo.pop()
+            out.append(nd)
+            todo.extend(nd.children)
+        return out
+
+    def prior_counts(self):
+        """(nodes below the root whose prior is exactly 0, nodes whose prior is a binary32 denormal)"""
+        pr = np.array([nd.prior for nd in self.nodes() if nd is not self.root], np.float32)
+        return int((pr == 0).sum()), int(((pr > 0) & (pr < F(2.0 ** -126))).sum())
+
+    def granules_needed(self, records=8, header=1):
+        """Arena granules the engine needs for this tree (bo_fastw.h: the root's granule, then per expanded node a header granule
+        and its children in granules of eight records)."""
+        return 1 + sum(header + (len(nd.children) + records - 1) // records for nd in self.nodes() if nd.state == EXPANDED)
 
     def play(self, uci):
         child = next((ch for ch in self.root.children if ch.move == uci), None)

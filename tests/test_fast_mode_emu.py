@@ -65,8 +65,9 @@ def reference_for(fen, moves, fn, sims, L, **kw):
     return FastSearcher(b, trk, fn, sims, L, **kw)
 
 
-def drive_search(backend, eng, G, L, eval_fn, noise, bufs=None):
-    """One search in every slot of `eng` with an external evaluator (all rows are evaluated; stale rows are ignored)."""
+def drive_search(backend, eng, G, L, eval_fn, noise, bufs=None, check=True):
+    """One search in every slot of `eng` with an external evaluator (all rows are evaluated; stale rows are ignored).
+    check=False leaves the status check to the caller (a search that is meant to end with a status bit set)."""
     nn_in, pol, val = bufs or (Buf(backend, (G * L, 120, 8, 8)), Buf(backend, (G * L, E.NUM_ACTIONS)), Buf(backend, (G * L,)))
     eng.search_begin([1] * G, noise, nn_in.ptr)
     kind, steps = E.POLICY_NONE, 0
@@ -80,7 +81,8 @@ def drive_search(backend, eng, G, L, eval_fn, noise, bufs=None):
         pol.set(p); val.set(v)
         kind = E.POLICY_PROBS
         assert steps < 10000
-    eng.check_status()
+    if check:
+        eng.check_status()
     return steps, (nn_in, pol, val)
 
 
@@ -235,7 +237,7 @@ MULTI = [
 ]
 
 
-def run_multi(backend, L, sims, opts, seed=5):
+def run_multi(backend, L, sims, opts, seed=5, eval_fn=None):
     """Every game slot holds a different position (the half-waves and the games interleaved per half-wave of bo_k_fw_select
     then diverge in depth, run length and end of descent); returns engine + per-game noise."""
     G = len(MULTI)
@@ -247,13 +249,13 @@ def run_multi(backend, L, sims, opts, seed=5):
     noise = np.zeros((G, E.MAX_LEGAL))
     for g in range(G):
         noise[g, :nl[g]] = np.random.RandomState(seed + g).dirichlet([0.1] * int(nl[g]))
-    fn = softmax_eval(13)
+    fn = eval_fn or softmax_eval(13)
     drive_search(backend, eng, G, L, fn, noise)
     return eng, noise, fn
 
 
-def check_multi(backend, L, sims, opts):
-    eng, noise, fn = run_multi(backend, L, sims, opts)
+def check_multi(backend, L, sims, opts, eval_fn=None):
+    eng, noise, fn = run_multi(backend, L, sims, opts, eval_fn=eval_fn)
     st = eng.status()
     for g, (fen, moves) in enumerate(MULTI):
         ref = reference_for(fen, moves, fn, sims, L)
