@@ -17,6 +17,7 @@
 #include "bo_reanalyse.h"
 #include "bo_perft.h"
 #include "bo_mate.h"
+#include "bo_anchor.h"
 #include "bo_book.h"
 #include "bo_merge.h"
 #include "bo_tb.h"
@@ -3143,6 +3144,16 @@ struct PerftRun {
         }
         return rc;
     }
+    int scan(int l, int64_t n) {  // cnt -> off of level l, the total into h_word[0] (bo_mate, bo_anchor)
+        PerftLevel &L = lv[l];
+        const int nt = (int)((n + BO_PERFT_TILE - 1) / BO_PERFT_TILE);
+        RT(RT_LAUNCH(bo_k_perft_tile_sums, nt, stream, (const int32_t *)L.cnt, n, tsum));
+        RT(RT_LAUNCH(bo_k_perft_tile_scan, 1, stream, (const int32_t *)tsum, nt, tbase, L.off, n));
+        RT(RT_LAUNCH(bo_k_perft_offsets, nt, stream, (const int32_t *)L.cnt, n, (const uint64_t *)tbase, L.off));
+        RT(rt_d2h(h_word, L.off + n, 8, stream));
+        RT(rt_sync(stream));
+        return BO_OK;
+    }
 };
 
 // the subtree below entries [0, n) of level l
@@ -3326,16 +3337,6 @@ struct MateRun : PerftRun {
         if (!rc) rc = rt_malloc((void **)&keymask, N * 32);
         if (!rc) have_roots = n;
         return rc;
-    }
-    int scan(int l, int64_t n) {  // cnt -> off of level l, the total into h_word[0]
-        PerftLevel &L = lv[l];
-        const int nt = (int)((n + BO_PERFT_TILE - 1) / BO_PERFT_TILE);
-        RT(RT_LAUNCH(bo_k_perft_tile_sums, nt, stream, (const int32_t *)L.cnt, n, tsum));
-        RT(RT_LAUNCH(bo_k_perft_tile_scan, 1, stream, (const int32_t *)tsum, nt, tbase, L.off, n));
-        RT(RT_LAUNCH(bo_k_perft_offsets, nt, stream, (const int32_t *)L.cnt, n, (const uint64_t *)tbase, L.off));
-        RT(rt_d2h(h_word, L.off + n, 8, stream));
-        RT(rt_sync(stream));
-        return BO_OK;
     }
 };
 
@@ -3600,6 +3601,220 @@ extern "C" int bo_mate(int device, int32_t n_roots, const char *const *fens, con
     }
     for (size_t i = 0; i < N; i++) results[i].nodes = R.visited;
     if (n_splits) *n_splits = R.splits;
+    return BO_OK;
+}
+
+// ---- the anchor opponent on the device (bo_anchor.h) ---------------------------------------------------------------------------------
+// The walk is perft's again, with mate's order of work: a level's chunk is expanded, the chunk below is taken to the bottom, then its
+// values are backed up into the parents it came from.  Every level keeps one int16 per entry; level 0 holds the roots that have a move.
+namespace {
+struct AnchorRun : PerftRun {
+    std::vector<int16_t *> val;  // per level [have_val]
+    std::vector<int64_t> have_val;
+    // per root [n]: check bits, row in root_moves, score row [256], score, number of best moves, lowest-index best move
+    int32_t *root_chk = nullptr, *act = nullptr, *scores = nullptr, *score = nullptr, *n_best = nullptr, *best = nullptr, *n_act = nullptr;
+    uint64_t visited = 0;  // frontier entries of levels 0 .. D - 1 (include/betaone_engine.h: nodes)
+    ~AnchorRun() {
+        (void)rt_sync(stream);
+        for (int16_t *p : val) rt_free(p);
+        rt_free(root_chk); rt_free(act); rt_free(scores); rt_free(score); rt_free(n_best); rt_free(best); rt_free(n_act);
+    }
+    int room_anchor(int l, int64_t n) {
+        int rc = room(l, n);
+        if (!rc) rc = room_scan(l, n);
+        const int64_t m = lv[l].have;
+        if (rc || have_val[l] >= m) return rc;
+        rt_free(val[l]);
+        val[l] = nullptr; have_val[l] = 0;
+        rc = rt_malloc((void **)&val[l], (size_t)m * 2);
+        if (!rc) have_val[l] = m;
+        return rc;
+    }
+};
+
+int anchor_backup(AnchorRun &R, int l, int64_t a, int64_t e) {
+    PerftLevel &L = R.lv[l];
+    const int16_t *below = l + 1 < R.depth ? R.val[l + 1] : nullptr;
+    if (l == 0)
+        RT(RT_LAUNCH(bo_k_anchor_backup_root, e - a, R.stream, (const int32_t *)R.n_act, (const uint64_t *)L.off, a, below, R.scores, R.score,
+                     R.n_best, R.best, (const int32_t *)R.act, (const int32_t *)R.root_moves));
+    else
+        RT(RT_LAUNCH(bo_k_anchor_backup, e - a, R.stream, (const int32_t *)L.cnt, (const uint64_t *)L.off, a, below, R.val[l]));
+    return BO_OK;
+}
+
+// the values of entries [0, n) of level l (R.room_anchor(l, n) has been called)
+int anchor_level(AnchorRun &R, int l, int64_t n) {
+    PerftLevel &L = R.lv[l];
+    R.visited += (uint64_t)n;
+    if (l == R.depth - 1) {
+        RT(RT_LAUNCH(bo_k_anchor_leaf, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], l == 0 ? R.scores : (int32_t *)nullptr, (int32_t)l,
+                     l == 0 ? AN_ROOT : 0u));
+        return l == 0 ? anchor_backup(R, 0, 0, n) : BO_OK;
+    }
+    RT(RT_LAUNCH(bo_k_anchor_count, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], (int32_t)l));
+    int rc = R.scan(l, n);
+    if (rc) return rc;
+    int64_t left = R.h_word[0], a = 0;
+    while (a < n && left > 0) {
+        int64_t e = n, c = left;
+        if (left > R.cap) {
+            RT(RT_LAUNCH(bo_k_perft_split, 1, R.stream, (const uint64_t *)L.off, a, n, R.cap, R.d_word));
+            RT(rt_d2h(R.h_word, R.d_word, 16, R.stream));
+            RT(rt_sync(R.stream));
+            e = R.h_word[0];
+            c = R.h_word[1];
+            if (e <= a || e > n || c < 1 || c > R.cap) return fail(BO_E_STATE, "bo_anchor: the level split is inconsistent");
+            if (c < left) R.splits++;
+        }
+        RT(R.room_anchor(l + 1, c));
+        PerftLevel &C = R.lv[l + 1];
+        RT(RT_LAUNCH(bo_k_perft_expand, e - a, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (const uint64_t *)L.off, a, C.pos, C.tag,
+                     C.have, 0u));
+        rc = anchor_level(R, l + 1, c);
+        if (!rc) rc = anchor_backup(R, l, a, e);
+        if (rc) return rc;
+        left -= c;
+        a = e;
+    }
+    if (l == 0 && a < n) return fail(BO_E_STATE, "bo_anchor: a root with moves has no children");
+    return BO_OK;  // (entries behind the last child have no move: they keep the count kernel's value)
+}
+
+bool anchor_record_ok(const bo_position &q, DPos *p) {
+    const bool fields = (q.turn == 0 || q.turn == 1) && q.castling <= 0xFu && q.ep_square >= -1 && q.ep_square <= 63 && q.ep_key >= -2 && q.ep_key <= 63;
+    if (fields) *p = from_abi(q);
+    return fields && mate_position_ok(*p);
+}
+}  // namespace
+
+extern "C" int bo_anchor(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t depth, int64_t capacity,
+                         uint32_t flags, bo_anchor_result *results, int32_t *root_moves, int32_t *move_scores, int64_t *n_splits, void *stream) {
+    if (n_splits) *n_splits = 0;
+    if (n_roots < 0 || n_roots > (1 << 20) || (fens != nullptr) == (positions != nullptr))
+        return fail(BO_E_ARG, "bo_anchor: exactly one of fens and positions, n_roots <= 2^20");
+    if (depth < 1 || depth > BO_ANCHOR_MAX_DEPTH) return fail(BO_E_ARG, "bo_anchor: depth must be 1 .. 8");
+    if (capacity < BO_MAX_MOVES || capacity > ((int64_t)1 << 26))
+        return fail(BO_E_CONFIG, "bo_anchor: capacity must be 256 (the children of one position) .. 2^26 positions per level");
+    if (flags) return fail(BO_E_ARG, "bo_anchor: unknown flag bits");
+    if (n_roots && !results) return fail(BO_E_ARG, "bo_anchor: results must be given");
+    if (n_roots == 0) return BO_OK;
+    const size_t N = (size_t)n_roots;
+    std::vector<DPos> roots;     // the roots that are positions
+    std::vector<int32_t> index;  // their rows in the caller's arrays
+    roots.reserve(N); index.reserve(N);
+    memset(results, 0, N * sizeof(bo_anchor_result));
+    for (size_t i = 0; i < N; i++) {
+        DPos p;
+        results[i].best = -1;
+        if (fens) {
+            if (!pgn_fen_root(fens[i] ? fens[i] : "", &p) || !mate_position_ok(p)) return fail(BO_E_FEN, "bo_anchor: bad FEN (root " + std::to_string(i) + ")");
+        } else if (!anchor_record_ok(positions[i], &p)) { results[i].status = BO_ANCHOR_NOT_A_POSITION; continue; }
+        roots.push_back(p);
+        index.push_back((int32_t)i);
+    }
+    for (size_t i = 0; i < N * BO_MAX_MOVES; i++) {
+        if (root_moves) root_moves[i] = -1;
+        if (move_scores) move_scores[i] = INT32_MIN;
+    }
+    if (roots.empty()) return BO_OK;
+    RT(rt_set_device(device));
+    AnchorRun R;
+    R.stream = stream; R.cap = capacity; R.depth = depth;
+    R.lv.resize((size_t)depth); R.val.resize((size_t)depth, nullptr); R.have_val.resize((size_t)depth, 0);
+    RT(rt_malloc((void **)&R.d_word, 16));
+    RT(rt_host_alloc((void **)&R.h_word, 16));
+    const size_t n = roots.size();
+    DPos *d_roots = nullptr;  // (freed below on every path: the roots kernel's in-place buffer)
+    RT(rt_malloc((void **)&R.root_moves, n * BO_MAX_MOVES * 4));
+    RT(rt_malloc((void **)&R.root_n, n * 4));
+    RT(rt_malloc((void **)&R.root_chk, n * 4));
+    RT(rt_malloc((void **)&R.act, n * 4));
+    RT(rt_malloc((void **)&R.n_act, n * 4));
+    RT(rt_malloc((void **)&R.scores, n * BO_MAX_MOVES * 4));
+    RT(rt_malloc((void **)&R.score, n * 4));
+    RT(rt_malloc((void **)&R.n_best, n * 4));
+    RT(rt_malloc((void **)&R.best, n * 4));
+    RT(rt_malloc((void **)&d_roots, n * sizeof(DPos)));
+    std::vector<int32_t> moves(n * BO_MAX_MOVES), rn(n), chk(n);
+    int rc = rt_h2d(d_roots, roots.data(), n * sizeof(DPos), stream);
+    if (!rc) rc = RT_LAUNCH(bo_k_mate_roots, n, stream, d_roots, R.root_moves, R.root_n, R.root_chk);
+    if (!rc) rc = rt_d2h(roots.data(), d_roots, n * sizeof(DPos), stream);
+    if (!rc) rc = rt_d2h(moves.data(), R.root_moves, moves.size() * 4, stream);
+    if (!rc) rc = rt_d2h(rn.data(), R.root_n, n * 4, stream);
+    if (!rc) rc = rt_d2h(chk.data(), R.root_chk, n * 4, stream);
+    if (!rc) rc = rt_sync(stream);
+    rt_free(d_roots);
+    RT(rc);
+    std::vector<int32_t> active, nact;  // the roots that are searched: a position with a move
+    std::vector<DPos> sub;
+    for (size_t r = 0; r < n; r++)
+        if (!(chk[r] & 2) && rn[r] > 0) { active.push_back((int32_t)r); nact.push_back(rn[r]); sub.push_back(roots[r]); }
+    const size_t na = active.size();
+    std::vector<int32_t> sc(na * BO_MAX_MOVES), s1(na), nb(na), bm(na);
+    if (na) {
+        RT(R.room_anchor(0, (int64_t)na));
+        std::vector<int32_t> tags(na, 0);
+        RT(rt_h2d(R.lv[0].pos, sub.data(), na * sizeof(DPos), stream));
+        RT(rt_h2d(R.lv[0].tag, tags.data(), na * 4, stream));
+        RT(rt_h2d(R.act, active.data(), na * 4, stream));
+        RT(rt_h2d(R.n_act, nact.data(), na * 4, stream));
+        RT(rt_sync(stream));  // (host vectors of this frame)
+        rc = anchor_level(R, 0, (int64_t)na);
+        if (rc) return rc;
+        RT(rt_d2h(sc.data(), R.scores, sc.size() * 4, stream));
+        RT(rt_d2h(s1.data(), R.score, na * 4, stream));
+        RT(rt_d2h(nb.data(), R.n_best, na * 4, stream));
+        RT(rt_d2h(bm.data(), R.best, na * 4, stream));
+        RT(rt_sync(stream));
+    }
+    for (size_t r = 0; r < n; r++) {
+        bo_anchor_result &o = results[(size_t)index[r]];
+        if (chk[r] & 2) o.status = BO_ANCHOR_NOT_A_POSITION;
+        else if (rn[r] == 0) o.status = (chk[r] & 1) ? BO_ANCHOR_CHECKMATED : BO_ANCHOR_STALEMATED;
+        else o.n_moves = rn[r];
+    }
+    for (size_t k = 0; k < na; k++) {
+        const size_t r = (size_t)active[k], i = (size_t)index[r];
+        results[i].score = s1[k]; results[i].n_best = nb[k]; results[i].best = bm[k];
+        for (int j = 0; j < rn[r]; j++) {
+            if (root_moves) root_moves[i * BO_MAX_MOVES + (size_t)j] = moves[r * BO_MAX_MOVES + (size_t)j];
+            if (move_scores) move_scores[i * BO_MAX_MOVES + (size_t)j] = sc[k * BO_MAX_MOVES + (size_t)j];
+        }
+    }
+    for (size_t i = 0; i < N; i++) results[i].nodes = R.visited;
+    if (n_splits) *n_splits = R.splits;
+    return BO_OK;
+}
+
+extern "C" int bo_anchor_eval(int device, int32_t n, const bo_position *positions, int32_t *ev_out, void *stream) {
+    if (n < 0 || n > (1 << 24) || (n && (!positions || !ev_out))) return fail(BO_E_ARG, "bo_anchor_eval: positions and ev_out must be given, n <= 2^24");
+    if (n == 0) return BO_OK;
+    std::vector<DPos> pos;
+    std::vector<int32_t> index;
+    for (int32_t i = 0; i < n; i++) {
+        DPos p;
+        ev_out[i] = INT32_MIN;
+        if (!anchor_record_ok(positions[i], &p)) continue;
+        pos.push_back(p);
+        index.push_back(i);
+    }
+    if (pos.empty()) return BO_OK;
+    RT(rt_set_device(device));
+    const size_t m = pos.size();
+    DPos *d_pos = nullptr;
+    int32_t *d_out = nullptr;
+    std::vector<int32_t> out(m);
+    int rc = rt_malloc((void **)&d_pos, m * sizeof(DPos));
+    if (!rc) rc = rt_malloc((void **)&d_out, m * 4);
+    if (!rc) rc = rt_h2d(d_pos, pos.data(), m * sizeof(DPos), stream);
+    if (!rc) rc = RT_LAUNCH(bo_k_anchor_eval, m, stream, (const DPos *)d_pos, d_out);
+    if (!rc) rc = rt_d2h(out.data(), d_out, m * 4, stream);
+    const int rs = rt_sync(stream);
+    rt_free(d_pos); rt_free(d_out);
+    RT(rc);
+    RT(rs);
+    for (size_t k = 0; k < m; k++) ev_out[index[k]] = out[k];
     return BO_OK;
 }
 

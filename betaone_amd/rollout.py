@@ -219,6 +219,8 @@ class Rollout:
         # simulations (a root kept from the previous search needs no evaluation of its own; a fresh one costs one more round)
         self.expected_evals = math.ceil(self.S / self.L) if self.fast else 1 + math.ceil(self.S / self.B)
         self.games: List[Optional[GameState]] = [None] * self.G
+        # the host-made turn's hook for moves made outside the search (anchor.AnchorRollout): None = today's code path exactly
+        self.external_moves: Optional[Callable] = None
         self.use_graph = bool(use_graph) and self.device.type == "cuda"
         # close_last_eval: on where the iterations run as captured graphs -- the product path.  The eager loop (use_graph=False) is the
         # path on which a caller watches every evaluation (seam recordings replayed through the oracle, which evaluates every leaf as
@@ -528,6 +530,8 @@ class Rollout:
             if while_searching is not None:
                 while_searching()
             return 0
+        if self.external_moves is not None:
+            return self._play_ply_external(go, n_legal, terminal, while_searching)
         res = self.search(go, n_legal, terminal)
         rv = self.eng.search_root_value(self._stream()) if self.values else None
         resigned = self._resign_decide(go, rv, np.array([0 if gs is None else gs.plies for gs in self.games], np.int64))
@@ -552,6 +556,39 @@ class Rollout:
         if while_searching is not None:
             while_searching()
         n_moves = int(np.count_nonzero(go & ~resigned))
+        self.n_plies += n_moves
+        return n_moves
+
+    def _play_ply_external(self, live, n_legal, terminal, while_searching) -> int:
+        """The rest of the host-made turn when `external_moves` is set (anchor.AnchorRollout): external_moves(live) -> (mask [G],
+        actions [G]) names the live slots whose move somebody else makes and that move's action index; the other live slots are searched
+        and sampled as always, and all moves go out in one eng.play.  An externally moved ply has an empty pi (and no root value)."""
+        if self.values:
+            raise ValueError("Rollout: external_moves does not go with resignation or root values")
+        mask, ext = self.external_moves(live)
+        mask = np.asarray(mask, bool) & (live != 0)
+        go = (live != 0) & ~mask
+        actions = np.full(self.G, -1, dtype=np.int32)
+        if go.any():
+            res = self.search(go.astype(np.int32), n_legal, terminal)
+        t0 = time.perf_counter()
+        th, ti, tf = self.temperature
+        for g in np.nonzero(live)[0]:
+            gs = self.games[g]
+            if mask[g]:
+                actions[g] = int(ext[g])
+                gs.pis.append((np.zeros(0, np.int32), np.zeros(0, np.float32)))
+            else:
+                n = int(res["n"][g])
+                idx, val = res["idx"][g, :n].copy(), res["val"][g, :n].copy()
+                actions[g] = sampling.select_action_sparse(idx, val, gs.fullmove_number(), gs.rng, th, ti, tf)
+                gs.pis.append((idx, val))
+            gs.plies += 1
+        self.host_seconds += time.perf_counter() - t0
+        self.eng.play(actions, self._stream())
+        if while_searching is not None:
+            while_searching()
+        n_moves = int(np.count_nonzero(live))
         self.n_plies += n_moves
         return n_moves
 

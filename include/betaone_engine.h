@@ -38,10 +38,11 @@ extern "C" {
  * 3 / 4 / 5, bo_root_info's terminal code 3 -- additions only; 15: reanalysis of self-play records -- bo_records_ring,
  * bo_reanalysis_result, status bit BO_ST_PI_OVERFLOW -- additions only; 16: opening books -- bo_book_insert -- addition only;
  * 18: board symmetries in the replay samplers -- bo_replay_sample_sym, _sparse_sym, _sparse_q_sym, _merged_sym -- additions only;
- * 19: forced mates on the device -- bo_mate, bo_mate_result -- additions only).
+ * 19: forced mates on the device -- bo_mate, bo_mate_result -- additions only; 20: the anchor opponent -- bo_anchor, bo_anchor_eval,
+ * bo_anchor_result -- additions only).
  * A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 19
+#define BO_ABI_VERSION 20
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -1029,6 +1030,45 @@ typedef struct bo_mate_result {
 } bo_mate_result;
 int bo_mate(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t max_moves, int64_t capacity,
             uint64_t max_nodes, uint32_t flags, bo_mate_result *results, int32_t *key_moves, int32_t *pv, int64_t *n_splits, void *stream);
+
+/* ---- (ABI 20, additions) the anchor opponent on the device: csrc/bo_anchor.h, betaone_amd/anchor.py ----------------------------------
+ * A deterministic classical player: a fixed-depth FULL-WIDTH negamax with a small integer static evaluation (DESIGN.md "Anchor
+ * opponent"), for whole batches of roots.  Draw rules are IGNORED inside the tree, as in perft and bo_mate: only a position without
+ * legal moves ends a line.  With p the plies below the root and D = depth:
+ *   val(P, p) = -(BO_ANCHOR_MATE - p) if P has no legal move and is in check, 0 if it has none and is not;
+ *               ev(P) if p == D;  the maximum over the moves m of -val(P.m, p + 1) otherwise.
+ * ev(P), centipawns from the side to move's view = the terms of its men minus the terms of the other side's.  For a man on file index
+ * f and rank index r counted from its owner's back rank, e = min(f, 7 - f), d = e + min(r, 7 - r): pawn 100 + 2 (r - 1)^2 + 3 e;
+ * knight 300 + 8 d; bishop 320 + 4 d; rook 500, + 20 if r == 6; queen 900 + 2 d; king 8 d if no queen of either colour is on the
+ * board, else -6 r.  |ev| < 15000; every value fits an int16.
+ * Per root: move_scores[i] = -val(root.m_i, 1) in the generator's order; score = their maximum (a mate in 1 scores
+ * BO_ANCHOR_MATE - 1); best = the lowest-index move that reaches it; n_best = how many do.  Engine-less; SYNCHRONISES `stream` and
+ * allocates and frees its own device memory, as bo_mate does.
+ *
+ * Roots, "not a position", n_roots and capacity: exactly as for bo_mate.  depth: 1 .. BO_ANCHOR_MAX_DEPTH.  flags: none defined (0).
+ * nodes: the frontier entries of levels 0 .. depth - 1 of the whole call (the positions whose move lists a level's kernel generated;
+ * the children the last level makes and evaluates are not entries), the same in every result and at every capacity.
+ * root_moves, move_scores (each may be NULL) [n_roots][BO_MAX_LEGAL]: entries beyond n_moves are -1 and INT32_MIN.
+ * Arguments are checked in this order, before any device call: n_roots out of range or both / neither of fens and positions
+ * (BO_E_ARG); depth out of range (BO_E_ARG); capacity (BO_E_CONFIG); flag bits (BO_E_ARG); results NULL with n_roots > 0 (BO_E_ARG).
+ *
+ * bo_anchor_eval: ev_out[i] = ev(positions[i]) (HOST memory both), one wave per position; INT32_MIN for a record that is not a
+ * position by the host-side rules above.  n <= 2^24; n == 0 does nothing.  Synchronises. */
+enum { BO_ANCHOR_OK = 0, BO_ANCHOR_CHECKMATED = 1, BO_ANCHOR_STALEMATED = 2, BO_ANCHOR_NOT_A_POSITION = 3 };
+#define BO_ANCHOR_MAX_DEPTH 8
+#define BO_ANCHOR_MATE 30000
+typedef struct bo_anchor_result {
+    int32_t status;               /* BO_ANCHOR_*: ok; the root's side to move is checkmated / stalemated; not a position */
+    int32_t score;                /* the maximum of the move scores (0 unless status is ok) */
+    int32_t best;                 /* the lowest-index move that reaches it (from | to << 6 | promo << 12), -1 none */
+    int32_t n_best;               /* moves that reach it */
+    int32_t n_moves;              /* legal moves of the root */
+    int32_t reserved;             /* 0 */
+    uint64_t nodes;               /* of the whole call, see above */
+} bo_anchor_result;
+int bo_anchor(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t depth, int64_t capacity,
+              uint32_t flags, bo_anchor_result *results, int32_t *root_moves, int32_t *move_scores, int64_t *n_splits, void *stream);
+int bo_anchor_eval(int device, int32_t n, const bo_position *positions, int32_t *ev_out, void *stream);
 
 #ifdef __cplusplus
 }
