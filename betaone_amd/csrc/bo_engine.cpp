@@ -7,6 +7,7 @@
 
 #include "bo_tree.h"
 #include "bo_fastw.h"
+#include "bo_info.h"
 #include "bo_select_wide.h"
 #include "bo_replay.h"
 #include "bo_train.h"
@@ -638,7 +639,6 @@ extern "C" int bo_search_poll(bo_engine *e, int32_t *n_running, int32_t *n_reque
 
 extern "C" int bo_search_stop(bo_engine *e, const int32_t *stop_mask, int32_t *sims_done, void *stream) {
     if (!e) return fail(BO_E_ARG, "null engine");
-    if (e->fast) return fail(BO_E_CONFIG, "bo_search_stop: reference-semantics engines only");
     const size_t G = (size_t)e->d.c.G;
     const int *d_mask = nullptr;
     if (stop_mask) {
@@ -646,9 +646,24 @@ extern "C" int bo_search_stop(bo_engine *e, const int32_t *stop_mask, int32_t *s
         RT(rt_h2d(e->d_go, e->h_go, G * 4, stream));
         d_mask = e->d_go;
     }
-    RT(RT_LAUNCH(bo_k_stop, e->d.c.G, stream, e->d, d_mask));
+    if (e->fast) {  // the step in flight is dropped (bo_info.h): nothing of it is in the tree
+        e->prefetch_valid = false;
+        RT(RT_LAUNCH(bo_k_fw_stop, e->d.c.G, stream, e->d, e->f, d_mask));
+    } else {
+        RT(RT_LAUNCH(bo_k_stop, e->d.c.G, stream, e->d, d_mask));
+    }
     if (sims_done) RT(rt_d2h(sims_done, e->d.sims_done, G * 4, stream));
     RT(rt_sync(stream));
+    return BO_OK;
+}
+
+// One bo_search_info record per slot into out[G] (device memory, or pinned host memory mapped into the device).  Read-only, asynchronous.
+extern "C" int bo_search_info(bo_engine *e, int32_t n_lines, bo_search_info_rec *out, void *stream) {
+    if (!e || !out) return fail(BO_E_ARG, "bo_search_info: null argument");
+    if (!e->fast) return fail(BO_E_CONFIG, "bo_search_info: fast-mode engines only (reference semantics: bo_analysis_result)");
+    if (n_lines < 0) return fail(BO_E_ARG, "bo_search_info: n_lines < 0");
+    static_assert(sizeof(bo_search_info_rec) == BO_INFO_WORDS * 4, "bo_search_info_rec is the record bo_k_fw_info writes");
+    RT(RT_LAUNCH(bo_k_fw_info, e->d.c.G, stream, e->d, e->f, (int)n_lines, (int *)out));
     return BO_OK;
 }
 

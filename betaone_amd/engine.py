@@ -91,6 +91,13 @@ REANALYSIS_DTYPE = np.dtype([("terminal", "<i4"), ("n_legal", "<i4"), ("total_vi
                              ("pi_n", "<i4"), ("played_prob", "<f4"), ("has_old", "<i4"), ("agree", "<i4"), ("tv", "<f4"), ("phase", "<i4"),
                              ("status", "<i4"), ("ply", "<i4"), ("sims_done", "<i4"), ("watch", "<i4"), ("reserved", "<i4")])  # bo_reanalysis
 PH_IDLE, PH_RUN, PH_DONE = 0, 1, 2
+INFO_LINES, INFO_PV = 8, 24  # BO_INFO_LINES, BO_INFO_PV
+INFO_LINE_DTYPE = np.dtype([("move", "<i4"), ("visits", "<i4"), ("w", "<f4"), ("prior", "<f4"), ("pv_len", "<i4"), ("pv", "<i4", (INFO_PV,)),
+                            ("reserved", "<i4", (3,))])
+INFO_DTYPE = np.dtype([("phase", "<i4"), ("status", "<i4"), ("terminal", "<i4"), ("n_legal", "<i4"), ("sims_done", "<i4"),
+                       ("root_visits", "<i4"), ("arena_top", "<i4"), ("arena_granules", "<i4"), ("watch", "<i4"), ("n_lines", "<i4"),
+                       ("reserved", "<i4", (6,)), ("line", INFO_LINE_DTYPE, (INFO_LINES,))])  # bo_search_info_rec (272 words)
+INFO_WORDS = INFO_DTYPE.itemsize // 4
 
 
 class BoHeadWeights(C.Structure):  # bo_head_weights: device addresses of one net's head Linear weights (bo_nn_heads_pair)
@@ -118,6 +125,7 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_search_poll": (C.c_int, [C.c_void_p, _I32P, _I32P, _I32P, C.c_void_p]),
     "bo_search_stop": (C.c_int, [C.c_void_p, _I32P, _I32P, C.c_void_p]),
     "bo_search_close": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bo_search_info": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "bo_search_result": (C.c_int, [C.c_void_p, _I32P, _I32P, _F32P, _I32P, _I32P, _I32P, C.c_void_p]),
     "bo_play": (C.c_int, [C.c_void_p, _I32P, C.c_void_p]),
     "bo_game_export": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BoPosition), _I32P, C.c_int32, _I32P, C.c_void_p]),
@@ -271,7 +279,7 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 20  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 21  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
 # BO_METRIC_ROW_* / BO_METRIC_* of include/betaone_engine.h by name (bo_train_metrics; tests/test_validate_emu.py compares with the header)
 METRIC_ROW = {name: k for k, name in enumerate((
@@ -501,11 +509,16 @@ class Engine:
         return run.value, req.value, mask
 
     def search_stop(self, mask=None, stream: int = 0) -> np.ndarray:
-        """Interrupt the running searches (all, or those with mask[g] != 0) between two steps; -> simulations completed per game."""
+        """Interrupt the running searches (all, or those with mask[g] != 0) between two steps; -> simulations completed per game.
+        Fast mode: the step in flight is dropped, the tree is the one after the last completed backup (include/betaone_engine.h)."""
         m = _i32(mask) if mask is not None else None
         done = np.zeros(self.G, dtype=np.int32)
         self._check(self.lib.bo_search_stop(self.h, _p(m) if m is not None else None, _p(done), stream))
         return done
+
+    def search_info(self, n_lines: int, out_ptr: int, stream: int = 0) -> None:
+        """bo_search_info: G records of INFO_DTYPE into out (device or pinned memory); fast-mode engines, any phase, read-only.  Nothing waits."""
+        self._check(self.lib.bo_search_info(self.h, int(n_lines), out_ptr, stream))
 
     def search_close(self, stream: int = 0) -> None:
         """Finish every search that waits for its LAST leaf evaluation without it (bo_search_close): the remaining visits are counted

@@ -39,10 +39,11 @@ extern "C" {
  * bo_reanalysis_result, status bit BO_ST_PI_OVERFLOW -- additions only; 16: opening books -- bo_book_insert -- addition only;
  * 18: board symmetries in the replay samplers -- bo_replay_sample_sym, _sparse_sym, _sparse_q_sym, _merged_sym -- additions only;
  * 19: forced mates on the device -- bo_mate, bo_mate_result -- additions only; 20: the anchor opponent -- bo_anchor, bo_anchor_eval,
- * bo_anchor_result -- additions only).
+ * bo_anchor_result -- additions only; 21: an interactive front end on the fast mode -- bo_search_stop accepts fast-mode engines,
+ * bo_search_info -- additions only).
  * A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 20
+#define BO_ABI_VERSION 21
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -176,7 +177,16 @@ int bo_search_poll(bo_engine *e, int32_t *n_running, int32_t *n_requested, int32
  * searches, uci.py:73): for every game with stop_mask[g] != 0 (NULL = all) whose search is running, the pending rows are
  * flushed exactly like the tail batch of mcts.py:256-257, an evaluation still outstanding is dropped, and the search is
  * marked finished -- bo_search_result then returns what the reference returns for NUM_SIMULATIONS = sims_done[g]
- * (optional out, [G] int32: simulations completed per game).  Reference-semantics engines only.  Synchronises. */
+ * (optional out, [G] int32: simulations completed per game).  Synchronises.
+ * (ABI 21) FAST-mode engines: the step in flight -- the rows the last bo_step selected, which wait for their evaluation -- is
+ * ABANDONED: its simulations are not counted and nothing of them is in the tree (the virtual loss is never written, a step is backed
+ * up by the NEXT step, and materialising a row writes no tree record), the control block's rows and simulations go to 0, no evaluation
+ * is requested any more and the search is marked finished.  sims_done[g] -- a multiple of leaves_per_step unless the search was about
+ * to end -- and the tree are those after the last completed backup: a stopped fast search equals a search created with
+ * num_simulations = sims_done[g], and bo_search_result answers from that tree.  One exception: a search stopped before the step
+ * that consumes its ROOT's evaluation has an unexpanded root, sims_done 0 and a uniform pi (a search with num_simulations = 0 would
+ * still have expanded the root).  The per-slot evaluation counter of bo_engine_status includes the dropped rows.  A later
+ * bo_search_begin on the slot continues in the same tree.  Slots that are idle, finished or not in the mask are untouched. */
 int bo_search_stop(bo_engine *e, const int32_t *stop_mask, int32_t *sims_done, void *stream);
 
 /* (ABI 13) Finish, WITHOUT its evaluation, every running search that waits for its last leaf evaluation: a leaf is requested, no rows
@@ -1069,6 +1079,33 @@ typedef struct bo_anchor_result {
 int bo_anchor(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t depth, int64_t capacity,
               uint32_t flags, bo_anchor_result *results, int32_t *root_moves, int32_t *move_scores, int64_t *n_splits, void *stream);
 int bo_anchor_eval(int device, int32_t n, const bo_position *positions, int32_t *ev_out, void *stream);
+
+/* ---- (ABI 21, additions) a look at a running FAST-mode search: csrc/bo_info.h, betaone_amd/uci.py -----------------------------------
+ * bo_search_info: one bo_search_info_rec per slot into out[G] (device memory, or pinned device-mapped host memory; every word is stored
+ * exactly once).  Read-only and asynchronous; to be enqueued between two bo_step calls (or before the first / after the last), whatever
+ * the slots' phases.  Fast-mode engines only (BO_E_CONFIG: reference-semantics engines have bo_analysis_result).
+ *   phase (0 idle, 1 running, 2 finished), status (BO_ST_* bits), terminal (bo_root_info's code), n_legal, sims_done (of this search:
+ *   completed backups only); root_visits: the root record's count (visits kept from earlier searches included); arena_top /
+ *   arena_granules: granules in use / per arena; watch: the word(s) named to bo_engine_watch as the last result kernel left them.
+ *   n_lines = min(n_lines asked for, BO_INFO_LINES, root children with a visit); 0 for a terminal or unexpanded root.
+ *   line[i]: the root child with the i-th most visits; among equal counts the earlier child in record (= legal-move) order first, so
+ *     line[0].move is bo_search_result's best move on the same tree.  visits; w: the child's raw float32 value sum, seen by the side
+ *     to move at the root (csrc/bo_fastw.h: W of a node is seen by the player who moved into it) -- the host divides; prior.
+ *     pv[0 .. pv_len): pv[0] == move, then at each node the child with the most visits, the first maximum in record order; the
+ *     variation ends at a node without children (unvisited, known mate, known draw), at a node whose best child has no visit, and
+ *     at BO_INFO_PV moves.  Words beyond n_lines / pv_len are 0. */
+#define BO_INFO_LINES 8
+#define BO_INFO_PV 24
+typedef struct bo_info_line {
+    int32_t move, visits;
+    float w, prior;
+    int32_t pv_len, pv[BO_INFO_PV], reserved[3];
+} bo_info_line;
+typedef struct bo_search_info_rec {
+    int32_t phase, status, terminal, n_legal, sims_done, root_visits, arena_top, arena_granules, watch, n_lines, reserved[6];
+    bo_info_line line[BO_INFO_LINES];
+} bo_search_info_rec;
+int bo_search_info(bo_engine *e, int32_t n_lines, bo_search_info_rec *out, void *stream);
 
 #ifdef __cplusplus
 }
