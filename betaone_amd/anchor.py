@@ -6,16 +6,22 @@ roots over perft's frontier.  Draw rules are ignored inside the tree, as in perf
 a line.  A mate in 1 scores MATE - 1, so a depth-D search finds every mate of at most D plies and prefers the shortest.
 
     search("r1bqkbnr/pppp1ppp/2n5/4p2Q/2B1P3/8/PPPP1PPP/RNB1K1NR w KQkq - 4 4", 1)[0].best      # 'h5f7'
-    python -m betaone_amd.anchor best "FEN" --depth 3 [--scores] [--json]
+    python -m betaone_amd.anchor best "FEN" --depth 3 [--quiesce 4] [--scores] [--json]
     python -m betaone_amd.anchor best --epd FILE --depth 3
-    python -m betaone_amd.anchor match NET.pth --depth 3 [--margin 15] [--games 200 --slots 64 --sims 800 --openings book.txt
+    python -m betaone_amd.anchor match NET.pth --depth 3 [--quiesce 4] [--margin 15] [--games 200 --slots 64 --sims 800 --openings book.txt
         --open-plies 8 --t-final 0.1 --max-game-moves 512 --pgn out.pgn --out result.json --seed-iteration 0]
 
 roots: a FEN, a sequence of FENs, or a ctypes array of engine.BoPosition, as mate.mate takes them.
 
+Quiescence (quiesce=Q, 1 .. 8; bo_anchor_q): at the horizon a position with a legal move gets qs(P, D, Q) in place of ev(P) -- up to Q
+further plies over the TACTICAL moves only (captures and promotions; every evasion when in check), standing pat on ev(P) when not in
+check.  The anchor then no longer evaluates in the middle of an exchange.  A mate score out of the quiescence plies is a forced mate (the
+mated side was in check at each of its nodes, so all its replies were searched): a found mate is a score >= MATE - (depth + quiesce).
+With quiesce 0 every call, byte and printed line is the fixed-depth anchor's.
+
 Move choice in games (pick): with `margin` centipawns and a seeded numpy RandomState, uniformly among the moves whose score is within
-the margin of the best; once the score is a found mate (score >= MATE - depth) only the moves that equal it qualify, so the anchor
-never gives up a mate.  No generator: the deterministic lowest-index best move.  Depth 0 is a uniformly random legal move.
+the margin of the best; once the score is a found mate (score >= MATE - (depth + quiesce)) only the moves that equal it qualify, so
+the anchor never gives up a mate.  No generator: the deterministic lowest-index best move.  Depth 0 is a uniformly random legal move.
 
 A match (AnchorRollout under match.play_match) plays the net -- one evaluate stage, the reference search, no Dirichlet noise -- against
 the anchor on the host-made turn: each ply the slots where the net is to move are searched and sampled as Rollout.play_ply does, the
@@ -41,6 +47,7 @@ from .perft import DEFAULT_CAPACITY, MAX_MOVES, START_FEN
 
 MATE = 30000     # BO_ANCHOR_MATE (include/betaone_engine.h)
 MAX_DEPTH = 8    # BO_ANCHOR_MAX_DEPTH
+MAX_QUIESCE = 8  # BO_ANCHOR_MAX_QUIESCE
 NONE = -(1 << 31)
 STATUS_NAMES = ("ok", "checkmated", "stalemated", "not a position")
 
@@ -62,9 +69,10 @@ class AnchorResult:
     n_moves: int
     move_words: Optional[List[int]] = None   # scores=True: the root's moves in generated order ...
     scores: Optional[List[int]] = None       # ... and the score of each
-    nodes: int = 0                     # frontier entries of levels 0 .. depth - 1, of the whole call
+    nodes: int = 0                     # frontier entries of levels 0 .. depth + quiesce - 1, of the whole call
     splits: int = 0                    # of the whole call
     seconds: float = 0.0               # of the whole call
+    quiesce: int = 0                   # quiescence plies behind the horizon
 
     @property
     def moves(self) -> Optional[List[str]]:
@@ -73,6 +81,8 @@ class AnchorResult:
     def to_json(self) -> dict:
         d = {"fen": self.fen, "status": self.status, "depth": self.depth, "score": self.score, "best": self.best, "n_best": self.n_best,
              "n_moves": self.n_moves, "nodes": self.nodes, "splits": self.splits, "seconds": self.seconds}
+        if self.quiesce:
+            d["quiesce"] = self.quiesce
         if self.scores is not None:
             d["moves"], d["scores"] = self.moves, list(self.scores)
         return d
@@ -85,9 +95,13 @@ def _stream(dev) -> int:
     return 0
 
 
-def search(roots: Union[str, Sequence[Optional[str]], C.Array], depth: int, *, scores: bool = False, capacity: int = DEFAULT_CAPACITY,
-           device="cuda:0", lib=None) -> List[AnchorResult]:
-    """The depth-`depth` anchor search of every root, in one device call on torch's current stream of `device`."""
+def search(roots: Union[str, Sequence[Optional[str]], C.Array], depth: int, *, quiesce: int = 0, scores: bool = False,
+           capacity: int = DEFAULT_CAPACITY, device="cuda:0", lib=None) -> List[AnchorResult]:
+    """The depth-`depth` anchor search of every root, with `quiesce` quiescence plies behind the horizon, in one device call on torch's
+    current stream of `device`."""
+    quiesce = int(quiesce)
+    if quiesce and int(depth) < 1:
+        raise ValueError("anchor.search: quiescence needs a depth of at least 1 (depth 0 is a random mover)")
     lib = lib or E.load_hip_library()
     dev = E.runtime_device(device)
     fens, arr, pos = None, None, None
@@ -105,8 +119,9 @@ def search(roots: Union[str, Sequence[Optional[str]], C.Array], depth: int, *, s
     splits = C.c_int64(0)
     stream = _stream(dev)
     t0 = time.perf_counter()
-    rc = lib.bo_anchor(int(dev.index or 0), n, arr, C.addressof(pos) if pos is not None else None, int(depth), int(capacity), 0,
-                       C.addressof(res), words.ctypes.data if scores else None, vals.ctypes.data if scores else None, C.byref(splits), stream)
+    tail = (int(capacity), 0, C.addressof(res), words.ctypes.data if scores else None, vals.ctypes.data if scores else None, C.byref(splits), stream)
+    head = (int(dev.index or 0), n, arr, C.addressof(pos) if pos is not None else None, int(depth))
+    rc = lib.bo_anchor_q(*head, quiesce, *tail) if quiesce else lib.bo_anchor(*head, *tail)
     dt = time.perf_counter() - t0
     if rc != 0:
         msg = f"bo_anchor: {lib.bo_last_error().decode()}"
@@ -118,7 +133,7 @@ def search(roots: Union[str, Sequence[Optional[str]], C.Array], depth: int, *, s
         out.append(AnchorResult(fens[i] if fens is not None else None, STATUS_NAMES[int(r.status)], int(depth), int(r.score),
                                 E.move_to_uci(int(r.best)) if r.best >= 0 else None, int(r.best), int(r.n_best), k,
                                 [int(w) for w in words[i, :k]] if scores else None, [int(v) for v in vals[i, :k]] if scores else None,
-                                nodes=int(r.nodes), splits=int(splits.value), seconds=dt))
+                                nodes=int(r.nodes), splits=int(splits.value), seconds=dt, quiesce=quiesce))
     return out
 
 
@@ -141,10 +156,10 @@ def evaluate(positions, *, device="cuda:0", lib=None) -> np.ndarray:
 
 def candidates(result: AnchorResult, margin: int = 0) -> List[int]:
     """Indices (into the root's move list) of the moves pick chooses among: within `margin` of the score; a found mate
-    (score >= MATE - depth) only by the moves that equal it."""
+    (score >= MATE - (depth + quiesce): a mate out of the quiescence plies is forced too) only by the moves that equal it."""
     if result.scores is None:
         raise ValueError("anchor.candidates: the result has no per-move scores (search(..., scores=True))")
-    m = 0 if result.score >= MATE - result.depth else max(int(margin), 0)
+    m = 0 if result.score >= MATE - (result.depth + result.quiesce) else max(int(margin), 0)
     return [i for i, v in enumerate(result.scores) if v >= result.score - m]
 
 
@@ -171,7 +186,9 @@ def random_result(move_words: Sequence[int], fen: Optional[str] = None) -> Ancho
     return AnchorResult(fen, "ok", 0, 0, None, -1, 0, len(w), w, [0] * len(w))
 
 
-def anchor_name(depth: int, margin: int) -> str:
+def anchor_name(depth: int, margin: int, quiesce: int = 0) -> str:
+    if int(quiesce):
+        return f"anchor(depth={int(depth)},quiesce={int(quiesce)},margin={int(margin)})"
     return f"anchor(depth={int(depth)},margin={int(margin)})"
 
 
@@ -182,18 +199,20 @@ class AnchorRollout:
     The seeds handed to start_games / refill are integers (selfplay_main.game_seed); the net's sampling stream is RandomState(seed),
     the anchor's RandomState(seed ^ 0x5bd1e995)."""
 
-    def __init__(self, model, n_games: int, depth: int, margin: int = 0, *, capacity: int = DEFAULT_CAPACITY, **rollout_kw):
+    def __init__(self, model, n_games: int, depth: int, margin: int = 0, *, quiesce: int = 0, capacity: int = DEFAULT_CAPACITY, **rollout_kw):
         from .rollout import Rollout
 
         if not 0 <= int(depth) <= MAX_DEPTH:
             raise ValueError(f"AnchorRollout: depth must be 0 .. {MAX_DEPTH}")
         if int(margin) < 0:
             raise ValueError("AnchorRollout: margin must be >= 0")
+        if not 0 <= int(quiesce) <= MAX_QUIESCE or (int(quiesce) and int(depth) == 0):
+            raise ValueError(f"AnchorRollout: quiesce must be 0 .. {MAX_QUIESCE}, and 0 at depth 0 (a random mover)")
         for k in ("resign_threshold", "record_values", "fast", "rng_mode", "dirichlet_alpha"):
             if rollout_kw.get(k):
                 raise ValueError(f"AnchorRollout: {k} is not supported (the net plays the reference search on the host-made turn, without noise)")
             rollout_kw.pop(k, None)
-        self.depth, self.margin, self.capacity = int(depth), int(margin), int(capacity)
+        self.depth, self.margin, self.quiesce, self.capacity = int(depth), int(margin), int(quiesce), int(capacity)
         self.ro = Rollout(model, n_games, rng_mode="python", dirichlet_alpha=0.0, **rollout_kw)
         self.ro.external_moves = self._anchor_moves
         self.G, self.eng, self.device = self.ro.G, self.ro.eng, self.ro.device
@@ -252,7 +271,7 @@ class AnchorRollout:
             lists, _ = self.eng.movegen(list(roots), ro._stream())
             res = [random_result(m) for m in lists]
         else:
-            res = search(roots, self.depth, scores=self.margin > 0, capacity=self.capacity, device=self.device)
+            res = search(roots, self.depth, quiesce=self.quiesce, scores=self.margin > 0, capacity=self.capacity, device=self.device)
             self.anchor_seconds += res[0].seconds
             self.anchor_nodes += res[0].nodes
         use_rng = self.depth == 0 or self.margin > 0
@@ -269,7 +288,8 @@ class AnchorRollout:
 def _line(r: AnchorResult) -> str:
     if r.status != "ok":
         return "not a position" if r.status == "not a position" else f"the side to move is {r.status}"
-    s = f"mate in {(MATE - r.score + 1) // 2}" if r.score >= MATE - r.depth else f"mated in {(MATE + r.score) // 2}" if r.score <= -(MATE - r.depth) \
+    h = r.depth + r.quiesce  # the deepest ply a mate can be found at
+    s = f"mate in {(MATE - r.score + 1) // 2}" if r.score >= MATE - h else f"mated in {(MATE + r.score) // 2}" if r.score <= -(MATE - h) \
         else f"{r.score:+d} cp"
     return f"best {r.best} ({s}, score {r.score}), {r.n_best} of {r.n_moves} moves reach it"
 
@@ -278,6 +298,7 @@ def main_best(argv, out) -> int:
     ap = argparse.ArgumentParser(prog="python -m betaone_amd.anchor best", description="the anchor's move at a position")
     ap.add_argument("fen", nargs="?", default=None, help="FEN (default: the start position)")
     ap.add_argument("--depth", type=int, default=3)
+    ap.add_argument("--quiesce", type=int, default=0, metavar="Q", help=f"quiescence plies behind the horizon, 0 .. {MAX_QUIESCE}")
     ap.add_argument("--scores", action="store_true", help="the score of every root move")
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--epd", default=None, metavar="FILE", help="one position per line (a FEN of four or six fields; operations are ignored)")
@@ -291,14 +312,15 @@ def main_best(argv, out) -> int:
         from .mate import parse_epd
 
         suite = parse_epd(open(a.epd).read())
-        res = search([s[1] for s in suite], a.depth, capacity=a.capacity, device=a.device) if suite else []
+        res = search([s[1] for s in suite], a.depth, quiesce=a.quiesce, capacity=a.capacity, device=a.device) if suite else []
         for (ln, fen, _, _), r in zip(suite, res):
             print(f"{a.epd}:{ln}: {fen}: {_line(r)}", file=out)
         nodes, secs = (res[0].nodes, res[0].seconds) if res else (0, 0.0)
-        print(f"{len(suite)} positions at depth {a.depth}; {nodes} nodes in {secs:.3f} s", file=out)
+        at = f"depth {a.depth}" + (f", quiesce {a.quiesce}" if a.quiesce else "")
+        print(f"{len(suite)} positions at {at}; {nodes} nodes in {secs:.3f} s", file=out)
         return 0
     fen = None if a.fen in (None, "startpos") else a.fen
-    r = search(fen, a.depth, scores=a.scores, capacity=a.capacity, device=a.device)[0]
+    r = search(fen, a.depth, quiesce=a.quiesce, scores=a.scores, capacity=a.capacity, device=a.device)[0]
     if a.json:
         print(json.dumps(r.to_json()), file=out)
         return 0
@@ -306,7 +328,8 @@ def main_best(argv, out) -> int:
     if a.scores and r.scores is not None:
         print(" ".join(f"{m} {v}" for m, v in zip(r.moves, r.scores)), file=out)
     rate = r.nodes / r.seconds if r.seconds > 0 else 0.0
-    print(f"depth {r.depth}: {r.nodes} nodes, {r.seconds:.3f} s, {rate / 1e6:.2f} M nodes/s" + (f", {r.splits} level splits" if r.splits else ""), file=out)
+    at = f"depth {r.depth}" + (f", quiesce {r.quiesce}" if r.quiesce else "")
+    print(f"{at}: {r.nodes} nodes, {r.seconds:.3f} s, {rate / 1e6:.2f} M nodes/s" + (f", {r.splits} level splits" if r.splits else ""), file=out)
     return 0
 
 
@@ -317,6 +340,7 @@ def main_match(argv, out) -> int:
     ap = argparse.ArgumentParser(prog="python -m betaone_amd.anchor match", description="Play a checkpoint against the anchor on the GPU.")
     ap.add_argument("net", help="the checkpoint")
     ap.add_argument("--depth", type=int, default=3, help=f"the anchor's search depth in plies, 0 (a random mover) .. {MAX_DEPTH}")
+    ap.add_argument("--quiesce", type=int, default=0, metavar="Q", help=f"the anchor's quiescence plies behind the horizon, 0 .. {MAX_QUIESCE}")
     ap.add_argument("--margin", type=int, default=0, help="the anchor picks uniformly among the moves within this many centipawns of its best")
     ap.add_argument("--games", type=int, default=200)
     ap.add_argument("--slots", type=int, default=64)
@@ -336,9 +360,9 @@ def main_match(argv, out) -> int:
     dev = E.runtime_device(a.device)
     net = nn_tune.best_inference_copy(M.build_net(sd, dev), a.slots, dev)
     openings = M.parse_openings(open(a.openings).read()) if a.openings else [(None, "")]
-    name = anchor_name(a.depth, a.margin)
+    name = anchor_name(a.depth, a.margin, a.quiesce)
     print(f"[anchor] net {M.net_shape(sd)} vs {name}", file=out)
-    ro = AnchorRollout(net, a.slots, a.depth, a.margin, capacity=a.capacity, num_simulations=a.sims, mcts_batch_size=a.mcts_batch,
+    ro = AnchorRollout(net, a.slots, a.depth, a.margin, quiesce=a.quiesce, capacity=a.capacity, num_simulations=a.sims, mcts_batch_size=a.mcts_batch,
                        temperature=(a.open_plies, 1.0, a.t_final), max_game_moves=a.max_game_moves, device=str(dev))
     sched = M.MatchScheduler(openings, a.games, a.slots, 1)
     finished: Optional[Dict] = {} if a.pgn else None
@@ -356,6 +380,8 @@ def main_match(argv, out) -> int:
     if a.out:
         settings = {k: getattr(a, k) for k in ("depth", "margin", "games", "slots", "sims", "mcts_batch", "openings", "open_plies", "t_final",
                                                "max_game_moves", "seed_iteration")}
+        if a.quiesce:
+            settings["quiesce"] = a.quiesce
         with open(a.out, "w") as f:
             json.dump(M.json_safe({"a": name, "b": a.net, "settings": settings, "summary": st, "games": played["games"]}), f, indent=1,
                       allow_nan=False)
@@ -369,7 +395,7 @@ def main(argv=None, out=None) -> int:
         return main_match(argv[1:], out)
     if argv and argv[0] == "best":
         return main_best(argv[1:], out)
-    print("usage: python -m betaone_amd.anchor best \"FEN\" --depth D [--scores] [--json] | best --epd FILE | match NET.pth --depth D ...", file=out)
+    print("usage: python -m betaone_amd.anchor best \"FEN\" --depth D [--quiesce Q] [--scores] [--json] | best --epd FILE | match NET.pth --depth D ...", file=out)
     return 2
 
 

@@ -3622,13 +3622,16 @@ extern "C" int bo_mate(int device, int32_t n_roots, const char *const *fens, con
 // ---- the anchor opponent on the device (bo_anchor.h) ---------------------------------------------------------------------------------
 // The walk is perft's again, with mate's order of work: a level's chunk is expanded, the chunk below is taken to the bottom, then its
 // values are backed up into the parents it came from.  Every level keeps one int16 per entry; level 0 holds the roots that have a move.
+// With quiescence Q > 0 (bo_anchor_q) the walk has D + Q levels: 0 .. D - 1 full width, D .. D + Q - 1 over the tactical moves only.
 namespace {
 struct AnchorRun : PerftRun {
     std::vector<int16_t *> val;  // per level [have_val]
     std::vector<int64_t> have_val;
     // per root [n]: check bits, row in root_moves, score row [256], score, number of best moves, lowest-index best move
     int32_t *root_chk = nullptr, *act = nullptr, *scores = nullptr, *score = nullptr, *n_best = nullptr, *best = nullptr, *n_act = nullptr;
-    uint64_t visited = 0;  // frontier entries of levels 0 .. D - 1 (include/betaone_engine.h: nodes)
+    uint64_t visited = 0;  // frontier entries of levels 0 .. D + Q - 1 (include/betaone_engine.h: nodes)
+    int quiesce = 0;       // Q; `depth` is D
+    int levels() const { return depth + quiesce; }
     ~AnchorRun() {
         (void)rt_sync(stream);
         for (int16_t *p : val) rt_free(p);
@@ -3649,10 +3652,12 @@ struct AnchorRun : PerftRun {
 
 int anchor_backup(AnchorRun &R, int l, int64_t a, int64_t e) {
     PerftLevel &L = R.lv[l];
-    const int16_t *below = l + 1 < R.depth ? R.val[l + 1] : nullptr;
+    const int16_t *below = l + 1 < R.levels() ? R.val[l + 1] : nullptr;
     if (l == 0)
         RT(RT_LAUNCH(bo_k_anchor_backup_root, e - a, R.stream, (const int32_t *)R.n_act, (const uint64_t *)L.off, a, below, R.scores, R.score,
                      R.n_best, R.best, (const int32_t *)R.act, (const int32_t *)R.root_moves));
+    else if (l >= R.depth)  // a quiescence level: the entry's own value (the floor) stands unless a tactical move beats it
+        RT(RT_LAUNCH(bo_k_anchor_backup_q, e - a, R.stream, (const int32_t *)L.cnt, (const uint64_t *)L.off, a, below, R.val[l]));
     else
         RT(RT_LAUNCH(bo_k_anchor_backup, e - a, R.stream, (const int32_t *)L.cnt, (const uint64_t *)L.off, a, below, R.val[l]));
     return BO_OK;
@@ -3662,12 +3667,18 @@ int anchor_backup(AnchorRun &R, int l, int64_t a, int64_t e) {
 int anchor_level(AnchorRun &R, int l, int64_t n) {
     PerftLevel &L = R.lv[l];
     R.visited += (uint64_t)n;
-    if (l == R.depth - 1) {
+    const bool quiet = l >= R.depth;  // a quiescence level (Q > 0 only): its children are the tactical moves
+    if (quiet && l == R.levels() - 1) {
+        RT(RT_LAUNCH(bo_k_anchor_qleaf, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], (int32_t)l));
+        return BO_OK;
+    }
+    if (l == R.levels() - 1) {
         RT(RT_LAUNCH(bo_k_anchor_leaf, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], l == 0 ? R.scores : (int32_t *)nullptr, (int32_t)l,
                      l == 0 ? AN_ROOT : 0u));
         return l == 0 ? anchor_backup(R, 0, 0, n) : BO_OK;
     }
-    RT(RT_LAUNCH(bo_k_anchor_count, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], (int32_t)l));
+    if (quiet) RT(RT_LAUNCH(bo_k_anchor_qcount, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], (int32_t)l));
+    else RT(RT_LAUNCH(bo_k_anchor_count, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], (int32_t)l));
     int rc = R.scan(l, n);
     if (rc) return rc;
     int64_t left = R.h_word[0], a = 0;
@@ -3684,8 +3695,10 @@ int anchor_level(AnchorRun &R, int l, int64_t n) {
         }
         RT(R.room_anchor(l + 1, c));
         PerftLevel &C = R.lv[l + 1];
-        RT(RT_LAUNCH(bo_k_perft_expand, e - a, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (const uint64_t *)L.off, a, C.pos, C.tag,
-                     C.have, 0u));
+        if (quiet) RT(RT_LAUNCH(bo_k_anchor_qexpand, e - a, R.stream, (const DPos *)L.pos, (const uint64_t *)L.off, a, C.pos, C.tag, C.have));
+        else
+            RT(RT_LAUNCH(bo_k_perft_expand, e - a, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (const uint64_t *)L.off, a, C.pos, C.tag,
+                         C.have, 0u));
         rc = anchor_level(R, l + 1, c);
         if (!rc) rc = anchor_backup(R, l, a, e);
         if (rc) return rc;
@@ -3693,7 +3706,7 @@ int anchor_level(AnchorRun &R, int l, int64_t n) {
         a = e;
     }
     if (l == 0 && a < n) return fail(BO_E_STATE, "bo_anchor: a root with moves has no children");
-    return BO_OK;  // (entries behind the last child have no move: they keep the count kernel's value)
+    return BO_OK;  // (entries behind the last child have no move, or no tactical one: they keep the count kernel's value)
 }
 
 bool anchor_record_ok(const bo_position &q, DPos *p) {
@@ -3701,18 +3714,20 @@ bool anchor_record_ok(const bo_position &q, DPos *p) {
     if (fields) *p = from_abi(q);
     return fields && mate_position_ok(*p);
 }
-}  // namespace
 
-extern "C" int bo_anchor(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t depth, int64_t capacity,
-                         uint32_t flags, bo_anchor_result *results, int32_t *root_moves, int32_t *move_scores, int64_t *n_splits, void *stream) {
+// bo_anchor (quiesce 0, who "bo_anchor") and bo_anchor_q: one body; at quiesce 0 the kernels and the bytes are bo_anchor's
+int anchor_search(const std::string &who, int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t depth,
+                  int32_t quiesce, int64_t capacity, uint32_t flags, bo_anchor_result *results, int32_t *root_moves, int32_t *move_scores,
+                  int64_t *n_splits, void *stream) {
     if (n_splits) *n_splits = 0;
     if (n_roots < 0 || n_roots > (1 << 20) || (fens != nullptr) == (positions != nullptr))
-        return fail(BO_E_ARG, "bo_anchor: exactly one of fens and positions, n_roots <= 2^20");
-    if (depth < 1 || depth > BO_ANCHOR_MAX_DEPTH) return fail(BO_E_ARG, "bo_anchor: depth must be 1 .. 8");
+        return fail(BO_E_ARG, who + ": exactly one of fens and positions, n_roots <= 2^20");
+    if (depth < 1 || depth > BO_ANCHOR_MAX_DEPTH) return fail(BO_E_ARG, who + ": depth must be 1 .. 8");
+    if (quiesce < 0 || quiesce > BO_ANCHOR_MAX_QUIESCE) return fail(BO_E_ARG, who + ": quiesce must be 0 .. 8");
     if (capacity < BO_MAX_MOVES || capacity > ((int64_t)1 << 26))
-        return fail(BO_E_CONFIG, "bo_anchor: capacity must be 256 (the children of one position) .. 2^26 positions per level");
-    if (flags) return fail(BO_E_ARG, "bo_anchor: unknown flag bits");
-    if (n_roots && !results) return fail(BO_E_ARG, "bo_anchor: results must be given");
+        return fail(BO_E_CONFIG, who + ": capacity must be 256 (the children of one position) .. 2^26 positions per level");
+    if (flags) return fail(BO_E_ARG, who + ": unknown flag bits");
+    if (n_roots && !results) return fail(BO_E_ARG, who + ": results must be given");
     if (n_roots == 0) return BO_OK;
     const size_t N = (size_t)n_roots;
     std::vector<DPos> roots;     // the roots that are positions
@@ -3723,7 +3738,7 @@ extern "C" int bo_anchor(int device, int32_t n_roots, const char *const *fens, c
         DPos p;
         results[i].best = -1;
         if (fens) {
-            if (!pgn_fen_root(fens[i] ? fens[i] : "", &p) || !mate_position_ok(p)) return fail(BO_E_FEN, "bo_anchor: bad FEN (root " + std::to_string(i) + ")");
+            if (!pgn_fen_root(fens[i] ? fens[i] : "", &p) || !mate_position_ok(p)) return fail(BO_E_FEN, who + ": bad FEN (root " + std::to_string(i) + ")");
         } else if (!anchor_record_ok(positions[i], &p)) { results[i].status = BO_ANCHOR_NOT_A_POSITION; continue; }
         roots.push_back(p);
         index.push_back((int32_t)i);
@@ -3735,8 +3750,8 @@ extern "C" int bo_anchor(int device, int32_t n_roots, const char *const *fens, c
     if (roots.empty()) return BO_OK;
     RT(rt_set_device(device));
     AnchorRun R;
-    R.stream = stream; R.cap = capacity; R.depth = depth;
-    R.lv.resize((size_t)depth); R.val.resize((size_t)depth, nullptr); R.have_val.resize((size_t)depth, 0);
+    R.stream = stream; R.cap = capacity; R.depth = depth; R.quiesce = quiesce;
+    R.lv.resize((size_t)R.levels()); R.val.resize((size_t)R.levels(), nullptr); R.have_val.resize((size_t)R.levels(), 0);
     RT(rt_malloc((void **)&R.d_word, 16));
     RT(rt_host_alloc((void **)&R.h_word, 16));
     const size_t n = roots.size();
@@ -3800,6 +3815,19 @@ extern "C" int bo_anchor(int device, int32_t n_roots, const char *const *fens, c
     for (size_t i = 0; i < N; i++) results[i].nodes = R.visited;
     if (n_splits) *n_splits = R.splits;
     return BO_OK;
+}
+}  // namespace
+
+extern "C" int bo_anchor(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t depth, int64_t capacity,
+                         uint32_t flags, bo_anchor_result *results, int32_t *root_moves, int32_t *move_scores, int64_t *n_splits, void *stream) {
+    return anchor_search("bo_anchor", device, n_roots, fens, positions, depth, 0, capacity, flags, results, root_moves, move_scores, n_splits, stream);
+}
+
+extern "C" int bo_anchor_q(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t depth, int32_t quiesce,
+                           int64_t capacity, uint32_t flags, bo_anchor_result *results, int32_t *root_moves, int32_t *move_scores,
+                           int64_t *n_splits, void *stream) {
+    return anchor_search("bo_anchor_q", device, n_roots, fens, positions, depth, quiesce, capacity, flags, results, root_moves, move_scores,
+                         n_splits, stream);
 }
 
 extern "C" int bo_anchor_eval(int device, int32_t n, const bo_position *positions, int32_t *ev_out, void *stream) {

@@ -249,6 +249,8 @@ _SYMBOLS = {  # include/betaone_engine.h: the drop-in boundary
     "bo_anchor": (C.c_int, [C.c_int, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "bo_anchor_eval": (C.c_int, [C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bo_anchor_q": (C.c_int, [C.c_int, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_uint32, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
 }
 # include/betaone_lab.h: introspection for the parity tests and in-kernel timing for bench.py / scripts/ (same library, not the boundary)
 _LAB_SYMBOLS = {
@@ -279,7 +281,7 @@ def bind(cdll: C.CDLL) -> C.CDLL:
 
 
 _hip_lib: Optional[C.CDLL] = None
-ABI_VERSION = 21  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 22  # BO_ABI_VERSION of include/betaone_engine.h this binding was written against (tests/test_abi.py compares)
 PROF_SLOTS = 16   # BO_PROF_SLOTS
 # BO_METRIC_ROW_* / BO_METRIC_* of include/betaone_engine.h by name (bo_train_metrics; tests/test_validate_emu.py compares with the header)
 METRIC_ROW = {name: k for k, name in enumerate((

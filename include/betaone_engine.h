@@ -40,10 +40,11 @@ extern "C" {
  * 18: board symmetries in the replay samplers -- bo_replay_sample_sym, _sparse_sym, _sparse_q_sym, _merged_sym -- additions only;
  * 19: forced mates on the device -- bo_mate, bo_mate_result -- additions only; 20: the anchor opponent -- bo_anchor, bo_anchor_eval,
  * bo_anchor_result -- additions only; 21: an interactive front end on the fast mode -- bo_search_stop accepts fast-mode engines,
- * bo_search_info -- additions only).
+ * bo_search_info -- additions only; 22: quiescence behind the anchor's fixed-depth walk -- bo_anchor_q, BO_ANCHOR_MAX_QUIESCE --
+ * additions only).
  * A caller checks
  * bo_abi_version() == BO_ABI_VERSION before anything else (tests/c_abi_smoke.c). */
-#define BO_ABI_VERSION 21
+#define BO_ABI_VERSION 22
 #define BO_NUM_ACTIONS 4672          /* config.NUM_ACTIONS, config.py:29 */
 #define BO_INPUT_CHANNELS 120        /* config.INPUT_CHANNELS, config.py:28 */
 #define BO_ROW_FLOATS (120 * 64)
@@ -1079,6 +1080,27 @@ typedef struct bo_anchor_result {
 int bo_anchor(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t depth, int64_t capacity,
               uint32_t flags, bo_anchor_result *results, int32_t *root_moves, int32_t *move_scores, int64_t *n_splits, void *stream);
 int bo_anchor_eval(int device, int32_t n, const bo_position *positions, int32_t *ev_out, void *stream);
+
+/* ---- (ABI 22, additions) quiescence behind the anchor's fixed-depth walk ----------------------------------------------------------
+ * bo_anchor_q is bo_anchor with `quiesce` = Q, 0 .. BO_ANCHOR_MAX_QUIESCE, after `depth`: the same results, arrays and status rules.
+ * At p == D a position with a legal move gets qs(P, D, Q) in place of ev(P):
+ *   The TACTICAL moves of P: all its legal moves if its side to move is in check; otherwise the legal moves that capture (the
+ *   destination holds an enemy man, or an en passant capture) or promote (to any piece); in the generator's order.
+ *   qs(P, p, q) = -(BO_ANCHOR_MATE - p) if P has no legal move and is in check, 0 if it has none and is not;  ev(P) if q == 0;
+ *                 otherwise the maximum of the FLOOR -- ev(P) if P is not in check, -BO_ANCHOR_MATE if it is (no standing pat in
+ *                 check) -- and of -qs(P.m, p + 1, q - 1) over the tactical moves m.
+ * Draw rules are ignored, as above.  p <= D + Q <= 16 and -BO_ANCHOR_MATE itself are representable: every value still fits an int16.
+ * A mate score out of the quiescence plies is a FORCED mate: the mated side stood in check at each of its nodes, so every one of its
+ * replies was searched.  A found mate is therefore a score >= BO_ANCHOR_MATE - (D + Q).
+ * nodes: the frontier entries of levels 0 .. D + Q - 1 -- levels 0 .. D - 1 are full width, an entry of level D .. D + Q - 1 has its
+ * tactical moves as children; the children the last level makes are not entries.  The same at every capacity.
+ * quiesce == 0 takes bo_anchor's path: the same kernels, byte-identical output.
+ * Arguments are checked in this order, before any device call: n_roots / fens / positions (BO_E_ARG); depth (BO_E_ARG); quiesce
+ * (BO_E_ARG); capacity (BO_E_CONFIG); flag bits (BO_E_ARG); results NULL with n_roots > 0 (BO_E_ARG). */
+#define BO_ANCHOR_MAX_QUIESCE 8
+int bo_anchor_q(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t depth, int32_t quiesce,
+                int64_t capacity, uint32_t flags, bo_anchor_result *results, int32_t *root_moves, int32_t *move_scores, int64_t *n_splits,
+                void *stream);
 
 /* ---- (ABI 21, additions) a look at a running FAST-mode search: csrc/bo_info.h, betaone_amd/uci.py -----------------------------------
  * bo_search_info: one bo_search_info_rec per slot into out[G] (device memory, or pinned device-mapped host memory; every word is stored
