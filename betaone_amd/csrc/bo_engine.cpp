@@ -3102,117 +3102,254 @@ extern "C" int bo_nn_conv3x3_small(const float *x_dev, const float *wpacked_dev,
 #endif
 }
 
-// ---- perft on the device (bo_perft.h) --------------------------------------------------------------------------------------------
+// ---- perft on the device (bo_perft.h), and the level walk it shares with forced mates and the anchor opponent ------------------------
 // Level l of the walk is a frontier (positions and tags) in HBM; level 0 holds the roots.  Every level but the last one generated also
-// keeps its move counts and their scan, because a level whose children do not fit the next buffer is expanded chunk by chunk.
+// keeps its move counts and their scan, because a level whose children do not fit the next buffer is expanded chunk by chunk.  One run
+// object (Walk) owns every device buffer of a call, one function (walk_level) is the recursion; bo_perft, bo_mate and bo_anchor differ in
+// the kernels their hooks launch.
 namespace {
-struct PerftLevel {
-    DPos *pos = nullptr;
-    int32_t *tag = nullptr, *cnt = nullptr;
-    uint64_t *off = nullptr;
-    int64_t have = 0, have_scan = 0;
-};
-struct PerftRun {
-    void *stream = nullptr;
-    int depth = 0;
-    int64_t cap = 0, splits = 0;
-    uint32_t flags = 0;
-    std::vector<PerftLevel> lv;
-    int32_t *tsum = nullptr, *root_moves = nullptr, *root_n = nullptr;
-    uint64_t *tbase = nullptr, *nodes = nullptr, *sums = nullptr, *stats = nullptr;
-    int64_t have_tiles = 0, *d_word = nullptr, *h_word = nullptr;
-    ~PerftRun() {
-        (void)rt_sync(stream);  // nothing of ours is in flight when its memory goes
-        for (PerftLevel &L : lv) { rt_free(L.pos); rt_free(L.tag); rt_free(L.cnt); rt_free(L.off); }
-        rt_free(tsum); rt_free(tbase); rt_free(root_moves); rt_free(root_n); rt_free(nodes); rt_free(sums); rt_free(stats); rt_free(d_word);
-        if (h_word) rt_host_free(h_word);
-    }
-    // grow-only, doubling up to `limit` entries (the old contents are dead: a buffer is refilled before it is read)
-    static int64_t grown(int64_t have, int64_t need, int64_t limit) { return std::max(need, std::min(limit, 2 * have)); }
-    int room(int l, int64_t n) {
-        PerftLevel &L = lv[l];
-        if (L.have >= n) return 0;
-        const int64_t m = grown(L.have, n, cap);
-        rt_free(L.pos); rt_free(L.tag);
-        L.pos = nullptr; L.tag = nullptr; L.have = 0;
-        int rc = rt_malloc((void **)&L.pos, (size_t)m * sizeof(DPos));
-        if (!rc) rc = rt_malloc((void **)&L.tag, (size_t)m * 4);
-        if (!rc) L.have = m;
+// Device memory that frees itself: the pointer and its element count, move-only.  Releasing waits for nothing: the owner of a DevBuf
+// synchronises the stream before the buffer goes (Walk's destructor; the one sync of bo_anchor_eval).
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    int64_t n = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    ~DevBuf() { rt_free(p); }
+    int alloc(int64_t m) {  // exactly m entries (the old contents are dead)
+        rt_free(p);
+        p = nullptr; n = 0;
+        const int rc = rt_malloc((void **)&p, (size_t)m * sizeof(T));
+        if (rc) p = nullptr; else n = m;
         return rc;
+    }
+    // grow-only, doubling up to `limit` entries (the old contents are dead: a buffer is refilled before it is read); no limit: exactly `need`
+    int room(int64_t need, int64_t limit = 0) { return n >= need ? 0 : alloc(std::max(need, std::min(limit, 2 * n))); }
+};
+template <class T> struct HostBuf {  // its pinned-host twin
+    T *p = nullptr;
+    HostBuf() = default;
+    HostBuf(const HostBuf &) = delete;
+    ~HostBuf() { if (p) rt_host_free(p); }
+    int alloc(int64_t m) {  // exactly m entries (the old contents are dead)
+        if (p) rt_host_free(p);
+        p = nullptr;
+        const int rc = rt_host_alloc((void **)&p, (size_t)m * sizeof(T));
+        if (rc) p = nullptr;
+        return rc;
+    }
+};
+
+struct WalkLevel {
+    DevBuf<DPos> pos;          // the frontier [have]: have = pos.n
+    DevBuf<int32_t> tag, cnt;  // [have]; the move counts [have_scan]: have_scan = cnt.n
+    DevBuf<uint64_t> off;      // their scan [have_scan + 1]
+    DevBuf<uint8_t> mate_val;  // bo_mate: one value byte per entry [have]
+    DevBuf<uint64_t> live;     // bo_mate, attacker levels (even): the live masks [have][4]
+    DevBuf<int16_t> val;       // bo_anchor: one value per entry [have]
+};
+// Everything one call of bo_perft, bo_mate or bo_anchor holds on the device.  The destructor's body runs before the members go, so the
+// stream is synchronised before any buffer of the run is released, on every return path.  (A run whose call has failed is not used again.)
+struct Walk {
+    const char *name;  // the caller's, for messages
+    void *stream;
+    int64_t cap, splits = 0;
+    int depth = 0, quiesce = 0;  // levels 0 .. depth - 1 full width, then `quiesce` levels over the tactical moves (bo_anchor_q only)
+    uint32_t flags = 0;          // bo_perft's
+    uint64_t visited = 0;        // bo_mate, bo_anchor: frontier entries of every level of every walk (include/betaone_engine.h: nodes)
+    std::vector<WalkLevel> lv;
+    DevBuf<int32_t> tsum;
+    DevBuf<uint64_t> tbase;
+    DevBuf<int64_t> d_word;
+    HostBuf<int64_t> h_word;
+    // per root: the roots kernel's in-place buffer, move words [256], counts, check bits, active -> root
+    DevBuf<DPos> d_roots;
+    DevBuf<int32_t> root_moves, root_n, root_chk, act;
+    DevBuf<uint64_t> nodes, sums, stats;               // bo_perft: per root move, per root, per root [PF_NSTATS]
+    DevBuf<int32_t> n_keys, key;                       // bo_mate, per root: keys, lowest key
+    DevBuf<uint64_t> keymask;                          // bo_mate, per root: key mask [4]
+    DevBuf<int32_t> scores, score, n_best, best, n_act;  // bo_anchor, per root: score row [256], score, best moves, lowest best, moves
+    Walk(const char *name_, void *stream_, int64_t cap_) : name(name_), stream(stream_), cap(cap_) {}
+    ~Walk() { (void)rt_sync(stream); }  // nothing of ours is in flight when its memory goes
+    int levels() const { return depth + quiesce; }
+    int words() {
+        RT(d_word.alloc(2));
+        RT(h_word.alloc(2));
+        return BO_OK;
+    }
+    int room(int l, int64_t n) {
+        RT(lv[l].pos.room(n, cap));
+        RT(lv[l].tag.room(n, cap));
+        return BO_OK;
     }
     int room_scan(int l, int64_t n) {
-        PerftLevel &L = lv[l];
-        if (L.have_scan >= n) return 0;
-        const int64_t m = grown(L.have_scan, n, std::max(cap, n));
-        rt_free(L.cnt); rt_free(L.off);
-        L.cnt = nullptr; L.off = nullptr; L.have_scan = 0;
-        int rc = rt_malloc((void **)&L.cnt, (size_t)m * 4);
-        if (!rc) rc = rt_malloc((void **)&L.off, (size_t)(m + 1) * 8);
-        if (!rc) L.have_scan = m;
-        const int64_t nt = (m + BO_PERFT_TILE - 1) / BO_PERFT_TILE;
-        if (!rc && have_tiles < nt) {
-            rt_free(tsum); rt_free(tbase);
-            tsum = nullptr; tbase = nullptr; have_tiles = 0;
-            rc = rt_malloc((void **)&tsum, (size_t)nt * 4);
-            if (!rc) rc = rt_malloc((void **)&tbase, (size_t)nt * 8);
-            if (!rc) have_tiles = nt;
-        }
-        return rc;
+        WalkLevel &L = lv[l];
+        if (L.cnt.n >= n) return BO_OK;
+        RT(L.cnt.room(n, std::max(cap, n)));
+        const int64_t m = L.cnt.n, nt = (m + BO_PERFT_TILE - 1) / BO_PERFT_TILE;
+        RT(L.off.alloc(m + 1));
+        RT(tsum.room(nt));
+        RT(tbase.room(nt));
+        return BO_OK;
     }
-    int scan(int l, int64_t n) {  // cnt -> off of level l, the total into h_word[0] (bo_mate, bo_anchor)
-        PerftLevel &L = lv[l];
+    int room_roots(int64_t n) {
+        RT(d_roots.room(n));
+        RT(root_moves.room(n * BO_MAX_MOVES));
+        RT(root_n.room(n));
+        RT(root_chk.room(n));
+        RT(act.room(n));
+        return BO_OK;
+    }
+    int scan(int l, int64_t n) {  // cnt -> off of level l, the total into h_word[0]: the one word the host reads between levels
+        WalkLevel &L = lv[l];
         const int nt = (int)((n + BO_PERFT_TILE - 1) / BO_PERFT_TILE);
-        RT(RT_LAUNCH(bo_k_perft_tile_sums, nt, stream, (const int32_t *)L.cnt, n, tsum));
-        RT(RT_LAUNCH(bo_k_perft_tile_scan, 1, stream, (const int32_t *)tsum, nt, tbase, L.off, n));
-        RT(RT_LAUNCH(bo_k_perft_offsets, nt, stream, (const int32_t *)L.cnt, n, (const uint64_t *)tbase, L.off));
-        RT(rt_d2h(h_word, L.off + n, 8, stream));
+        RT(RT_LAUNCH(bo_k_perft_tile_sums, nt, stream, (const int32_t *)L.cnt.p, n, tsum.p));
+        RT(RT_LAUNCH(bo_k_perft_tile_scan, 1, stream, (const int32_t *)tsum.p, nt, tbase.p, L.off.p, n));
+        RT(RT_LAUNCH(bo_k_perft_offsets, nt, stream, (const int32_t *)L.cnt.p, n, (const uint64_t *)tbase.p, L.off.p));
+        RT(rt_d2h(h_word.p, L.off.p + n, 8, stream));
         RT(rt_sync(stream));
         return BO_OK;
     }
 };
 
-// the subtree below entries [0, n) of level l
-int perft_level(PerftRun &R, int l, int64_t n) {
-    PerftLevel &L = R.lv[l];
-    const uint32_t mode = ((R.flags & BO_PERFT_ORDER) ? PF_ORDER : 0u) | (l == 0 ? PF_ROOT_LEVEL : 0u);
-    if (l == R.depth - 1) {
-        if (R.flags & BO_PERFT_STATS)
-            RT(RT_LAUNCH(bo_k_perft_count_stats, n, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (int64_t)0, R.nodes, R.sums, R.stats, mode));
-        else
-            RT(RT_LAUNCH(bo_k_perft_count, n, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (int64_t)0, (int32_t *)nullptr, R.nodes, R.sums,
-                         mode | PF_LEAF));
-        return BO_OK;
-    }
-    RT(R.room_scan(l, n));
-    const int nt = (int)((n + BO_PERFT_TILE - 1) / BO_PERFT_TILE);
-    RT(RT_LAUNCH(bo_k_perft_count, n, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (int64_t)0, L.cnt, R.nodes, R.sums, mode));
-    RT(RT_LAUNCH(bo_k_perft_tile_sums, nt, R.stream, (const int32_t *)L.cnt, n, R.tsum));
-    RT(RT_LAUNCH(bo_k_perft_tile_scan, 1, R.stream, (const int32_t *)R.tsum, nt, R.tbase, L.off, n));
-    RT(RT_LAUNCH(bo_k_perft_offsets, nt, R.stream, (const int32_t *)L.cnt, n, (const uint64_t *)R.tbase, L.off));
-    RT(rt_d2h(R.h_word, L.off + n, 8, R.stream));  // the one word the host reads between levels
-    RT(rt_sync(R.stream));
-    int64_t left = R.h_word[0], a = 0;
-    while (a < n && left > 0) {
-        int64_t e = n, c = left;
-        if (left > R.cap) {  // the rest of the level does not fit: the longest run of entries from a that does
-            RT(RT_LAUNCH(bo_k_perft_split, 1, R.stream, (const uint64_t *)L.off, a, n, R.cap, R.d_word));
-            RT(rt_d2h(R.h_word, R.d_word, 16, R.stream));
-            RT(rt_sync(R.stream));
-            e = R.h_word[0];
-            c = R.h_word[1];
-            if (e <= a || e > n || c < 1 || c > R.cap) return fail(BO_E_STATE, "bo_perft: the level split is inconsistent");
-            if (c < left) R.splits++;
-        }
-        RT(R.room(l + 1, c));
-        RT(RT_LAUNCH(bo_k_perft_expand, e - a, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (const uint64_t *)L.off, a, R.lv[l + 1].pos,
-                     R.lv[l + 1].tag, R.lv[l + 1].have, mode));
-        const int rc = perft_level(R, l + 1, c);
+// The subtree below entries [0, n) of level l, whose frontier is in place.  The hooks H of a walk:
+//   enter(l, n, &bottom)  launches what fills cnt (and the values) of level l; bottom: the level has no children to walk
+//   room(l, n)            room for n entries of level l
+//   expand(l, a, e)       the children of entries [a, e) of level l into level l + 1
+//   backup(l, a, e)       the values of those children, taken to the bottom, into their parents
+//   after(a, n)           level 0 only: the roots [a, n) behind the last child
+template <class H> int walk_level(Walk &R, H &h, int l, int64_t n) {
+    WalkLevel &L = R.lv[l];
+    bool bottom = false;
+    int rc = h.enter(l, n, &bottom);
+    if (rc) return rc;
+    int64_t a = 0;
+    if (!bottom) {
+        rc = R.scan(l, n);
         if (rc) return rc;
-        left -= c;
-        a = e;
+        int64_t left = R.h_word.p[0];
+        while (a < n && left > 0) {
+            int64_t e = n, c = left;
+            if (left > R.cap) {  // the rest of the level does not fit: the longest run of entries from a that does
+                RT(RT_LAUNCH(bo_k_perft_split, 1, R.stream, (const uint64_t *)L.off.p, a, n, R.cap, R.d_word.p));
+                RT(rt_d2h(R.h_word.p, R.d_word.p, 16, R.stream));
+                RT(rt_sync(R.stream));
+                e = R.h_word.p[0];
+                c = R.h_word.p[1];
+                if (e <= a || e > n || c < 1 || c > R.cap) return fail(BO_E_STATE, std::string(R.name) + ": the level split is inconsistent");
+                if (c < left) R.splits++;
+            }
+            rc = h.room(l + 1, c);
+            if (!rc) rc = h.expand(l, a, e);
+            if (!rc) rc = walk_level(R, h, l + 1, c);
+            if (!rc) rc = h.backup(l, a, e);
+            if (rc) return rc;
+            left -= c;
+            a = e;
+        }
+    }
+    return l == 0 && a < n ? h.after(a, n) : BO_OK;
+}
+
+// what the generator's 256-move lists and its king lookups need of a position (include/betaone_engine.h: "not a position")
+bool position_ok(const DPos &p) {
+    uint64_t all = 0;
+    for (int i = 0; i < 6; i++) {
+        if (all & p.bb[i]) return false;
+        all |= p.bb[i];
+    }
+    if ((p.bb[BB_WHITE] & p.bb[BB_BLACK]) || (p.bb[BB_WHITE] | p.bb[BB_BLACK]) != all) return false;
+    if (p.bb[BB_P] & (RANK_1 | RANK_8)) return false;
+    for (int c = 0; c < 2; c++) {
+        const uint64_t own = p.bb[c ? BB_BLACK : BB_WHITE];
+        auto cnt = [&](int t) { return __builtin_popcountll(p.bb[t] & own); };
+        if (cnt(BB_K) != 1 || __builtin_popcountll(own) > 16 || cnt(BB_P) > 8) return false;
+        const int extra = std::max(0, cnt(BB_N) - 2) + std::max(0, cnt(BB_B) - 2) + std::max(0, cnt(BB_R) - 2) + std::max(0, cnt(BB_Q) - 1);
+        if (extra > 8 - cnt(BB_P)) return false;
+    }
+    return true;
+}
+bool record_ok(const bo_position &q, DPos *p) {
+    const bool fields = (q.turn == 0 || q.turn == 1) && q.castling <= 0xFu && q.ep_square >= -1 && q.ep_square <= 63 && q.ep_key >= -2 && q.ep_key <= 63;
+    if (fields) *p = from_abi(q);
+    return fields && position_ok(*p);
+}
+int capacity_ok(const std::string &who, int64_t capacity) {
+    if (capacity < BO_MAX_MOVES || capacity > ((int64_t)1 << 26))
+        return fail(BO_E_CONFIG, who + ": capacity must be 256 (the children of one position) .. 2^26 positions per level");
+    return BO_OK;
+}
+
+// The roots of bo_mate and bo_anchor that are positions, and their rows in the caller's arrays.  Every result is zeroed, then init(result)
+// row by row; a FEN that is no position fails the call there, a record that is none gets the status `not_a_position` and is left out.
+template <class Res, class Init>
+int collect_roots(const std::string &who, size_t N, const char *const *fens, const bo_position *positions, Res *results, Init init,
+                  int32_t not_a_position, std::vector<DPos> &roots, std::vector<int32_t> &index) {
+    roots.reserve(N); index.reserve(N);
+    memset(results, 0, N * sizeof(Res));
+    for (size_t i = 0; i < N; i++) {
+        DPos p;
+        init(results[i]);
+        if (fens) {
+            if (!pgn_fen_root(fens[i] ? fens[i] : "", &p) || !position_ok(p)) return fail(BO_E_FEN, who + ": bad FEN (root " + std::to_string(i) + ")");
+        } else if (!record_ok(positions[i], &p)) { results[i].status = not_a_position; continue; }
+        roots.push_back(p);
+        index.push_back((int32_t)i);
     }
     return BO_OK;
 }
+
+// The roots on the device: finished in place (key fields as bo_k_perft_roots leaves them), their move lists moves [n][256], counts and
+// check bits; active = the roots that are searched: a position with a move.
+int prepare_roots(Walk &R, std::vector<DPos> &roots, std::vector<int32_t> &moves, std::vector<int32_t> &rn, std::vector<int32_t> &chk,
+                  std::vector<int32_t> &active) {
+    const size_t n = roots.size();
+    moves.assign(n * BO_MAX_MOVES, -1); rn.assign(n, 0); chk.assign(n, 0); active.clear();
+    if (!n) return BO_OK;
+    int rc = R.room_roots((int64_t)n);
+    if (rc) return rc;
+    RT(rt_h2d(R.d_roots.p, roots.data(), n * sizeof(DPos), R.stream));
+    RT(RT_LAUNCH(bo_k_mate_roots, n, R.stream, R.d_roots.p, R.root_moves.p, R.root_n.p, R.root_chk.p));
+    RT(rt_d2h(roots.data(), R.d_roots.p, n * sizeof(DPos), R.stream));
+    RT(rt_d2h(moves.data(), R.root_moves.p, moves.size() * 4, R.stream));
+    RT(rt_d2h(rn.data(), R.root_n.p, n * 4, R.stream));
+    RT(rt_d2h(chk.data(), R.root_chk.p, n * 4, R.stream));
+    RT(rt_sync(R.stream));
+    for (size_t r = 0; r < n; r++)
+        if (!(chk[r] & 2) && rn[r] > 0) active.push_back((int32_t)r);
+    return BO_OK;
+}
+
+struct PerftWalk {
+    Walk &R;
+    uint32_t mode(int l) const { return ((R.flags & BO_PERFT_ORDER) ? PF_ORDER : 0u) | (l == 0 ? PF_ROOT_LEVEL : 0u); }
+    int enter(int l, int64_t n, bool *bottom) {
+        WalkLevel &L = R.lv[l];
+        *bottom = l == R.depth - 1;
+        if (*bottom && (R.flags & BO_PERFT_STATS))
+            RT(RT_LAUNCH(bo_k_perft_count_stats, n, R.stream, (const DPos *)L.pos.p, (const int32_t *)L.tag.p, (int64_t)0, R.nodes.p, R.sums.p,
+                         R.stats.p, mode(l)));
+        else if (*bottom)
+            RT(RT_LAUNCH(bo_k_perft_count, n, R.stream, (const DPos *)L.pos.p, (const int32_t *)L.tag.p, (int64_t)0, (int32_t *)nullptr, R.nodes.p,
+                         R.sums.p, mode(l) | PF_LEAF));
+        else {
+            const int rc = R.room_scan(l, n);
+            if (rc) return rc;
+            RT(RT_LAUNCH(bo_k_perft_count, n, R.stream, (const DPos *)L.pos.p, (const int32_t *)L.tag.p, (int64_t)0, L.cnt.p, R.nodes.p, R.sums.p,
+                         mode(l)));
+        }
+        return BO_OK;
+    }
+    int room(int l, int64_t n) { return R.room(l, n); }
+    int expand(int l, int64_t a, int64_t e) {
+        WalkLevel &L = R.lv[l], &C = R.lv[l + 1];
+        RT(RT_LAUNCH(bo_k_perft_expand, e - a, R.stream, (const DPos *)L.pos.p, (const int32_t *)L.tag.p, (const uint64_t *)L.off.p, a, C.pos.p,
+                     C.tag.p, C.pos.n, mode(l)));
+        return BO_OK;
+    }
+    int backup(int, int64_t, int64_t) { return BO_OK; }
+    int after(int64_t, int64_t) { return BO_OK; }
+};
 }  // namespace
 
 extern "C" int bo_perft(int device, int32_t n_roots, const char *const *fens, int32_t depth, int64_t capacity, uint32_t flags,
@@ -3222,8 +3359,8 @@ extern "C" int bo_perft(int device, int32_t n_roots, const char *const *fens, in
         return fail(BO_E_ARG, "bo_perft: bad arguments (n_roots <= 2^20, 0 <= depth <= 64)");
     const bool divide = (flags & BO_PERFT_DIVIDE) != 0;
     if (divide && n_roots && (!divide_moves || !divide_nodes)) return fail(BO_E_ARG, "bo_perft: BO_PERFT_DIVIDE needs divide_moves and divide_nodes");
-    if (capacity < BO_MAX_MOVES || capacity > ((int64_t)1 << 26))
-        return fail(BO_E_CONFIG, "bo_perft: capacity must be 256 (the children of one position) .. 2^26 positions per level");
+    int rc = capacity_ok("bo_perft", capacity);
+    if (rc) return rc;
     if (n_roots == 0) return BO_OK;
     std::vector<DPos> roots((size_t)n_roots);
     for (int i = 0; i < n_roots; i++) {
@@ -3239,40 +3376,38 @@ extern "C" int bo_perft(int device, int32_t n_roots, const char *const *fens, in
         return BO_OK;
     }
     RT(rt_set_device(device));
-    PerftRun R;
-    R.stream = stream; R.depth = depth; R.cap = capacity; R.flags = flags;
+    Walk R("bo_perft", stream, capacity);
+    R.depth = depth; R.flags = flags;
     R.lv.resize((size_t)depth);
-    {   // level 0: the roots (outside `capacity`: the caller chose their number)
-        PerftLevel &L = R.lv[0];
-        RT(rt_malloc((void **)&L.pos, N * sizeof(DPos)));
-        RT(rt_malloc((void **)&L.tag, N * 4));
-        L.have = n_roots;
-    }
-    RT(rt_malloc((void **)&R.root_moves, N * BO_MAX_MOVES * 4));
-    RT(rt_malloc((void **)&R.root_n, N * 4));
-    RT(rt_malloc((void **)&R.nodes, N * BO_MAX_MOVES * 8));
-    RT(rt_malloc((void **)&R.sums, N * 8));
-    RT(rt_malloc((void **)&R.stats, N * PF_NSTATS * 8));
-    RT(rt_malloc((void **)&R.d_word, 16));
-    RT(rt_host_alloc((void **)&R.h_word, 16));
+    WalkLevel &L0 = R.lv[0];  // level 0: the roots (outside `capacity`: the caller chose their number)
+    RT(L0.pos.alloc(n_roots));
+    RT(L0.tag.alloc(n_roots));
+    RT(R.root_moves.alloc(n_roots * (int64_t)BO_MAX_MOVES));
+    RT(R.root_n.alloc(n_roots));
+    RT(R.nodes.alloc(n_roots * (int64_t)BO_MAX_MOVES));
+    RT(R.sums.alloc(n_roots));
+    RT(R.stats.alloc(n_roots * (int64_t)PF_NSTATS));
+    rc = R.words();
+    if (rc) return rc;
     std::vector<int32_t> tags(N);
     for (size_t i = 0; i < N; i++) tags[i] = (int32_t)(i * BO_MAX_MOVES);
-    RT(rt_h2d(R.lv[0].pos, roots.data(), N * sizeof(DPos), stream));
-    RT(rt_h2d(R.lv[0].tag, tags.data(), N * 4, stream));
-    RT(rt_memset(R.nodes, 0, N * BO_MAX_MOVES * 8, stream));
-    RT(rt_memset(R.sums, 0, N * 8, stream));
-    RT(rt_memset(R.stats, 0, N * PF_NSTATS * 8, stream));
-    RT(RT_LAUNCH(bo_k_perft_roots, n_roots, stream, R.lv[0].pos, R.root_moves, R.root_n));
+    RT(rt_h2d(L0.pos.p, roots.data(), N * sizeof(DPos), stream));
+    RT(rt_h2d(L0.tag.p, tags.data(), N * 4, stream));
+    RT(rt_memset(R.nodes.p, 0, N * BO_MAX_MOVES * 8, stream));
+    RT(rt_memset(R.sums.p, 0, N * 8, stream));
+    RT(rt_memset(R.stats.p, 0, N * PF_NSTATS * 8, stream));
+    RT(RT_LAUNCH(bo_k_perft_roots, n_roots, stream, L0.pos.p, R.root_moves.p, R.root_n.p));
     RT(rt_sync(stream));  // (roots and tags are host vectors of this frame)
-    const int rc = perft_level(R, 0, n_roots);
+    PerftWalk P{R};
+    rc = walk_level(R, P, 0, n_roots);
     if (rc) return rc;
     std::vector<uint64_t> nodes(N * BO_MAX_MOVES), sums(N), stats(N * PF_NSTATS);
     std::vector<int32_t> rmoves(N * BO_MAX_MOVES), rn(N);
-    RT(rt_d2h(nodes.data(), R.nodes, nodes.size() * 8, stream));
-    RT(rt_d2h(sums.data(), R.sums, sums.size() * 8, stream));
-    RT(rt_d2h(stats.data(), R.stats, stats.size() * 8, stream));
-    RT(rt_d2h(rmoves.data(), R.root_moves, rmoves.size() * 4, stream));
-    RT(rt_d2h(rn.data(), R.root_n, rn.size() * 4, stream));
+    RT(rt_d2h(nodes.data(), R.nodes.p, nodes.size() * 8, stream));
+    RT(rt_d2h(sums.data(), R.sums.p, sums.size() * 8, stream));
+    RT(rt_d2h(stats.data(), R.stats.p, stats.size() * 8, stream));
+    RT(rt_d2h(rmoves.data(), R.root_moves.p, rmoves.size() * 4, stream));
+    RT(rt_d2h(rn.data(), R.root_n.p, rn.size() * 4, stream));
     RT(rt_sync(stream));
     for (size_t r = 0; r < N; r++) {
         bo_perft_result &o = results[r];
@@ -3297,140 +3432,80 @@ extern "C" int bo_perft(int device, int32_t n_roots, const char *const *fens, in
 }
 
 // ---- forced mates on the device (bo_mate.h) ----------------------------------------------------------------------------------------
-// The walk is perft's: a frontier per level, PerftRun's buffers, scan and split.  Each level also keeps one value byte per entry, an
-// attacker level (even) the live masks of its entries; after a chunk of level l + 1 has been taken to the bottom, its values are backed
-// up into the parents of level l that the chunk was expanded from.
+// The walk is perft's.  Each level also keeps one value byte per entry, an attacker level (even) the live masks of its entries; after a
+// chunk of level l + 1 has been taken to the bottom, its values are backed up into the parents of level l that the chunk was expanded from.
 namespace {
 struct MateRoot {
     int32_t dtm = 0, searched = 0, n_moves = 0, n_keys = 0, key = -1, chk = 0;
     uint64_t mask[4] = {0, 0, 0, 0};
 };
-struct MateRun : PerftRun {
-    std::vector<uint8_t *> val;    // per level [have_val]
-    std::vector<uint64_t *> live;  // per attacker level [have_val][4]
-    std::vector<int64_t> have_val;
-    // per root of the current solve [have_roots]: the roots, check bits, active -> root, key mask [4], keys, lowest key
-    DPos *d_roots = nullptr;
-    int32_t *root_chk = nullptr, *act = nullptr, *n_keys = nullptr, *key = nullptr;
-    uint64_t *keymask = nullptr;
-    int64_t have_roots = 0;
-    uint64_t visited = 0;  // frontier entries of every level of every walk (include/betaone_engine.h: nodes)
-    ~MateRun() {
-        (void)rt_sync(stream);
-        for (uint8_t *p : val) rt_free(p);
-        for (uint64_t *p : live) rt_free(p);
-        rt_free(d_roots); rt_free(root_chk); rt_free(act); rt_free(n_keys); rt_free(key); rt_free(keymask);
+struct MateWalk {
+    Walk &R;
+    int enter(int l, int64_t n, bool *bottom) {
+        WalkLevel &L = R.lv[l];
+        const bool last = l == R.depth - 1;
+        R.visited += (uint64_t)n;
+        if (!(l & 1))
+            RT(RT_LAUNCH(bo_k_mate_attack, n, R.stream, (const DPos *)L.pos.p, L.cnt.p, L.mate_val.p, L.live.p,
+                         l == 0 ? R.keymask.p : (uint64_t *)nullptr, (last ? MT_LAST : 0u) | (l == 0 ? MT_ROOT : 0u)));
+        else
+            RT(RT_LAUNCH(bo_k_perft_count, n, R.stream, (const DPos *)L.pos.p, (const int32_t *)L.tag.p, (int64_t)0, L.cnt.p, (uint64_t *)nullptr,
+                         (uint64_t *)nullptr, 0u));
+        *bottom = last;  // (every count is 0: no offsets are read)
+        return BO_OK;
     }
-    void levels(size_t k) {
-        if (lv.size() >= k) return;
-        lv.resize(k); val.resize(k, nullptr); live.resize(k, nullptr); have_val.resize(k, 0);
+    int room(int l, int64_t n) {
+        int rc = R.room(l, n);
+        if (!rc) rc = R.room_scan(l, n);
+        WalkLevel &L = R.lv[l];
+        const int64_t m = L.pos.n;
+        if (rc || L.mate_val.n >= m) return rc;
+        RT(L.mate_val.alloc(m));
+        if (!(l & 1)) RT(L.live.alloc(4 * m));
+        return BO_OK;
     }
-    int room_mate(int l, int64_t n) {
-        int rc = room(l, n);
-        if (!rc) rc = room_scan(l, n);
-        const int64_t m = lv[l].have;
-        if (rc || have_val[l] >= m) return rc;
-        rt_free(val[l]); rt_free(live[l]);
-        val[l] = nullptr; live[l] = nullptr; have_val[l] = 0;
-        rc = rt_malloc((void **)&val[l], (size_t)m);
-        if (!rc && !(l & 1)) rc = rt_malloc((void **)&live[l], (size_t)m * 32);
-        if (!rc) have_val[l] = m;
-        return rc;
+    int room_keys(int64_t n) {
+        RT(R.n_keys.room(n));
+        RT(R.key.room(n));
+        RT(R.keymask.room(4 * n));
+        return BO_OK;
     }
-    int room_roots(int64_t n) {
-        if (have_roots >= n) return 0;
-        rt_free(d_roots); rt_free(root_moves); rt_free(root_n); rt_free(root_chk); rt_free(act); rt_free(n_keys); rt_free(key); rt_free(keymask);
-        d_roots = nullptr; root_moves = root_n = root_chk = act = n_keys = key = nullptr; keymask = nullptr; have_roots = 0;
-        const size_t N = (size_t)n;
-        int rc = rt_malloc((void **)&d_roots, N * sizeof(DPos));
-        if (!rc) rc = rt_malloc((void **)&root_moves, N * BO_MAX_MOVES * 4);
-        if (!rc) rc = rt_malloc((void **)&root_n, N * 4);
-        if (!rc) rc = rt_malloc((void **)&root_chk, N * 4);
-        if (!rc) rc = rt_malloc((void **)&act, N * 4);
-        if (!rc) rc = rt_malloc((void **)&n_keys, N * 4);
-        if (!rc) rc = rt_malloc((void **)&key, N * 4);
-        if (!rc) rc = rt_malloc((void **)&keymask, N * 32);
-        if (!rc) have_roots = n;
-        return rc;
+    int expand(int l, int64_t a, int64_t e) {
+        WalkLevel &L = R.lv[l], &C = R.lv[l + 1];
+        if (!(l & 1))
+            RT(RT_LAUNCH(bo_k_mate_expand, e - a, R.stream, (const DPos *)L.pos.p, (const uint64_t *)L.off.p, (const uint64_t *)L.live.p, a, C.pos.p,
+                         C.tag.p, C.pos.n));
+        else
+            RT(RT_LAUNCH(bo_k_perft_expand, e - a, R.stream, (const DPos *)L.pos.p, (const int32_t *)L.tag.p, (const uint64_t *)L.off.p, a, C.pos.p,
+                         C.tag.p, C.pos.n, 0u));
+        return BO_OK;
     }
+    int backup(int l, int64_t a, int64_t e) {
+        WalkLevel &L = R.lv[l];
+        const uint8_t *below = l + 1 < (int)R.lv.size() ? R.lv[l + 1].mate_val.p : nullptr;  // (read only by parents that have children)
+        if (l == 0)
+            RT(RT_LAUNCH(bo_k_mate_backup_root, e - a, R.stream, (const int32_t *)L.cnt.p, (const uint64_t *)L.off.p, a, below, L.mate_val.p,
+                         (const uint64_t *)L.live.p, R.keymask.p, (const int32_t *)R.act.p, (const int32_t *)R.root_moves.p, R.n_keys.p, R.key.p));
+        else
+            RT(RT_LAUNCH(bo_k_mate_backup, e - a, R.stream, (const int32_t *)L.cnt.p, (const uint64_t *)L.off.p, a, below, L.mate_val.p,
+                         (uint32_t)!(l & 1)));
+        return BO_OK;
+    }
+    int after(int64_t a, int64_t n) { return backup(0, a, n); }  // mates in 1 and roots without a live move
 };
 
-int mate_backup(MateRun &R, int l, int64_t a, int64_t e) {
-    PerftLevel &L = R.lv[l];
-    const uint8_t *below = l + 1 < (int)R.lv.size() ? R.val[l + 1] : nullptr;  // (read only by parents that have children)
-    if (l == 0)
-        RT(RT_LAUNCH(bo_k_mate_backup_root, e - a, R.stream, (const int32_t *)L.cnt, (const uint64_t *)L.off, a, below, R.val[0],
-                     (const uint64_t *)R.live[0], R.keymask, (const int32_t *)R.act, (const int32_t *)R.root_moves, R.n_keys, R.key));
-    else
-        RT(RT_LAUNCH(bo_k_mate_backup, e - a, R.stream, (const int32_t *)L.cnt, (const uint64_t *)L.off, a, below, R.val[l], (uint32_t)!(l & 1)));
-    return BO_OK;
-}
-
-// the values of entries [0, n) of level l (R.room_mate(l, n) has been called)
-int mate_level(MateRun &R, int l, int64_t n) {
-    PerftLevel &L = R.lv[l];
-    const bool attacker = !(l & 1), last = l == R.depth - 1;
-    R.visited += (uint64_t)n;
-    if (attacker)
-        RT(RT_LAUNCH(bo_k_mate_attack, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], R.live[l], l == 0 ? R.keymask : (uint64_t *)nullptr,
-                     (last ? MT_LAST : 0u) | (l == 0 ? MT_ROOT : 0u)));
-    else
-        RT(RT_LAUNCH(bo_k_perft_count, n, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (int64_t)0, L.cnt, (uint64_t *)nullptr,
-                     (uint64_t *)nullptr, 0u));
-    if (last) return l == 0 ? mate_backup(R, 0, 0, n) : BO_OK;  // (every count is 0: no offsets are read)
-    int rc = R.scan(l, n);
-    if (rc) return rc;
-    int64_t left = R.h_word[0], a = 0;
-    while (a < n && left > 0) {
-        int64_t e = n, c = left;
-        if (left > R.cap) {
-            RT(RT_LAUNCH(bo_k_perft_split, 1, R.stream, (const uint64_t *)L.off, a, n, R.cap, R.d_word));
-            RT(rt_d2h(R.h_word, R.d_word, 16, R.stream));
-            RT(rt_sync(R.stream));
-            e = R.h_word[0];
-            c = R.h_word[1];
-            if (e <= a || e > n || c < 1 || c > R.cap) return fail(BO_E_STATE, "bo_mate: the level split is inconsistent");
-            if (c < left) R.splits++;
-        }
-        RT(R.room_mate(l + 1, c));
-        PerftLevel &C = R.lv[l + 1];
-        if (attacker)
-            RT(RT_LAUNCH(bo_k_mate_expand, e - a, R.stream, (const DPos *)L.pos, (const uint64_t *)L.off, (const uint64_t *)R.live[l], a, C.pos, C.tag,
-                         C.have));
-        else
-            RT(RT_LAUNCH(bo_k_perft_expand, e - a, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (const uint64_t *)L.off, a, C.pos, C.tag,
-                         C.have, 0u));
-        rc = mate_level(R, l + 1, c);
-        if (!rc) rc = mate_backup(R, l, a, e);
-        if (rc) return rc;
-        left -= c;
-        a = e;
-    }
-    if (l == 0 && a < n) return mate_backup(R, 0, a, n);  // roots behind the last child: mates in 1 and roots without a live move
-    return BO_OK;
-}
-
-// Iterative deepening over `roots` (finished in place: key fields as bo_k_perft_roots leaves them): n = 1 .. N over the roots still
-// unresolved.  moves [n][256] = the roots' move lists.
-int mate_solve(MateRun &R, std::vector<DPos> &roots, int N, uint64_t max_nodes, std::vector<MateRoot> &out, std::vector<int32_t> &moves) {
+// Iterative deepening over `roots` (finished in place): n = 1 .. N over the roots still unresolved.  moves [n][256] = the roots' move lists.
+int mate_solve(MateWalk &M, std::vector<DPos> &roots, int N, uint64_t max_nodes, std::vector<MateRoot> &out, std::vector<int32_t> &moves) {
+    Walk &R = M.R;
     const size_t n = roots.size();
     out.assign(n, MateRoot());
-    moves.assign(n * BO_MAX_MOVES, -1);
-    if (!n) return BO_OK;
-    RT(R.room_roots((int64_t)n));
-    std::vector<int32_t> rn(n), chk(n);
-    RT(rt_h2d(R.d_roots, roots.data(), n * sizeof(DPos), R.stream));
-    RT(RT_LAUNCH(bo_k_mate_roots, n, R.stream, R.d_roots, R.root_moves, R.root_n, R.root_chk));
-    RT(rt_d2h(roots.data(), R.d_roots, n * sizeof(DPos), R.stream));
-    RT(rt_d2h(moves.data(), R.root_moves, moves.size() * 4, R.stream));
-    RT(rt_d2h(rn.data(), R.root_n, n * 4, R.stream));
-    RT(rt_d2h(chk.data(), R.root_chk, n * 4, R.stream));
-    RT(rt_sync(R.stream));
-    std::vector<int32_t> active;
+    std::vector<int32_t> rn, chk, active;
+    int rc = n ? M.room_keys((int64_t)n) : BO_OK;
+    if (!rc) rc = prepare_roots(R, roots, moves, rn, chk, active);
+    if (rc) return rc;
     for (size_t r = 0; r < n; r++) {
         out[r].n_moves = rn[r];
         out[r].chk = chk[r];
-        if (!(chk[r] & 2) && rn[r] > 0) active.push_back((int32_t)r);
     }
     std::vector<DPos> sub;
     std::vector<uint8_t> v;
@@ -3440,20 +3515,21 @@ int mate_solve(MateRun &R, std::vector<DPos> &roots, int N, uint64_t max_nodes, 
         if (max_nodes && R.visited > max_nodes) break;
         const size_t na = active.size();
         R.depth = 2 * it - 1;
-        R.levels((size_t)R.depth);
-        RT(R.room_mate(0, (int64_t)na));
+        if (R.lv.size() < (size_t)R.depth) R.lv.resize((size_t)R.depth);
+        rc = M.room(0, (int64_t)na);
+        if (rc) return rc;
         sub.resize(na);
         for (size_t i = 0; i < na; i++) sub[i] = roots[(size_t)active[i]];
-        RT(rt_h2d(R.lv[0].pos, sub.data(), na * sizeof(DPos), R.stream));
-        RT(rt_h2d(R.act, active.data(), na * 4, R.stream));
+        RT(rt_h2d(R.lv[0].pos.p, sub.data(), na * sizeof(DPos), R.stream));
+        RT(rt_h2d(R.act.p, active.data(), na * 4, R.stream));
         RT(rt_sync(R.stream));
-        const int rc = mate_level(R, 0, (int64_t)na);
+        rc = walk_level(R, M, 0, (int64_t)na);
         if (rc) return rc;
         v.resize(na); nk.resize(na); ky.resize(na); km.resize(na * 4);
-        RT(rt_d2h(v.data(), R.val[0], na, R.stream));
-        RT(rt_d2h(nk.data(), R.n_keys, na * 4, R.stream));
-        RT(rt_d2h(ky.data(), R.key, na * 4, R.stream));
-        RT(rt_d2h(km.data(), R.keymask, na * 32, R.stream));
+        RT(rt_d2h(v.data(), R.lv[0].mate_val.p, na, R.stream));
+        RT(rt_d2h(nk.data(), R.n_keys.p, na * 4, R.stream));
+        RT(rt_d2h(ky.data(), R.key.p, na * 4, R.stream));
+        RT(rt_d2h(km.data(), R.keymask.p, na * 32, R.stream));
         RT(rt_sync(R.stream));
         std::vector<int32_t> next;
         for (size_t i = 0; i < na; i++) {
@@ -3471,7 +3547,8 @@ int mate_solve(MateRun &R, std::vector<DPos> &roots, int N, uint64_t max_nodes, 
 
 // The principal variation of every solved root: pv [n][W].  Along the line the attacker's move is known (the lowest-index key); the
 // defender's replies of all unfinished lines become one batch of roots, solved at the remaining distance.
-int mate_pv(MateRun &R, const std::vector<DPos> &roots, const std::vector<MateRoot> &out, const std::vector<int32_t> &index, int W, int32_t *pv) {
+int mate_pv(MateWalk &M, const std::vector<DPos> &roots, const std::vector<MateRoot> &out, const std::vector<int32_t> &index, int W, int32_t *pv) {
+    Walk &R = M.R;
     struct Line { size_t row; DPos A; int32_t key; int d, ply; };
     std::vector<Line> lines;
     for (size_t r = 0; r < roots.size(); r++)
@@ -3489,33 +3566,36 @@ int mate_pv(MateRun &R, const std::vector<DPos> &roots, const std::vector<MateRo
         std::vector<int32_t> keys(ns);
         int nsub = 1;
         for (size_t j = 0; j < ns; j++) { A[j] = lines[S[j]].A; keys[j] = lines[S[j]].key; nsub = std::max(nsub, (lines[S[j]].d - 1) / 2); }
-        R.levels(2);
-        RT(R.room_roots((int64_t)ns));
-        RT(R.room_mate(0, (int64_t)ns));
-        PerftLevel &L = R.lv[0];
-        RT(rt_h2d(L.pos, A.data(), ns * sizeof(DPos), R.stream));
-        RT(rt_h2d(R.key, keys.data(), ns * 4, R.stream));
-        RT(RT_LAUNCH(bo_k_mate_play, (ns + 63) / 64, R.stream, (const DPos *)L.pos, (const int32_t *)R.key, (int64_t)ns, L.pos, L.tag));
-        RT(RT_LAUNCH(bo_k_mate_roots, ns, R.stream, L.pos, R.root_moves, R.root_n, R.root_chk));  // the replies' words
-        RT(RT_LAUNCH(bo_k_perft_count, ns, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (int64_t)0, L.cnt, (uint64_t *)nullptr,
-                     (uint64_t *)nullptr, 0u));
-        int rc = R.scan(0, (int64_t)ns);
+        if (R.lv.size() < 2) R.lv.resize(2);
+        int rc = R.room_roots((int64_t)ns);
+        if (!rc) rc = M.room_keys((int64_t)ns);
+        if (!rc) rc = M.room(0, (int64_t)ns);
         if (rc) return rc;
-        const int64_t T = R.h_word[0];
+        WalkLevel &L = R.lv[0];
+        RT(rt_h2d(L.pos.p, A.data(), ns * sizeof(DPos), R.stream));
+        RT(rt_h2d(R.key.p, keys.data(), ns * 4, R.stream));
+        RT(RT_LAUNCH(bo_k_mate_play, (ns + 63) / 64, R.stream, (const DPos *)L.pos.p, (const int32_t *)R.key.p, (int64_t)ns, L.pos.p, L.tag.p));
+        RT(RT_LAUNCH(bo_k_mate_roots, ns, R.stream, L.pos.p, R.root_moves.p, R.root_n.p, R.root_chk.p));  // the replies' words
+        RT(RT_LAUNCH(bo_k_perft_count, ns, R.stream, (const DPos *)L.pos.p, (const int32_t *)L.tag.p, (int64_t)0, L.cnt.p, (uint64_t *)nullptr,
+                     (uint64_t *)nullptr, 0u));
+        rc = R.scan(0, (int64_t)ns);
+        if (rc) return rc;
+        const int64_t T = R.h_word.p[0];
         if (T < (int64_t)ns) return fail(BO_E_STATE, "bo_mate: a defender on a mating line has no reply");
-        RT(R.room(1, T));
-        RT(RT_LAUNCH(bo_k_perft_expand, ns, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (const uint64_t *)L.off, (int64_t)0, R.lv[1].pos,
-                     R.lv[1].tag, R.lv[1].have, 0u));
+        rc = R.room(1, T);
+        if (rc) return rc;
+        RT(RT_LAUNCH(bo_k_perft_expand, ns, R.stream, (const DPos *)L.pos.p, (const int32_t *)L.tag.p, (const uint64_t *)L.off.p, (int64_t)0,
+                     R.lv[1].pos.p, R.lv[1].tag.p, R.lv[1].pos.n, 0u));
         std::vector<DPos> B((size_t)T);
         std::vector<uint64_t> off(ns + 1);
         std::vector<int32_t> words(ns * BO_MAX_MOVES);
-        RT(rt_d2h(B.data(), R.lv[1].pos, (size_t)T * sizeof(DPos), R.stream));
-        RT(rt_d2h(off.data(), L.off, (ns + 1) * 8, R.stream));
-        RT(rt_d2h(words.data(), R.root_moves, words.size() * 4, R.stream));
+        RT(rt_d2h(B.data(), R.lv[1].pos.p, (size_t)T * sizeof(DPos), R.stream));
+        RT(rt_d2h(off.data(), L.off.p, (ns + 1) * 8, R.stream));
+        RT(rt_d2h(words.data(), R.root_moves.p, words.size() * 4, R.stream));
         RT(rt_sync(R.stream));
         std::vector<MateRoot> ob;
         std::vector<int32_t> mb;
-        rc = mate_solve(R, B, nsub, 0, ob, mb);
+        rc = mate_solve(M, B, nsub, 0, ob, mb);
         if (rc) return rc;
         for (size_t j = 0; j < ns; j++) {
             Line &ln = lines[S[j]];
@@ -3533,25 +3613,6 @@ int mate_pv(MateRun &R, const std::vector<DPos> &roots, const std::vector<MateRo
         }
     }
 }
-
-// what the generator's 256-move lists and its king lookups need of a position (include/betaone_engine.h: "not a position")
-bool mate_position_ok(const DPos &p) {
-    uint64_t all = 0;
-    for (int i = 0; i < 6; i++) {
-        if (all & p.bb[i]) return false;
-        all |= p.bb[i];
-    }
-    if ((p.bb[BB_WHITE] & p.bb[BB_BLACK]) || (p.bb[BB_WHITE] | p.bb[BB_BLACK]) != all) return false;
-    if (p.bb[BB_P] & (RANK_1 | RANK_8)) return false;
-    for (int c = 0; c < 2; c++) {
-        const uint64_t own = p.bb[c ? BB_BLACK : BB_WHITE];
-        auto cnt = [&](int t) { return __builtin_popcountll(p.bb[t] & own); };
-        if (cnt(BB_K) != 1 || __builtin_popcountll(own) > 16 || cnt(BB_P) > 8) return false;
-        const int extra = std::max(0, cnt(BB_N) - 2) + std::max(0, cnt(BB_B) - 2) + std::max(0, cnt(BB_R) - 2) + std::max(0, cnt(BB_Q) - 1);
-        if (extra > 8 - cnt(BB_P)) return false;
-    }
-    return true;
-}
 }  // namespace
 
 extern "C" int bo_mate(int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t max_moves, int64_t capacity,
@@ -3560,45 +3621,31 @@ extern "C" int bo_mate(int device, int32_t n_roots, const char *const *fens, con
     if (n_roots < 0 || n_roots > (1 << 20) || (fens != nullptr) == (positions != nullptr))
         return fail(BO_E_ARG, "bo_mate: exactly one of fens and positions, n_roots <= 2^20");
     if (max_moves < 1 || max_moves > BO_MATE_MAX_MOVES) return fail(BO_E_ARG, "bo_mate: max_moves must be 1 .. 16");
-    if (capacity < BO_MAX_MOVES || capacity > ((int64_t)1 << 26))
-        return fail(BO_E_CONFIG, "bo_mate: capacity must be 256 (the children of one position) .. 2^26 positions per level");
+    int rc = capacity_ok("bo_mate", capacity);
+    if (rc) return rc;
     if (flags & ~(uint32_t)BO_MATE_PV) return fail(BO_E_ARG, "bo_mate: unknown flag bits");
     if (n_roots && (!results || ((flags & BO_MATE_PV) && !pv))) return fail(BO_E_ARG, "bo_mate: results (and pv with BO_MATE_PV) must be given");
     if (n_roots == 0) return BO_OK;
     const size_t N = (size_t)n_roots;
     const int W = 2 * max_moves - 1;
-    std::vector<DPos> roots;       // the roots that are positions
-    std::vector<int32_t> index;    // their rows in the caller's arrays
-    roots.reserve(N); index.reserve(N);
-    memset(results, 0, N * sizeof(bo_mate_result));
-    for (size_t i = 0; i < N; i++) {
-        DPos p;
-        results[i].key = -1;
-        if (fens) {
-            if (!pgn_fen_root(fens[i] ? fens[i] : "", &p) || !mate_position_ok(p)) return fail(BO_E_FEN, "bo_mate: bad FEN (root " + std::to_string(i) + ")");
-        } else {
-            const bo_position &q = positions[i];
-            const bool fields = (q.turn == 0 || q.turn == 1) && q.castling <= 0xFu && q.ep_square >= -1 && q.ep_square <= 63 && q.ep_key >= -2 && q.ep_key <= 63;
-            if (fields) p = from_abi(q);
-            if (!fields || !mate_position_ok(p)) { results[i].status = BO_MATE_NOT_A_POSITION; continue; }
-        }
-        roots.push_back(p);
-        index.push_back((int32_t)i);
-    }
+    std::vector<DPos> roots;     // the roots that are positions
+    std::vector<int32_t> index;  // their rows in the caller's arrays
+    rc = collect_roots("bo_mate", N, fens, positions, results, [](bo_mate_result &o) { o.key = -1; }, BO_MATE_NOT_A_POSITION, roots, index);
+    if (rc) return rc;
     if (key_moves)
         for (size_t i = 0; i < N * BO_MAX_MOVES; i++) key_moves[i] = -1;
     if (flags & BO_MATE_PV)
         for (size_t i = 0; i < N * (size_t)W; i++) pv[i] = -1;
     if (roots.empty()) return BO_OK;
     RT(rt_set_device(device));
-    MateRun R;
-    R.stream = stream; R.cap = capacity;
-    RT(rt_malloc((void **)&R.d_word, 16));
-    RT(rt_host_alloc((void **)&R.h_word, 16));
+    Walk R("bo_mate", stream, capacity);
+    MateWalk M{R};
+    rc = R.words();
+    if (rc) return rc;
     std::vector<MateRoot> out;
     std::vector<int32_t> moves;
-    int rc = mate_solve(R, roots, max_moves, max_nodes, out, moves);
-    if (!rc && (flags & BO_MATE_PV)) rc = mate_pv(R, roots, out, index, W, pv);
+    rc = mate_solve(M, roots, max_moves, max_nodes, out, moves);
+    if (!rc && (flags & BO_MATE_PV)) rc = mate_pv(M, roots, out, index, W, pv);
     if (rc) return rc;
     for (size_t r = 0; r < roots.size(); r++) {
         const size_t i = (size_t)index[r];
@@ -3624,96 +3671,55 @@ extern "C" int bo_mate(int device, int32_t n_roots, const char *const *fens, con
 // values are backed up into the parents it came from.  Every level keeps one int16 per entry; level 0 holds the roots that have a move.
 // With quiescence Q > 0 (bo_anchor_q) the walk has D + Q levels: 0 .. D - 1 full width, D .. D + Q - 1 over the tactical moves only.
 namespace {
-struct AnchorRun : PerftRun {
-    std::vector<int16_t *> val;  // per level [have_val]
-    std::vector<int64_t> have_val;
-    // per root [n]: check bits, row in root_moves, score row [256], score, number of best moves, lowest-index best move
-    int32_t *root_chk = nullptr, *act = nullptr, *scores = nullptr, *score = nullptr, *n_best = nullptr, *best = nullptr, *n_act = nullptr;
-    uint64_t visited = 0;  // frontier entries of levels 0 .. D + Q - 1 (include/betaone_engine.h: nodes)
-    int quiesce = 0;       // Q; `depth` is D
-    int levels() const { return depth + quiesce; }
-    ~AnchorRun() {
-        (void)rt_sync(stream);
-        for (int16_t *p : val) rt_free(p);
-        rt_free(root_chk); rt_free(act); rt_free(scores); rt_free(score); rt_free(n_best); rt_free(best); rt_free(n_act);
-    }
-    int room_anchor(int l, int64_t n) {
-        int rc = room(l, n);
-        if (!rc) rc = room_scan(l, n);
-        const int64_t m = lv[l].have;
-        if (rc || have_val[l] >= m) return rc;
-        rt_free(val[l]);
-        val[l] = nullptr; have_val[l] = 0;
-        rc = rt_malloc((void **)&val[l], (size_t)m * 2);
-        if (!rc) have_val[l] = m;
-        return rc;
-    }
-};
-
-int anchor_backup(AnchorRun &R, int l, int64_t a, int64_t e) {
-    PerftLevel &L = R.lv[l];
-    const int16_t *below = l + 1 < R.levels() ? R.val[l + 1] : nullptr;
-    if (l == 0)
-        RT(RT_LAUNCH(bo_k_anchor_backup_root, e - a, R.stream, (const int32_t *)R.n_act, (const uint64_t *)L.off, a, below, R.scores, R.score,
-                     R.n_best, R.best, (const int32_t *)R.act, (const int32_t *)R.root_moves));
-    else if (l >= R.depth)  // a quiescence level: the entry's own value (the floor) stands unless a tactical move beats it
-        RT(RT_LAUNCH(bo_k_anchor_backup_q, e - a, R.stream, (const int32_t *)L.cnt, (const uint64_t *)L.off, a, below, R.val[l]));
-    else
-        RT(RT_LAUNCH(bo_k_anchor_backup, e - a, R.stream, (const int32_t *)L.cnt, (const uint64_t *)L.off, a, below, R.val[l]));
-    return BO_OK;
-}
-
-// the values of entries [0, n) of level l (R.room_anchor(l, n) has been called)
-int anchor_level(AnchorRun &R, int l, int64_t n) {
-    PerftLevel &L = R.lv[l];
-    R.visited += (uint64_t)n;
-    const bool quiet = l >= R.depth;  // a quiescence level (Q > 0 only): its children are the tactical moves
-    if (quiet && l == R.levels() - 1) {
-        RT(RT_LAUNCH(bo_k_anchor_qleaf, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], (int32_t)l));
+struct AnchorWalk {
+    Walk &R;
+    int enter(int l, int64_t n, bool *bottom) {
+        WalkLevel &L = R.lv[l];
+        R.visited += (uint64_t)n;
+        const bool quiet = l >= R.depth;  // a quiescence level (Q > 0 only): its children are the tactical moves
+        *bottom = l == R.levels() - 1;
+        if (*bottom && quiet) RT(RT_LAUNCH(bo_k_anchor_qleaf, n, R.stream, (const DPos *)L.pos.p, L.cnt.p, L.val.p, (int32_t)l));
+        else if (*bottom)
+            RT(RT_LAUNCH(bo_k_anchor_leaf, n, R.stream, (const DPos *)L.pos.p, L.cnt.p, L.val.p, l == 0 ? R.scores.p : (int32_t *)nullptr, (int32_t)l,
+                         l == 0 ? AN_ROOT : 0u));
+        else if (quiet) RT(RT_LAUNCH(bo_k_anchor_qcount, n, R.stream, (const DPos *)L.pos.p, L.cnt.p, L.val.p, (int32_t)l));
+        else RT(RT_LAUNCH(bo_k_anchor_count, n, R.stream, (const DPos *)L.pos.p, L.cnt.p, L.val.p, (int32_t)l));
         return BO_OK;
     }
-    if (l == R.levels() - 1) {
-        RT(RT_LAUNCH(bo_k_anchor_leaf, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], l == 0 ? R.scores : (int32_t *)nullptr, (int32_t)l,
-                     l == 0 ? AN_ROOT : 0u));
-        return l == 0 ? anchor_backup(R, 0, 0, n) : BO_OK;
-    }
-    if (quiet) RT(RT_LAUNCH(bo_k_anchor_qcount, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], (int32_t)l));
-    else RT(RT_LAUNCH(bo_k_anchor_count, n, R.stream, (const DPos *)L.pos, L.cnt, R.val[l], (int32_t)l));
-    int rc = R.scan(l, n);
-    if (rc) return rc;
-    int64_t left = R.h_word[0], a = 0;
-    while (a < n && left > 0) {
-        int64_t e = n, c = left;
-        if (left > R.cap) {
-            RT(RT_LAUNCH(bo_k_perft_split, 1, R.stream, (const uint64_t *)L.off, a, n, R.cap, R.d_word));
-            RT(rt_d2h(R.h_word, R.d_word, 16, R.stream));
-            RT(rt_sync(R.stream));
-            e = R.h_word[0];
-            c = R.h_word[1];
-            if (e <= a || e > n || c < 1 || c > R.cap) return fail(BO_E_STATE, "bo_anchor: the level split is inconsistent");
-            if (c < left) R.splits++;
-        }
-        RT(R.room_anchor(l + 1, c));
-        PerftLevel &C = R.lv[l + 1];
-        if (quiet) RT(RT_LAUNCH(bo_k_anchor_qexpand, e - a, R.stream, (const DPos *)L.pos, (const uint64_t *)L.off, a, C.pos, C.tag, C.have));
-        else
-            RT(RT_LAUNCH(bo_k_perft_expand, e - a, R.stream, (const DPos *)L.pos, (const int32_t *)L.tag, (const uint64_t *)L.off, a, C.pos, C.tag,
-                         C.have, 0u));
-        rc = anchor_level(R, l + 1, c);
-        if (!rc) rc = anchor_backup(R, l, a, e);
+    int room(int l, int64_t n) {
+        int rc = R.room(l, n);
+        if (!rc) rc = R.room_scan(l, n);
         if (rc) return rc;
-        left -= c;
-        a = e;
+        RT(R.lv[l].val.room(R.lv[l].pos.n));
+        return BO_OK;
     }
-    if (l == 0 && a < n) return fail(BO_E_STATE, "bo_anchor: a root with moves has no children");
-    return BO_OK;  // (entries behind the last child have no move, or no tactical one: they keep the count kernel's value)
-}
-
-bool anchor_record_ok(const bo_position &q, DPos *p) {
-    const bool fields = (q.turn == 0 || q.turn == 1) && q.castling <= 0xFu && q.ep_square >= -1 && q.ep_square <= 63 && q.ep_key >= -2 && q.ep_key <= 63;
-    if (fields) *p = from_abi(q);
-    return fields && mate_position_ok(*p);
-}
+    int expand(int l, int64_t a, int64_t e) {
+        WalkLevel &L = R.lv[l], &C = R.lv[l + 1];
+        if (l >= R.depth)
+            RT(RT_LAUNCH(bo_k_anchor_qexpand, e - a, R.stream, (const DPos *)L.pos.p, (const uint64_t *)L.off.p, a, C.pos.p, C.tag.p, C.pos.n));
+        else
+            RT(RT_LAUNCH(bo_k_perft_expand, e - a, R.stream, (const DPos *)L.pos.p, (const int32_t *)L.tag.p, (const uint64_t *)L.off.p, a, C.pos.p,
+                         C.tag.p, C.pos.n, 0u));
+        return BO_OK;
+    }
+    int backup(int l, int64_t a, int64_t e) {
+        WalkLevel &L = R.lv[l];
+        const int16_t *below = l + 1 < R.levels() ? R.lv[l + 1].val.p : nullptr;
+        if (l == 0)
+            RT(RT_LAUNCH(bo_k_anchor_backup_root, e - a, R.stream, (const int32_t *)R.n_act.p, (const uint64_t *)L.off.p, a, below, R.scores.p,
+                         R.score.p, R.n_best.p, R.best.p, (const int32_t *)R.act.p, (const int32_t *)R.root_moves.p));
+        else if (l >= R.depth)  // a quiescence level: the entry's own value (the floor) stands unless a tactical move beats it
+            RT(RT_LAUNCH(bo_k_anchor_backup_q, e - a, R.stream, (const int32_t *)L.cnt.p, (const uint64_t *)L.off.p, a, below, L.val.p));
+        else
+            RT(RT_LAUNCH(bo_k_anchor_backup, e - a, R.stream, (const int32_t *)L.cnt.p, (const uint64_t *)L.off.p, a, below, L.val.p));
+        return BO_OK;
+    }
+    // (below level 0, entries behind the last child have no move, or no tactical one: they keep the count kernel's value)
+    int after(int64_t a, int64_t n) {
+        if (R.levels() == 1) return backup(0, a, n);  // the roots are the leaves: their scores are the leaf kernel's
+        return fail(BO_E_STATE, "bo_anchor: a root with moves has no children");
+    }
+};
 
 // bo_anchor (quiesce 0, who "bo_anchor") and bo_anchor_q: one body; at quiesce 0 the kernels and the bytes are bo_anchor's
 int anchor_search(const std::string &who, int device, int32_t n_roots, const char *const *fens, const bo_position *positions, int32_t depth,
@@ -3724,81 +3730,59 @@ int anchor_search(const std::string &who, int device, int32_t n_roots, const cha
         return fail(BO_E_ARG, who + ": exactly one of fens and positions, n_roots <= 2^20");
     if (depth < 1 || depth > BO_ANCHOR_MAX_DEPTH) return fail(BO_E_ARG, who + ": depth must be 1 .. 8");
     if (quiesce < 0 || quiesce > BO_ANCHOR_MAX_QUIESCE) return fail(BO_E_ARG, who + ": quiesce must be 0 .. 8");
-    if (capacity < BO_MAX_MOVES || capacity > ((int64_t)1 << 26))
-        return fail(BO_E_CONFIG, who + ": capacity must be 256 (the children of one position) .. 2^26 positions per level");
+    int rc = capacity_ok(who, capacity);
+    if (rc) return rc;
     if (flags) return fail(BO_E_ARG, who + ": unknown flag bits");
     if (n_roots && !results) return fail(BO_E_ARG, who + ": results must be given");
     if (n_roots == 0) return BO_OK;
     const size_t N = (size_t)n_roots;
     std::vector<DPos> roots;     // the roots that are positions
     std::vector<int32_t> index;  // their rows in the caller's arrays
-    roots.reserve(N); index.reserve(N);
-    memset(results, 0, N * sizeof(bo_anchor_result));
-    for (size_t i = 0; i < N; i++) {
-        DPos p;
-        results[i].best = -1;
-        if (fens) {
-            if (!pgn_fen_root(fens[i] ? fens[i] : "", &p) || !mate_position_ok(p)) return fail(BO_E_FEN, who + ": bad FEN (root " + std::to_string(i) + ")");
-        } else if (!anchor_record_ok(positions[i], &p)) { results[i].status = BO_ANCHOR_NOT_A_POSITION; continue; }
-        roots.push_back(p);
-        index.push_back((int32_t)i);
-    }
+    rc = collect_roots(who, N, fens, positions, results, [](bo_anchor_result &o) { o.best = -1; }, BO_ANCHOR_NOT_A_POSITION, roots, index);
+    if (rc) return rc;
     for (size_t i = 0; i < N * BO_MAX_MOVES; i++) {
         if (root_moves) root_moves[i] = -1;
         if (move_scores) move_scores[i] = INT32_MIN;
     }
     if (roots.empty()) return BO_OK;
     RT(rt_set_device(device));
-    AnchorRun R;
-    R.stream = stream; R.cap = capacity; R.depth = depth; R.quiesce = quiesce;
-    R.lv.resize((size_t)R.levels()); R.val.resize((size_t)R.levels(), nullptr); R.have_val.resize((size_t)R.levels(), 0);
-    RT(rt_malloc((void **)&R.d_word, 16));
-    RT(rt_host_alloc((void **)&R.h_word, 16));
-    const size_t n = roots.size();
-    DPos *d_roots = nullptr;  // (freed below on every path: the roots kernel's in-place buffer)
-    RT(rt_malloc((void **)&R.root_moves, n * BO_MAX_MOVES * 4));
-    RT(rt_malloc((void **)&R.root_n, n * 4));
-    RT(rt_malloc((void **)&R.root_chk, n * 4));
-    RT(rt_malloc((void **)&R.act, n * 4));
-    RT(rt_malloc((void **)&R.n_act, n * 4));
-    RT(rt_malloc((void **)&R.scores, n * BO_MAX_MOVES * 4));
-    RT(rt_malloc((void **)&R.score, n * 4));
-    RT(rt_malloc((void **)&R.n_best, n * 4));
-    RT(rt_malloc((void **)&R.best, n * 4));
-    RT(rt_malloc((void **)&d_roots, n * sizeof(DPos)));
-    std::vector<int32_t> moves(n * BO_MAX_MOVES), rn(n), chk(n);
-    int rc = rt_h2d(d_roots, roots.data(), n * sizeof(DPos), stream);
-    if (!rc) rc = RT_LAUNCH(bo_k_mate_roots, n, stream, d_roots, R.root_moves, R.root_n, R.root_chk);
-    if (!rc) rc = rt_d2h(roots.data(), d_roots, n * sizeof(DPos), stream);
-    if (!rc) rc = rt_d2h(moves.data(), R.root_moves, moves.size() * 4, stream);
-    if (!rc) rc = rt_d2h(rn.data(), R.root_n, n * 4, stream);
-    if (!rc) rc = rt_d2h(chk.data(), R.root_chk, n * 4, stream);
-    if (!rc) rc = rt_sync(stream);
-    rt_free(d_roots);
-    RT(rc);
-    std::vector<int32_t> active, nact;  // the roots that are searched: a position with a move
+    Walk R("bo_anchor", stream, capacity);
+    AnchorWalk A{R};
+    R.depth = depth; R.quiesce = quiesce;
+    R.lv.resize((size_t)R.levels());
+    rc = R.words();
+    if (rc) return rc;
+    const int64_t n = (int64_t)roots.size();
+    RT(R.n_act.alloc(n));
+    RT(R.scores.alloc(n * BO_MAX_MOVES));
+    RT(R.score.alloc(n));
+    RT(R.n_best.alloc(n));
+    RT(R.best.alloc(n));
+    std::vector<int32_t> moves, rn, chk, active, nact;
+    rc = prepare_roots(R, roots, moves, rn, chk, active);
+    if (rc) return rc;
     std::vector<DPos> sub;
-    for (size_t r = 0; r < n; r++)
-        if (!(chk[r] & 2) && rn[r] > 0) { active.push_back((int32_t)r); nact.push_back(rn[r]); sub.push_back(roots[r]); }
+    for (int32_t r : active) { nact.push_back(rn[(size_t)r]); sub.push_back(roots[(size_t)r]); }
     const size_t na = active.size();
     std::vector<int32_t> sc(na * BO_MAX_MOVES), s1(na), nb(na), bm(na);
     if (na) {
-        RT(R.room_anchor(0, (int64_t)na));
-        std::vector<int32_t> tags(na, 0);
-        RT(rt_h2d(R.lv[0].pos, sub.data(), na * sizeof(DPos), stream));
-        RT(rt_h2d(R.lv[0].tag, tags.data(), na * 4, stream));
-        RT(rt_h2d(R.act, active.data(), na * 4, stream));
-        RT(rt_h2d(R.n_act, nact.data(), na * 4, stream));
-        RT(rt_sync(stream));  // (host vectors of this frame)
-        rc = anchor_level(R, 0, (int64_t)na);
+        rc = A.room(0, (int64_t)na);
         if (rc) return rc;
-        RT(rt_d2h(sc.data(), R.scores, sc.size() * 4, stream));
-        RT(rt_d2h(s1.data(), R.score, na * 4, stream));
-        RT(rt_d2h(nb.data(), R.n_best, na * 4, stream));
-        RT(rt_d2h(bm.data(), R.best, na * 4, stream));
+        std::vector<int32_t> tags(na, 0);
+        RT(rt_h2d(R.lv[0].pos.p, sub.data(), na * sizeof(DPos), stream));
+        RT(rt_h2d(R.lv[0].tag.p, tags.data(), na * 4, stream));
+        RT(rt_h2d(R.act.p, active.data(), na * 4, stream));
+        RT(rt_h2d(R.n_act.p, nact.data(), na * 4, stream));
+        RT(rt_sync(stream));  // (host vectors of this frame)
+        rc = walk_level(R, A, 0, (int64_t)na);
+        if (rc) return rc;
+        RT(rt_d2h(sc.data(), R.scores.p, sc.size() * 4, stream));
+        RT(rt_d2h(s1.data(), R.score.p, na * 4, stream));
+        RT(rt_d2h(nb.data(), R.n_best.p, na * 4, stream));
+        RT(rt_d2h(bm.data(), R.best.p, na * 4, stream));
         RT(rt_sync(stream));
     }
-    for (size_t r = 0; r < n; r++) {
+    for (size_t r = 0; r < (size_t)n; r++) {
         bo_anchor_result &o = results[(size_t)index[r]];
         if (chk[r] & 2) o.status = BO_ANCHOR_NOT_A_POSITION;
         else if (rn[r] == 0) o.status = (chk[r] & 1) ? BO_ANCHOR_CHECKMATED : BO_ANCHOR_STALEMATED;
@@ -3838,23 +3822,22 @@ extern "C" int bo_anchor_eval(int device, int32_t n, const bo_position *position
     for (int32_t i = 0; i < n; i++) {
         DPos p;
         ev_out[i] = INT32_MIN;
-        if (!anchor_record_ok(positions[i], &p)) continue;
+        if (!record_ok(positions[i], &p)) continue;
         pos.push_back(p);
         index.push_back(i);
     }
     if (pos.empty()) return BO_OK;
     RT(rt_set_device(device));
     const size_t m = pos.size();
-    DPos *d_pos = nullptr;
-    int32_t *d_out = nullptr;
+    DevBuf<DPos> d_pos;
+    DevBuf<int32_t> d_out;
     std::vector<int32_t> out(m);
-    int rc = rt_malloc((void **)&d_pos, m * sizeof(DPos));
-    if (!rc) rc = rt_malloc((void **)&d_out, m * 4);
-    if (!rc) rc = rt_h2d(d_pos, pos.data(), m * sizeof(DPos), stream);
-    if (!rc) rc = RT_LAUNCH(bo_k_anchor_eval, m, stream, (const DPos *)d_pos, d_out);
-    if (!rc) rc = rt_d2h(out.data(), d_out, m * 4, stream);
-    const int rs = rt_sync(stream);
-    rt_free(d_pos); rt_free(d_out);
+    int rc = d_pos.alloc((int64_t)m);
+    if (!rc) rc = d_out.alloc((int64_t)m);
+    if (!rc) rc = rt_h2d(d_pos.p, pos.data(), m * sizeof(DPos), stream);
+    if (!rc) rc = RT_LAUNCH(bo_k_anchor_eval, m, stream, (const DPos *)d_pos.p, d_out.p);
+    if (!rc) rc = rt_d2h(out.data(), d_out.p, m * 4, stream);
+    const int rs = rt_sync(stream);  // nothing returns between the allocations and here: the stream is idle when the two buffers go
     RT(rc);
     RT(rs);
     for (size_t k = 0; k < m; k++) ev_out[index[k]] = out[k];
